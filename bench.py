@@ -25,7 +25,11 @@ Layouts (``--layout``):
   * ``tp`` — model parallelism first: N=2 tp2, N=4 tp2pp2, N=8 tp2pp2dp2 (+SP).
   ``--tp/--pp`` override any layout. The JSON line names the layout and its parallelism.
 
-Self-explanation (``--comm-stats 1``, default): the JSON line carries ``phase_ms`` — the step split
+A plain run sets up, warms up, times ``--steps`` steps, writes ``--dump-outputs DIR`` if asked
+(the last timed step's losses and a fixed sample of its gradients and updated parameters as
+``.npy``) and prints the JSON line. Everything else it can measure needs ``--full``.
+
+Self-explanation (``--full``; ``--comm-stats 0`` turns it off): the JSON line carries ``phase_ms`` — the step split
 from CUDA events on the compute stream into forward/backward compute, TP-exchange wait, pipeline
 p2p wait + bubble, ZeRO parameter-gather wait, DP gradient sync, optimizer and the device idle gap
 between steps (comm/stats.py; the pieces sum to the step) — and ``comm``: per axis (tp / pp / dp /
@@ -106,7 +110,7 @@ def parse():
     p.add_argument("--vpp", type=int, default=1,
                    help="virtual pipeline chunks per rank (interleaved 1F1B; uniform layer split)")
     p.add_argument("--phase-probe", type=int, default=0,
-                   help="(pp = 1) after the timed steps, time this many micro-batches as F / B / W: forward, "
+                   help="(--full, pp = 1) after the timed steps, time this many micro-batches as F / B / W: forward, "
                         "backward with the weight-gradient GEMMs held, then those GEMMs "
                         "(train/pipeline_sim.py inputs); reported as fbw_ms")
     p.add_argument("--hidden-dropout", type=float, default=0.1)
@@ -120,7 +124,7 @@ def parse():
                         "with the next step's forward (DistributedDataParallel.overlap_optimizer)")
     p.add_argument("--bucket-size", type=int, default=None,
                    help="DDP bucket elements (default: auto, 8-32 MB from a start-up link timing)")
-    p.add_argument("--comm-stats", type=int, default=1, help="phase_ms / per-collective stats in the JSON")
+    p.add_argument("--comm-stats", type=int, default=1, help="(--full) phase_ms / per-collective stats in the JSON")
     p.add_argument("--no-flash", action="store_true")
     p.add_argument("--recompute", choices=["none", "full"], default="none")
     p.add_argument("--profile-steps", type=int, default=0)
@@ -134,7 +138,20 @@ def parse():
                    help="autotune torch's hipBLASLt GEMMs per shape during the (untimed) warmup")
     p.add_argument("--tune-ms", type=int, default=40)
     p.add_argument("--tune-out", type=str, default=None)
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="everything beyond the headline figure: the phase_ms / comm breakdown (--comm-stats, "
+                        "two extra steps after the timed ones) and the F / B / W probe (--phase-probe). "
+                        "Without it the run sets up, warms up, times --steps steps and prints the result line")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, write what the last of them computed as DIR/<name>.npy "
+                        "(float32): its micro-batch losses and a fixed, seeded sample of the reduced "
+                        "gradients and of the updated parameters (dump_outputs)")
+    a = p.parse_args()
+    if not a.full:
+        if a.phase_probe:
+            print("[bench] --phase-probe needs --full; skipped", file=sys.stderr)
+        a.comm_stats, a.phase_probe = 0, 0
+    return a
 
 
 TUNED_GEMMS = os.environ.get("SMDT_TUNED_GEMMS") or os.path.join(
@@ -460,7 +477,9 @@ def main():
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el.item())
     ms_step = 1000 * elapsed / a.steps
-    # phase_ms / comm come from two extra steps after the timed ones: the per-collective events
+    if a.dump_outputs and rank == 0:   # before any further step touches the gradients / parameters
+        dump_outputs(a.dump_outputs, last, ddp, opt)
+    # (--full) phase_ms / comm come from two extra steps after the timed ones: the per-collective events
     # and phase marks cost ~3 % of a step at the N = 8 rank's ~4 k launches per step (207.6 vs
     # 201.8 ms, profiles/r4_comm_stats_cost/), so the timed steps run without them
     if a.comm_stats and not cpu_stats:
@@ -550,6 +569,35 @@ def main():
         print(json.dumps(rec), flush=True)
     if dist.is_initialized():
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 2 * 1024 * 1024   # elements kept of each flat buffer (8 MB as float32)
+
+
+def dump_outputs(out_dir, last, ddp, opt):
+    """--dump-outputs: what the last timed step left with its caller, as float32 ``.npy`` files
+    (rank 0's view): ``loss`` — its micro-batch losses (absent on a rank without the loss) —, and
+    ``grads`` / ``params`` / ``master_params`` — the reduced gradients, the updated 16-bit
+    parameters and their fp32 masters. A flat buffer longer than DUMP_SAMPLE elements is written
+    as a sample at fixed positions (drawn once from a CPU generator seeded with its length), so two
+    builds run with the same arguments write comparable arrays."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def sample(flat):
+        n = flat.numel()
+        if n > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(n)
+            idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        return flat.detach().float().cpu().numpy()
+
+    if last:
+        loss = torch.stack([d["lm loss"].detach().float().reshape(()) for d in last])
+        np.save(os.path.join(out_dir, "loss.npy"), loss.cpu().numpy())
+    for name, buf in (("grads", ddp.grad_data), ("params", ddp.param_data), ("master_params", opt.master)):
+        if isinstance(buf, torch.Tensor) and buf.numel():
+            np.save(os.path.join(out_dir, name + ".npy"), sample(buf.reshape(-1)))
 
 
 def _tp_flag(name):

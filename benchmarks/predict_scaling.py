@@ -107,7 +107,7 @@ def measure(steps: int, warmup: int, logdir: str, only=None) -> dict:
         if only and name not in only:
             continue
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup),
-               "--comm-stats", "1"] + extra
+               "--full", "--comm-stats", "1"] + extra
         env = dict(os.environ, **RUN_ENV.get(name, {}))
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
         with open(os.path.join(logdir, f"{name}.log"), "w") as f:

@@ -44,7 +44,7 @@ def _run_bench(n, layout, tmp_path, extra=()):
     from _dist import free_port
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n),
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", str(n), "--layout", layout] + TINY + list(extra)
+           "--gpus", str(n), "--layout", layout, "--full"] + TINY + list(extra)
     r = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -123,6 +123,41 @@ def test_bench_emulated_tp_rank(tmp_path):
     assert rec["config"]["model"].endswith("vocab 256, seq 32)")   # padded to 128 x tp and rec["final_loss"] > 0
 
 
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full the line carries the headline fields only (no phase_ms / comm / fbw_ms, even
+    with --phase-probe given); --dump-outputs writes the last timed step's losses, gradients and
+    parameters as float32 .npy, identical from run to run on the deterministic CPU path."""
+    import numpy as np
+    env = dict(os.environ, CUDA_VISIBLE_DEVICES="", OMP_NUM_THREADS="1")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    recs = []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--phase-probe", "2",
+               "--dump-outputs", str(tmp_path / d)] + TINY
+        r = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        recs.append(json.loads(lines[0]))
+    rec = recs[0]
+    assert not {"phase_ms", "comm", "fbw_ms"} & set(rec)
+    assert rec["steps"] == 2 and rec["warmup"] == 1 and rec["ms_per_step"] > 0
+    assert rec["unit"] == "tokens/s" and rec["higher_is_better"] and rec["dtype"] == "bf16"
+    assert abs(rec["value"] - 4 * 32 / (rec["ms_per_step"] / 1e3)) <= 0.01 * rec["value"]
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["grads.npy", "loss.npy", "master_params.npy", "params.npy"]
+    total = 0
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype == np.float32 and x.size > 0 and np.isfinite(x).all()
+        assert np.array_equal(x, y), n
+        total += x.nbytes
+    assert total <= 64 * 2 ** 20
+    assert abs(float(np.load(tmp_path / "a" / "loss.npy").mean()) - rec["final_loss"]) < 1e-6
+    assert np.abs(np.load(tmp_path / "a" / "grads.npy")).max() > 0
+
+
 @pytest.mark.parametrize("stage", ["--emulate-first-stage", "--emulate-last-stage"])
 def test_bench_emulated_pipeline_stage(tmp_path, stage):
     """The per-stage emulations predict_scaling.py times: the first stage without the LM head, the
@@ -131,7 +166,7 @@ def test_bench_emulated_pipeline_stage(tmp_path, stage):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--emulate-tp", "2", "--micro-batch-size", "2",
-           "--grad-accum", "2", "--phase-probe", "2", stage] + TINY
+           "--grad-accum", "2", "--full", "--phase-probe", "2", stage] + TINY
     r = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
