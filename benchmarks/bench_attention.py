@@ -2,6 +2,11 @@
 
 python benchmarks/bench_attention.py [--b 16 --h 16 --s 1024 --d 64 --causal 1]
 Reports fwd / bwd times and TFLOP/s (causal FLOPs counted as half of the dense 4*B*H*S^2*D).
+
+--doc-len N: per-document attention (``doc_start``) with a document boundary every N tokens
+(N >= S: one document, i.e. the DOC kernels on plain causal work) next to the plain causal kernels
+on the same tensors, the two alternating over --repeats rounds; reports each side's median and
+min / max over the rounds and the doc / causal ratios.
 """
 import argparse
 import json
@@ -42,6 +47,36 @@ def timeit(fn, iters=20, warm=5):
     return ts[len(ts) // 2]
 
 
+def doc_compare(a, q, k, v, do):
+    """Plain causal vs per-document attention, alternating in one process (same tensors)."""
+    B, S, H, D = q.shape
+    ar = torch.arange(S, device="cuda", dtype=torch.int32)
+    n = min(a.doc_len, S)
+    ds = ((ar // n) * n).unsqueeze(0).expand(B, S).contiguous()
+    scale = 1 / math.sqrt(D)
+    outs = {"causal": SF.flash_attention(q, k, v, scale, True, dropout_p=a.dropout),
+            "doc": SF.flash_attention(q, k, v, scale, True, dropout_p=a.dropout, doc_start=ds)}
+    fwd = {"causal": lambda: SF.flash_attention(q, k, v, scale, True, dropout_p=a.dropout),
+           "doc": lambda: SF.flash_attention(q, k, v, scale, True, dropout_p=a.dropout, doc_start=ds)}
+    ts = {(w, d): [] for w in ("causal", "doc") for d in ("fwd", "bwd")}
+    for _ in range(a.repeats):
+        for w in ("causal", "doc"):
+            ts[w, "fwd"].append(timeit(fwd[w]))
+            ts[w, "bwd"].append(timeit(lambda: torch.autograd.grad(outs[w], (q, k, v), do, retain_graph=True)))
+    # (query, key) pairs each side has to visit, as a share of the dense S x S
+    docs = [(i, min(i + n, S)) for i in range(0, S, n)]
+    res = {"shape": [B, S, H, k.shape[2], D], "dropout": a.dropout, "doc_len": a.doc_len, "repeats": a.repeats,
+           "pairs_doc_over_causal": sum((e - s) * (e - s + 1) / 2 for s, e in docs) / (S * (S + 1) / 2)}
+    for (w, d), x in ts.items():
+        x = sorted(x)
+        res[f"{w}_{d}_ms"] = {"median": x[len(x) // 2], "min": x[0], "max": x[-1]}
+    for d in ("fwd", "bwd"):
+        res[f"doc_over_causal_{d}"] = res[f"doc_{d}_ms"]["median"] / res[f"causal_{d}_ms"]["median"]
+    if n >= S:
+        res["single_doc_equal_out"] = bool(torch.equal(outs["causal"], outs["doc"])) if a.dropout == 0 else None
+    print(json.dumps(res), flush=True)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--b", type=int, default=16)
@@ -53,6 +88,9 @@ def main():
     p.add_argument("--sdpa", type=int, default=1)
     p.add_argument("--dropout", type=float, default=0.0)
     p.add_argument("--ext", default=None, help="alternate _C.so for A/B runs")
+    p.add_argument("--doc-len", type=int, default=0,
+                   help="per-document attention with a boundary every N tokens, next to plain causal")
+    p.add_argument("--repeats", type=int, default=5, help="--doc-len: alternating rounds per side")
     a = p.parse_args()
     B, H, S, D = a.b, a.h, a.s, a.d
     Hkv = a.hkv or H
@@ -62,6 +100,8 @@ def main():
     v = torch.randn(B, S, Hkv, D, device="cuda", dtype=torch.bfloat16, requires_grad=True)
     do = torch.randn(B, S, H, D, device="cuda", dtype=torch.bfloat16)
     flops = 4 * B * H * S * S * D * (0.5 if a.causal else 1.0)
+    if a.doc_len > 0:
+        return doc_compare(a, q, k, v, do)
     res = {"shape": [B, S, H, Hkv, D], "causal": bool(a.causal), "dropout": a.dropout}
 
     def ours_f():

@@ -34,7 +34,7 @@ from smdt_amd.parallel import tensor_parallel  # noqa: E402
 from smdt_amd.train.arguments import core_transformer_config_from_args, get_args, get_timers, get_tokenizer  # noqa: E402
 from smdt_amd.train.training import ModelType, pretrain  # noqa: E402
 from smdt_amd.train.utils import (average_losses_across_data_parallel_group, context_parallel_slice,  # noqa: E402
-                                  get_ltor_masks_and_position_ids)
+                                  document_starts, get_ltor_masks_and_position_ids)
 
 
 def model_provider(pre_process=True, post_process=True):
@@ -56,13 +56,16 @@ def get_batch(data_iterator):
     tokens_ = b["text"].long()
     labels = tokens_[:, 1:].contiguous()
     tokens = tokens_[:, :-1].contiguous()
-    need_mask = args.reset_attention_mask or not args.use_flash_attn
+    # --reset-attention-mask: the model takes the per-token document start (b s integers, made on
+    # the device); the dense [b, 1, s, s] mask is built only for the unfused path's signature
+    dense = not args.use_flash_attn
     attention_mask, loss_mask, position_ids = get_ltor_masks_and_position_ids(
-        tokens, tokenizer.eod, args.reset_position_ids, args.reset_attention_mask, args.eod_mask_loss,
-        build_attention_mask=need_mask)
+        tokens, tokenizer.eod, args.reset_position_ids, args.reset_attention_mask and dense, args.eod_mask_loss,
+        build_attention_mask=dense)
+    doc_start = document_starts(tokens, tokenizer.eod) if args.reset_attention_mask else None
     # --context-parallel-size: this rank keeps its contiguous chunk of the sequence
     tokens, labels, loss_mask, position_ids = context_parallel_slice(tokens, labels, loss_mask, position_ids)
-    return tokens, labels, loss_mask, attention_mask, position_ids
+    return tokens, labels, loss_mask, attention_mask, position_ids, doc_start
 
 
 def loss_func(loss_mask, output_tensor):
@@ -77,10 +80,14 @@ def forward_step(data_iterator, model):
     """Forward step."""
     timers = get_timers()
     timers("batch-generator", log_level=2).start()
-    tokens, labels, loss_mask, attention_mask, position_ids = get_batch(data_iterator)
+    tokens, labels, loss_mask, attention_mask, position_ids, doc_start = get_batch(data_iterator)
     timers("batch-generator").stop()
     # the loss mask tells the fused LM head + CE the reduction loss_func applies
-    output_tensor = model(tokens, position_ids, attention_mask, labels=labels, loss_mask=loss_mask)
+    if doc_start is None:
+        output_tensor = model(tokens, position_ids, attention_mask, labels=labels, loss_mask=loss_mask)
+    else:
+        output_tensor = model(tokens, position_ids, attention_mask, labels=labels, loss_mask=loss_mask,
+                              doc_start=doc_start)
     return output_tensor, partial(loss_func, loss_mask)
 
 

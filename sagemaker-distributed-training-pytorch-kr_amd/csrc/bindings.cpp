@@ -608,10 +608,22 @@ void fa_check(const Tensor& t, const char* n) {
               "flash: '", n, "' must keep 16-byte row alignment");
 }
 
+// Per-document descriptor (doc_start / doc_end): int32, contiguous [B, S], on q's device.
+const int* fa_doc_ptr(const OptT& d, const Tensor& q, const char* n) {
+  if (!d) return nullptr;
+  need_cuda(*d, n);
+  TORCH_CHECK(d->scalar_type() == at::kInt, "flash: '", n, "' must be int32");
+  TORCH_CHECK(d->dim() == 2 && d->size(0) == q.size(0) && d->size(1) == q.size(1) && d->is_contiguous(),
+              "flash: '", n, "' must be a contiguous [B, S] tensor");
+  TORCH_CHECK(d->device() == q.device(), "flash: '", n, "' is on another device than q");
+  return d->data_ptr<int>();
+}
+
 // `out` (optional) is a preallocated [B, S, H, D] view with any strides (e.g. the [s, b, h]
-// activation layout used by the transformer trunk).
+// activation layout used by the transformer trunk). `doc_start` (optional, causal only) selects the
+// per-document kernels.
 std::vector<Tensor> flash_fwd(Tensor q, Tensor k, Tensor v, double scale, bool causal, OptT out,
-                              double dropout_p, int64_t seed, int64_t offset) {
+                              double dropout_p, int64_t seed, int64_t offset, OptT doc_start) {
   fa_check(q, "q"); fa_check(k, "k"); fa_check(v, "v");
   TORCH_CHECK(k.scalar_type() == q.scalar_type() && v.scalar_type() == q.scalar_type(), "flash: q/k/v dtypes differ");
   const int64_t B = q.size(0), S = q.size(1), H = q.size(2), D = q.size(3), Hkv = k.size(2);
@@ -627,6 +639,16 @@ std::vector<Tensor> flash_fwd(Tensor q, Tensor k, Tensor v, double scale, bool c
   }
   auto lse = torch::empty({B, H, S}, q.options().dtype(at::kFloat));
   TORCH_CHECK(o.scalar_type() == q.scalar_type(), "flash: out dtype mismatch");
+  if (const int* ds = fa_doc_ptr(doc_start, q, "doc_start")) {
+    TORCH_CHECK(causal, "flash: doc_start needs causal attention");
+    check(smdt_flash_fwd_doc(dcode(q), q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
+                             lse.data_ptr<float>(), (int)B, (int)H, (int)Hkv, (int)S, (int)D, q.stride(0),
+                             q.stride(1), q.stride(2), k.stride(0), k.stride(1), k.stride(2), v.stride(0),
+                             v.stride(1), v.stride(2), o.stride(0), o.stride(1), o.stride(2), (float)scale,
+                             (float)dropout_p, (uint64_t)seed, (uint64_t)offset, ds, cur_stream()),
+          "flash_fwd_doc");
+    return {o, lse};
+  }
   check(smdt_flash_fwd(dcode(q), q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr<float>(),
                        (int)B, (int)H, (int)Hkv, (int)S, (int)D, q.stride(0), q.stride(1), q.stride(2),
                        k.stride(0), k.stride(1), k.stride(2), v.stride(0), v.stride(1), v.stride(2),
@@ -640,7 +662,7 @@ std::vector<Tensor> flash_fwd(Tensor q, Tensor k, Tensor v, double scale, bool c
 // views into one fused d(QKV) buffer so the QKV projection backward needs no concatenation.
 std::vector<Tensor> flash_bwd(Tensor q, Tensor k, Tensor v, Tensor o, Tensor dout, Tensor lse,
                               double scale, bool causal, OptT dq_out, OptT dk_out, OptT dv_out,
-                              double dropout_p, int64_t seed, int64_t offset) {
+                              double dropout_p, int64_t seed, int64_t offset, OptT doc_start, OptT doc_end) {
   fa_check(q, "q"); fa_check(k, "k"); fa_check(v, "v"); fa_check(o, "o");
   TORCH_CHECK(k.scalar_type() == q.scalar_type() && v.scalar_type() == q.scalar_type() &&
               o.scalar_type() == q.scalar_type() && dout.scalar_type() == q.scalar_type(), "flash_bwd: dtypes differ");
@@ -666,6 +688,18 @@ std::vector<Tensor> flash_bwd(Tensor q, Tensor k, Tensor v, Tensor o, Tensor dou
   const Tensor* ts[8] = {&q, &k, &v, &o, &dout, &dq, &dk, &dv};
   for (int i = 0; i < 8; ++i)
     for (int j = 0; j < 3; ++j) st[3 * i + j] = ts[i]->stride(j);
+  const int* ds = fa_doc_ptr(doc_start, q, "doc_start");
+  const int* de = fa_doc_ptr(doc_end, q, "doc_end");
+  TORCH_CHECK((ds == nullptr) == (de == nullptr), "flash_bwd: doc_start and doc_end come together");
+  if (ds) {
+    TORCH_CHECK(causal, "flash_bwd: doc_start needs causal attention");
+    check(smdt_flash_bwd_doc(dcode(q), q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), dout.data_ptr(),
+                             lse.data_ptr<float>(), delta.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(),
+                             dv.data_ptr(), (int)B, (int)H, (int)Hkv, (int)S, (int)D, st, (float)scale,
+                             (float)dropout_p, (uint64_t)seed, (uint64_t)offset, ds, de, cur_stream()),
+          "flash_bwd_doc");
+    return {dq, dk, dv};
+  }
   check(smdt_flash_bwd(dcode(q), q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), dout.data_ptr(),
                        lse.data_ptr<float>(), delta.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(),
                        dv.data_ptr(), (int)B, (int)H, (int)Hkv, (int)S, (int)D, st, (float)scale,
@@ -906,7 +940,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ce_fused", &ce_fused);
   namespace py = pybind11;
   m.def("flash_fwd", &flash_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"), py::arg("causal"),
-        py::arg("out") = py::none(), py::arg("dropout_p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0);
+        py::arg("out") = py::none(), py::arg("dropout_p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0,
+        py::arg("doc_start") = py::none());
   m.def("ipc_malloc", &ipc_malloc, py::arg("bytes"), py::arg("uncached"));
   m.def("ipc_free", &ipc_free);
   m.def("ipc_get_handle", &ipc_get_handle);
@@ -934,5 +969,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("relay_read_error", &relay_read_error);
   m.def("flash_bwd", &flash_bwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("dout"),
         py::arg("lse"), py::arg("scale"), py::arg("causal"), py::arg("dq") = py::none(), py::arg("dk") = py::none(),
-        py::arg("dv") = py::none(), py::arg("dropout_p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0);
+        py::arg("dv") = py::none(), py::arg("dropout_p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0,
+        py::arg("doc_start") = py::none(), py::arg("doc_end") = py::none());
 }

@@ -36,6 +36,15 @@
 // so the kernels read Q, K, V directly out of a fused QKV projection output. lse / delta are
 // fp32 [B, H, S]. Requirements (checked by the launcher): S % 128 == 0, D in {64, 128},
 // H % Hkv == 0, 16-byte aligned rows.
+//
+// DOC variants (per-document attention of packed samples, causal only): query q attends key k iff
+// doc_start[b, q] <= k <= q, with doc_start int32 [B, S] the index of the first token of q's
+// document (non-decreasing along s). The forward and dQ kernels start their K / V sweep at the
+// tile that holds doc_start of the block's first query and mask k < doc_start[q] on the tiles that
+// straddle a boundary; the dK / dV kernel uses the key-side twin doc_end[b, k] (one past the last
+// query of k's document, also non-decreasing): a key block stops its query sweep at doc_end of its
+// last key and masks q >= doc_end[k]. DOC is a template flag: the plain instantiations are
+// unchanged.
 #include <cmath>
 
 #include "common.h"
@@ -300,14 +309,16 @@ struct GldsTile {
 // ---------------------------------------------------------------------------------------
 // Forward. Workgroup = 4 waves = 128 query rows of one (b, h); K/V streamed in 64-key tiles,
 // double-buffered.
-template <int D, bool CAUSAL, bool DROP, class E>
+template <int D, bool CAUSAL, bool DROP, class E, bool DOC = false>
 __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fwd_kernel(const E* __restrict__ Q,
                                                      const E* __restrict__ K,
                                                      const E* __restrict__ V,
                                                      E* __restrict__ O, float* __restrict__ LSE,
                                                      int B, int H, int Hkv, int S, Strides qs,
                                                      Strides ks_, Strides vs, Strides os,
-                                                     float scale, Drop drop) {
+                                                     float scale, Drop drop,
+                                                     const int* __restrict__ DSTART = nullptr) {
+  static_assert(!DOC || CAUSAL, "per-document attention is causal");
   using G = Geo<D>;
   // Three [K | V] tile buffers (separate objects: the compiler sees that the LDS-DMA into one does
   // not alias the fragment reads of another, so it leaves the DMA queue alone).
@@ -368,6 +379,17 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fwd_kernel(const E* __re
 
   const int kend = CAUSAL ? (q0 + kBlockRows) : S;
   const int ntiles = kend / kTile;
+  // DOC: doc_start is non-decreasing along s, so the block's first key tile is the one that holds
+  // doc_start of its first query (<= q0, hence tfirst < ntiles); ds_lo / ds_hi bound the wave's 32
+  // rows (wave-uniform, SGPRs), ds_q is this lane's row.
+  int tfirst = 0, ds_q = 0, ds_lo = 0, ds_hi = 0;
+  if constexpr (DOC) {
+    const int* dsb = DSTART + (int64_t)b * S;
+    tfirst = min(max(__builtin_amdgcn_readfirstlane(dsb[q0]), 0), q0) / kTile;  // clamped: never past the block
+    ds_lo = __builtin_amdgcn_readfirstlane(dsb[qw]);
+    ds_hi = __builtin_amdgcn_readfirstlane(dsb[qw + 31]);
+    ds_q = dsb[my_q];
+  }
   const uint32_t dkey = DROP ? drop_key(drop, bh) : 0u;
   const uint32_t shalf = (uint32_t)S >> 1;
   // block counter of this lane's first hashed key pair (key rows 4 h .. ; odd queries hash the
@@ -385,8 +407,8 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fwd_kernel(const E* __re
     gv.issue(Vb + (int64_t)t * kTile * vs.ss, img + G::TB, w);
   };
   constexpr int kPer = 2 * GldsTile<D>::kPerWave;  // DMA wave-instructions per tile and wave
-  issue(0, L0);
-  if constexpr (kBuf == 3) issue(ntiles > 1 ? 1 : 0, L1);
+  issue(tfirst, L0);
+  if constexpr (kBuf == 3) issue(tfirst + 1 < ntiles ? tfirst + 1 : tfirst, L1);
   wait_vm<(kBuf - 2) * kPer>();
   __builtin_amdgcn_s_barrier();
 
@@ -396,7 +418,9 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fwd_kernel(const E* __re
     const int kb = t * kTile;
     const char* vt = kt + G::TB;
     issue(t + kBuf - 1 < ntiles ? t + kBuf - 1 : ntiles - 1, pre);
-    if (!CAUSAL || kb <= qw + 31) {
+    // DOC: a tile that ends before the earliest document of this wave's rows is skipped like the
+    // tiles past the diagonal
+    if ((!CAUSAL || kb <= qw + 31) && (!DOC || kb + kTile > ds_lo)) {
       // S^T tiles (log2 domain, minus m): rows = keys (registers), column = this lane's query.
       f32x16 st[2];
       auto scores = [&]() {
@@ -418,6 +442,15 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fwd_kernel(const E* __re
           };
           if (kb == qw) diag(0);
           else diag(-32);
+        }
+        if constexpr (DOC) {
+          if (kb < ds_hi) {  // the tile starts before the latest document of the wave's rows
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+              for (int i = 0; i < 16; ++i)
+                if (kb + 32 * tt + acc_row(i, h) < ds_q) st[tt][i] = -INFINITY;
+          }
         }
       };
       float rs0 = 0.f, rs1 = 0.f;  // two chains: the denominator uses the un-dropped p
@@ -444,7 +477,12 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fwd_kernel(const E* __re
       // exact row max, rescales and redoes the exponentials. Saves the ~21 max instructions per
       // tile of a per-tile max (the loop is VALU-issue-bound).
       float rsum = expsum();
-      const bool bad = !(rsum <= 0x1p64f) || (l == 0.f && rsum < 0x1p-64f);
+      // DOC: a row whose document starts past this tile has every score at -inf here (rsum = 0
+      // with l = 0): it must neither ask for the rescue nor move m (tmax = -inf would make
+      // alpha = exp2(+inf) and 0 * inf = NaN). Such a row keeps d = 0 below; every other visited
+      // tile holds at least the row's own key or its document's first key, as in the plain kernel.
+      const bool dead = DOC && kb + kTile <= ds_q;
+      const bool bad = !dead && (!(rsum <= 0x1p64f) || (l == 0.f && rsum < 0x1p-64f));
       if (__builtin_amdgcn_ballot_w64(bad) != 0) {
         scores();
         float tmax = st[0][0];
@@ -496,13 +534,13 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fwd_kernel(const E* __re
     __builtin_amdgcn_s_barrier();
   };
   if constexpr (kBuf == 3) {
-    for (int t = 0; t < ntiles; t += 3) {
+    for (int t = tfirst; t < ntiles; t += 3) {
       tile(t, L0, L2);
       if (t + 1 < ntiles) tile(t + 1, L1, L0);
       if (t + 2 < ntiles) tile(t + 2, L2, L1);
     }
   } else {
-    for (int t = 0; t < ntiles; t += 2) {
+    for (int t = tfirst; t < ntiles; t += 2) {
       tile(t, L0, L1);
       if (t + 1 < ntiles) tile(t + 1, L1, L0);
     }
@@ -561,12 +599,14 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fwd_kernel(const E* __re
 #ifndef SMDT_FA_DKDV_OCC
 #define SMDT_FA_DKDV_OCC 2
 #endif
-template <int D, bool CAUSAL, bool DROP, class E>
+template <int D, bool CAUSAL, bool DROP, class E, bool DOC = false>
 __global__ __launch_bounds__(256, D == 64 ? SMDT_FA_DKDV_OCC : 1) void bwd_dkdv_kernel(
     const E* __restrict__ Q, const E* __restrict__ K, const E* __restrict__ V,
     const E* __restrict__ dO, const E* __restrict__ RC3,
     const float* __restrict__ DELTA, E* __restrict__ dK, E* __restrict__ dV, int B, int H, int Hkv, int S,
-    Strides qs, Strides ks_, Strides vs, Strides dos, Strides dks, Strides dvs, float scale, Drop drop) {
+    Strides qs, Strides ks_, Strides vs, Strides dos, Strides dks, Strides dvs, float scale, Drop drop,
+    const int* __restrict__ DEND = nullptr) {
+  static_assert(!DOC || CAUSAL, "per-document attention is causal");
   using G = Geo<D>;
   using VF = v8_t<E>;
   // Q | dO | the tile's 64 query rows of the row constants as ONE 16-bit term row each (16 B,
@@ -630,7 +670,18 @@ __global__ __launch_bounds__(256, D == 64 ? SMDT_FA_DKDV_OCC : 1) void bwd_dkdv_
   const float c2 = scale * kLog2e;
 
   const int qstart = CAUSAL ? k0 : 0;
-  const int ntiles = (S - qstart) / kTile;
+  // DOC: doc_end (one past the last query of a key's document) is non-decreasing along s, so the
+  // sweep ends with the document of the block's last key (k0 + 128 <= that end <= S); de_lo /
+  // de_hi bound the wave's 32 keys (wave-uniform), de_k is this lane's key.
+  int qstop = S, de_k = 0, de_lo = 0, de_hi = 0;
+  if constexpr (DOC) {
+    const int* deb = DEND + (int64_t)b * S;
+    qstop = min(max(__builtin_amdgcn_readfirstlane(deb[k0 + kBlockRows - 1]), k0 + kBlockRows), S);  // clamped
+    de_lo = __builtin_amdgcn_readfirstlane(deb[kw]);
+    de_hi = __builtin_amdgcn_readfirstlane(deb[kw + 31]);
+    de_k = deb[my_key];
+  }
+  const int ntiles = DOC ? (qstop - qstart + kTile - 1) / kTile : (S - qstart) / kTile;
   const int total = ntiles * group;
 
   // Q / dO tiles and the tile's raw lse / delta rows stream in by LDS-DMA through a ring of kBuf
@@ -707,6 +758,12 @@ __global__ __launch_bounds__(256, D == 64 ? SMDT_FA_DKDV_OCC : 1) void bwd_dkdv_
         for (int j = 0; j < 4; ++j)
           if ((lane & 31) > 8 * g + 4 * h + j) sa[4 * g + j] = -1e30f;
     };
+    // DOC: queries at or past the end of this lane's key's document (S' was finite: p = 0 exactly)
+    auto doc_mask = [&](int qsub, f32x16& sa) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        if (qsub + acc_row(i, h) >= de_k) sa[i] = -1e30f;
+    };
     auto sd_mma = [&](int qs2, f32x16& sa, f32x16& pa) {
 #pragma unroll
       for (int kk = 0; kk < G::KS; ++kk) {
@@ -778,11 +835,15 @@ __global__ __launch_bounds__(256, D == 64 ? SMDT_FA_DKDV_OCC : 1) void bwd_dkdv_
     for (int qs2 = 0; qs2 < 2; ++qs2) {
       const int qsub = qb + 32 * qs2;
       if (CAUSAL && qsub + 31 < kw) continue;  // all queries precede all of this wave's keys
+      if (DOC && qsub >= de_hi) continue;      // all queries follow the documents of this wave's keys
       f32x16 sa, pa;
       v8_t<E> pb[2], db[2];
       sd_init(qs2, sa, pa);
       sd_mma(qs2, sa, pa);
       if (CAUSAL && qsub == kw) diag_mask(sa);  // the diagonal block: key > query is masked
+      if constexpr (DOC) {
+        if (qsub + 31 >= de_lo) doc_mask(qsub, sa);  // some key's document ends inside these queries
+      }
       softmax_ds(qs2, sa, pa, pb, db);
       acc_mma(qs2, pb, db);
     }
@@ -844,13 +905,14 @@ __global__ __launch_bounds__(256, D == 64 ? SMDT_FA_DKDV_OCC : 1) void bwd_dkdv_
 // ---------------------------------------------------------------------------------------
 // dQ. Workgroup = 4 waves = 128 query rows of one (b, h); K/V streamed in 64-key tiles,
 // double-buffered.
-template <int D, bool CAUSAL, bool DROP, class E>
+template <int D, bool CAUSAL, bool DROP, class E, bool DOC = false>
 __global__ __launch_bounds__(256, D == 64 ? SMDT_FA_DQ_OCC : 1) void bwd_dq_kernel(
     const E* __restrict__ Q, const E* __restrict__ K, const E* __restrict__ V,
     const E* __restrict__ dO, const E* __restrict__ O, const float* __restrict__ LSE,
     float* __restrict__ DELTA, E* __restrict__ RC3, E* __restrict__ dQ, int B, int H, int Hkv,
     int S, Strides qs, Strides ks_, Strides vs, Strides dos, Strides os, Strides dqs, float scale,
-    float dscale, float lsub, Drop drop) {
+    float dscale, float lsub, Drop drop, const int* __restrict__ DSTART = nullptr) {
+  static_assert(!DOC || CAUSAL, "per-document attention is causal");
   using G = Geo<D>;
   // D = 64: three [K | V] buffers, two tiles in flight; D = 128 (twice the bytes): two buffers,
   // so two workgroups still fit a CU's 160 KB of LDS.
@@ -947,6 +1009,15 @@ __global__ __launch_bounds__(256, D == 64 ? SMDT_FA_DQ_OCC : 1) void bwd_dq_kern
 
   const int kend = CAUSAL ? (q0 + kBlockRows) : S;
   const int ntiles = kend / kTile;
+  // DOC: first key tile and the wave's / lane's doc_start, as in the forward
+  int tfirst = 0, ds_q = 0, ds_lo = 0, ds_hi = 0;
+  if constexpr (DOC) {
+    const int* dsb = DSTART + (int64_t)b * S;
+    tfirst = min(max(__builtin_amdgcn_readfirstlane(dsb[q0]), 0), q0) / kTile;  // clamped: never past the block
+    ds_lo = __builtin_amdgcn_readfirstlane(dsb[qw]);
+    ds_hi = __builtin_amdgcn_readfirstlane(dsb[qw + 31]);
+    ds_q = dsb[my_q];
+  }
   // K/V tiles by LDS-DMA through a 3-buffer ring, two tiles in flight (as in the forward).
   GldsTile<D> gk, gv;
   gk.init(w, lane, ks_.ss);
@@ -956,8 +1027,8 @@ __global__ __launch_bounds__(256, D == 64 ? SMDT_FA_DQ_OCC : 1) void bwd_dq_kern
     gv.issue(Vb + (int64_t)t * kTile * vs.ss, img + G::TB, w);
   };
   constexpr int kPer = 2 * GldsTile<D>::kPerWave;
-  issue(0, L0);
-  if constexpr (kBuf == 3) issue(ntiles > 1 ? 1 : 0, L1);
+  issue(tfirst, L0);
+  if constexpr (kBuf == 3) issue(tfirst + 1 < ntiles ? tfirst + 1 : tfirst, L1);
   wait_vm<(kBuf - 2) * kPer>();
   __builtin_amdgcn_s_barrier();
 
@@ -983,6 +1054,13 @@ __global__ __launch_bounds__(256, D == 64 ? SMDT_FA_DQ_OCC : 1) void bwd_dq_kern
 #pragma unroll
       for (int i = 0; i < 16; ++i)
         if (ksub + acc_row(i, h) > my_q) st[i] = -1e30f;
+    };
+    // DOC: keys before the start of this lane's query's document (S' was finite: p = 0 exactly)
+    auto doc_mask = [&](int tt, f32x16& st) {
+      const int ksub = kb + 32 * tt;
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        if (ksub + acc_row(i, h) < ds_q) st[i] = -1e30f;
     };
     // dS^T into dpt (P' = exp2(S'); dropout: kept dP - delta', dropped -delta')
     auto soft = [&](int tt, const f32x16& st, f32x16& dpt) {
@@ -1024,9 +1102,13 @@ __global__ __launch_bounds__(256, D == 64 ? SMDT_FA_DQ_OCC : 1) void bwd_dq_kern
     for (int tt = 0; tt < 2; ++tt) {
       const int ksub = kb + 32 * tt;
       if (CAUSAL && ksub > qw + 31) continue;
+      if (DOC && ksub + 32 <= ds_lo) continue;  // all keys precede the documents of this wave's rows
       f32x16 st, dpt;
       sd(tt, st, dpt);
       if (CAUSAL && ksub + 31 > qw) diag_mask(tt, st);
+      if constexpr (DOC) {
+        if (ksub < ds_hi) doc_mask(tt, st);
+      }
       soft(tt, st, dpt);
       acc(tt, dpt);
     }
@@ -1035,13 +1117,13 @@ __global__ __launch_bounds__(256, D == 64 ? SMDT_FA_DQ_OCC : 1) void bwd_dq_kern
     __builtin_amdgcn_s_barrier();
   };
   if constexpr (kBuf == 3) {
-    for (int t = 0; t < ntiles; t += 3) {
+    for (int t = tfirst; t < ntiles; t += 3) {
       tile(t, L0, L2);
       if (t + 1 < ntiles) tile(t + 1, L1, L0);
       if (t + 2 < ntiles) tile(t + 2, L2, L1);
     }
   } else {
-    for (int t = 0; t < ntiles; t += 2) {
+    for (int t = tfirst; t < ntiles; t += 2) {
       tile(t, L0, L1);
       if (t + 1 < ntiles) tile(t + 1, L1, L0);
     }
@@ -1100,14 +1182,16 @@ static Drop make_drop(float p, uint64_t seed, uint64_t offset) {
   return d;
 }
 
-extern "C" hipError_t smdt_flash_fwd(int dtype, const void* q, const void* k, const void* v,
-                                     void* o, float* lse, int B, int H, int Hkv, int S, int D,
-                                     int64_t q_sb, int64_t q_ss, int64_t q_sh, int64_t k_sb,
-                                     int64_t k_ss, int64_t k_sh, int64_t v_sb, int64_t v_ss,
-                                     int64_t v_sh, int64_t o_sb, int64_t o_ss, int64_t o_sh,
-                                     float scale, int causal, float dropout_p, uint64_t seed,
-                                     uint64_t offset, hipStream_t st) {
+// doc_start (int32 [B, S], may be null): per-document attention, causal only.
+static hipError_t flash_fwd_impl(int dtype, const void* q, const void* k, const void* v,
+                                 void* o, float* lse, int B, int H, int Hkv, int S, int D,
+                                 int64_t q_sb, int64_t q_ss, int64_t q_sh, int64_t k_sb,
+                                 int64_t k_ss, int64_t k_sh, int64_t v_sb, int64_t v_ss,
+                                 int64_t v_sh, int64_t o_sb, int64_t o_ss, int64_t o_sh,
+                                 float scale, int causal, float dropout_p, uint64_t seed,
+                                 uint64_t offset, const int* doc_start, hipStream_t st) {
   if (!fa_shape_ok(dtype, H, Hkv, S, D) || dropout_p < 0.f || dropout_p >= 1.f) return hipErrorInvalidValue;
+  if (doc_start && !causal) return hipErrorInvalidValue;
   Strides qs{q_sb, q_ss, q_sh}, ks{k_sb, k_ss, k_sh}, vs{v_sb, v_ss, v_sh}, os{o_sb, o_ss, o_sh};
   dim3 grid((unsigned)((int64_t)B * H * (S / kBlockRows)));
   const Drop dr = make_drop(dropout_p, seed, offset);
@@ -1125,20 +1209,60 @@ extern "C" hipError_t smdt_flash_fwd(int dtype, const void* q, const void* k, co
   } while (0)
 #define SMDT_FA_FWD2(DD, CC) \
   do { if (drop) SMDT_FA_FWD(DD, CC, true); else SMDT_FA_FWD(DD, CC, false); } while (0)
-  if (D == 64) { if (causal) SMDT_FA_FWD2(64, true); else SMDT_FA_FWD2(64, false); }
+#define SMDT_FA_FWD_DOC(DD, DR)                                                                 \
+  do {                                                                                          \
+    if (dtype == 2)                                                                             \
+      hipLaunchKernelGGL((fwd_kernel<DD, true, DR, f16, true>), grid, dim3(256), 0, st,         \
+                         (const f16*)q, (const f16*)k, (const f16*)v, (f16*)o, lse, B, H, Hkv, S, qs, \
+                         ks, vs, os, scale, dr, doc_start);                                     \
+    else                                                                                        \
+      hipLaunchKernelGGL((fwd_kernel<DD, true, DR, bf16, true>), grid, dim3(256), 0, st,        \
+                         (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, lse, B, H, Hkv, S, \
+                         qs, ks, vs, os, scale, dr, doc_start);                                 \
+  } while (0)
+  if (doc_start) {
+    if (D == 64) { if (drop) SMDT_FA_FWD_DOC(64, true); else SMDT_FA_FWD_DOC(64, false); }
+    else { if (drop) SMDT_FA_FWD_DOC(128, true); else SMDT_FA_FWD_DOC(128, false); }
+  } else if (D == 64) { if (causal) SMDT_FA_FWD2(64, true); else SMDT_FA_FWD2(64, false); }
   else { if (causal) SMDT_FA_FWD2(128, true); else SMDT_FA_FWD2(128, false); }
+#undef SMDT_FA_FWD_DOC
 #undef SMDT_FA_FWD2
 #undef SMDT_FA_FWD
   return hipGetLastError();
 }
 
-extern "C" hipError_t smdt_flash_bwd(int dtype, const void* q, const void* k, const void* v,
-                                     const void* o, const void* dout, const float* lse,
-                                     float* delta, void* dq, void* dk, void* dv, int B, int H,
-                                     int Hkv, int S, int D, const int64_t* strides, float scale,
-                                     int causal, float dropout_p, uint64_t seed, uint64_t offset,
-                                     hipStream_t st) {
+extern "C" hipError_t smdt_flash_fwd(int dtype, const void* q, const void* k, const void* v,
+                                     void* o, float* lse, int B, int H, int Hkv, int S, int D,
+                                     int64_t q_sb, int64_t q_ss, int64_t q_sh, int64_t k_sb,
+                                     int64_t k_ss, int64_t k_sh, int64_t v_sb, int64_t v_ss,
+                                     int64_t v_sh, int64_t o_sb, int64_t o_ss, int64_t o_sh,
+                                     float scale, int causal, float dropout_p, uint64_t seed,
+                                     uint64_t offset, hipStream_t st) {
+  return flash_fwd_impl(dtype, q, k, v, o, lse, B, H, Hkv, S, D, q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, v_sb,
+                        v_ss, v_sh, o_sb, o_ss, o_sh, scale, causal, dropout_p, seed, offset, nullptr, st);
+}
+
+extern "C" hipError_t smdt_flash_fwd_doc(int dtype, const void* q, const void* k, const void* v,
+                                         void* o, float* lse, int B, int H, int Hkv, int S, int D,
+                                         int64_t q_sb, int64_t q_ss, int64_t q_sh, int64_t k_sb,
+                                         int64_t k_ss, int64_t k_sh, int64_t v_sb, int64_t v_ss,
+                                         int64_t v_sh, int64_t o_sb, int64_t o_ss, int64_t o_sh,
+                                         float scale, float dropout_p, uint64_t seed, uint64_t offset,
+                                         const int* doc_start, hipStream_t st) {
+  if (!doc_start) return hipErrorInvalidValue;
+  return flash_fwd_impl(dtype, q, k, v, o, lse, B, H, Hkv, S, D, q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, v_sb,
+                        v_ss, v_sh, o_sb, o_ss, o_sh, scale, 1, dropout_p, seed, offset, doc_start, st);
+}
+
+// doc_start / doc_end (int32 [B, S], both or neither): per-document attention, causal only.
+static hipError_t flash_bwd_impl(int dtype, const void* q, const void* k, const void* v,
+                                 const void* o, const void* dout, const float* lse,
+                                 float* delta, void* dq, void* dk, void* dv, int B, int H,
+                                 int Hkv, int S, int D, const int64_t* strides, float scale,
+                                 int causal, float dropout_p, uint64_t seed, uint64_t offset,
+                                 const int* doc_start, const int* doc_end, hipStream_t st) {
   if (!fa_shape_ok(dtype, H, Hkv, S, D) || dropout_p < 0.f || dropout_p >= 1.f) return hipErrorInvalidValue;
+  if ((doc_start == nullptr) != (doc_end == nullptr) || (doc_start && !causal)) return hipErrorInvalidValue;
   const Drop dr = make_drop(dropout_p, seed, offset);
   const bool drop = dropout_p > 0.f;
   // strides: 8 x (batch, seq, head) element strides for q, k, v, o, dO, dQ, dK, dV.
@@ -1168,10 +1292,49 @@ extern "C" hipError_t smdt_flash_bwd(int dtype, const void* q, const void* k, co
   do { if (dtype == 2) SMDT_FA_BWD_T(DD, CC, DR, f16); else SMDT_FA_BWD_T(DD, CC, DR, bf16); } while (0)
 #define SMDT_FA_BWD2(DD, CC) \
   do { if (drop) SMDT_FA_BWD(DD, CC, true); else SMDT_FA_BWD(DD, CC, false); } while (0)
-  if (D == 64) { if (causal) SMDT_FA_BWD2(64, true); else SMDT_FA_BWD2(64, false); }
+#define SMDT_FA_BWD_DOC_T(DD, DR, ET)                                                            \
+  do {                                                                                           \
+    hipLaunchKernelGGL((bwd_dq_kernel<DD, true, DR, ET, true>), gq, dim3(256), 0, st,            \
+                       (const ET*)q, (const ET*)k, (const ET*)v, (const ET*)dout, (const ET*)o,   \
+                       lse, delta, (ET*)rc3, (ET*)dq, B, H, Hkv, S, qs, ks, vs, dos, os, dqs,     \
+                       scale, dscale, lsub, dr, doc_start);                                       \
+    hipLaunchKernelGGL((bwd_dkdv_kernel<DD, true, DR, ET, true>), gkv, dim3(256), 0, st,         \
+                       (const ET*)q, (const ET*)k, (const ET*)v, (const ET*)dout, (const ET*)rc3, \
+                       delta, (ET*)dk, (ET*)dv, B, H, Hkv, S, qs, ks, vs, dos, dks, dvs, scale,   \
+                       dr, doc_end);                                                              \
+  } while (0)
+#define SMDT_FA_BWD_DOC(DD, DR) \
+  do { if (dtype == 2) SMDT_FA_BWD_DOC_T(DD, DR, f16); else SMDT_FA_BWD_DOC_T(DD, DR, bf16); } while (0)
+  if (doc_start) {
+    if (D == 64) { if (drop) SMDT_FA_BWD_DOC(64, true); else SMDT_FA_BWD_DOC(64, false); }
+    else { if (drop) SMDT_FA_BWD_DOC(128, true); else SMDT_FA_BWD_DOC(128, false); }
+  } else if (D == 64) { if (causal) SMDT_FA_BWD2(64, true); else SMDT_FA_BWD2(64, false); }
   else { if (causal) SMDT_FA_BWD2(128, true); else SMDT_FA_BWD2(128, false); }
+#undef SMDT_FA_BWD_DOC
+#undef SMDT_FA_BWD_DOC_T
 #undef SMDT_FA_BWD2
 #undef SMDT_FA_BWD
 #undef SMDT_FA_BWD_T
   return hipGetLastError();
+}
+
+extern "C" hipError_t smdt_flash_bwd(int dtype, const void* q, const void* k, const void* v,
+                                     const void* o, const void* dout, const float* lse,
+                                     float* delta, void* dq, void* dk, void* dv, int B, int H,
+                                     int Hkv, int S, int D, const int64_t* strides, float scale,
+                                     int causal, float dropout_p, uint64_t seed, uint64_t offset,
+                                     hipStream_t st) {
+  return flash_bwd_impl(dtype, q, k, v, o, dout, lse, delta, dq, dk, dv, B, H, Hkv, S, D, strides, scale,
+                        causal, dropout_p, seed, offset, nullptr, nullptr, st);
+}
+
+extern "C" hipError_t smdt_flash_bwd_doc(int dtype, const void* q, const void* k, const void* v,
+                                         const void* o, const void* dout, const float* lse,
+                                         float* delta, void* dq, void* dk, void* dv, int B, int H,
+                                         int Hkv, int S, int D, const int64_t* strides, float scale,
+                                         float dropout_p, uint64_t seed, uint64_t offset,
+                                         const int* doc_start, const int* doc_end, hipStream_t st) {
+  if (!doc_start || !doc_end) return hipErrorInvalidValue;
+  return flash_bwd_impl(dtype, q, k, v, o, dout, lse, delta, dq, dk, dv, B, H, Hkv, S, D, strides, scale, 1,
+                        dropout_p, seed, offset, doc_start, doc_end, st);
 }

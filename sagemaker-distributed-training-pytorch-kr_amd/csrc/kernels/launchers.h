@@ -108,6 +108,19 @@ hipError_t smdt_flash_bwd(int dtype, const void* q, const void* k, const void* v
                           void* dv, int B, int H, int Hkv, int S, int D, const int64_t* strides,
                           float scale, int causal, float dropout_p, uint64_t seed,
                           uint64_t offset, hipStream_t st);
+// Per-document (block-diagonal causal) attention: doc_start[b, q] = first token of q's document,
+// doc_end[b, k] = one past the last token of k's document, both int32 [B, S], non-decreasing in s.
+hipError_t smdt_flash_fwd_doc(int dtype, const void* q, const void* k, const void* v, void* o,
+                              float* lse, int B, int H, int Hkv, int S, int D, int64_t q_sb,
+                              int64_t q_ss, int64_t q_sh, int64_t k_sb, int64_t k_ss, int64_t k_sh,
+                              int64_t v_sb, int64_t v_ss, int64_t v_sh, int64_t o_sb, int64_t o_ss,
+                              int64_t o_sh, float scale, float dropout_p, uint64_t seed,
+                              uint64_t offset, const int* doc_start, hipStream_t st);
+hipError_t smdt_flash_bwd_doc(int dtype, const void* q, const void* k, const void* v, const void* o,
+                              const void* dout, const float* lse, float* delta, void* dq, void* dk,
+                              void* dv, int B, int H, int Hkv, int S, int D, const int64_t* strides,
+                              float scale, float dropout_p, uint64_t seed, uint64_t offset,
+                              const int* doc_start, const int* doc_end, hipStream_t st);
 
 // gemm_tn.hip: C[M, N] = A[M, K] . B[N, K]^T (16-bit in / out, fp32 accumulate) with an epilogue:
 // epi 0 none, 1 + bias[n], 2 C = pre-activation and C2 = gelu_tanh(C + bias[n]) (bias_gelu fusion),

@@ -162,9 +162,15 @@ class GPTModel(nn.Module):
             logits = tp.gather_from_tensor_model_parallel_region(logits)
         return logits                                            # [s, b, V / tp]
 
-    def forward(self, tokens, position_ids=None, attention_mask=None, labels=None, loss_mask=None):
+    def forward(self, tokens, position_ids=None, attention_mask=None, labels=None, loss_mask=None,
+                doc_start=None):
         """Returns per-token losses [b, s] when ``labels`` are given, else the logits. ``loss_mask``
-        is accepted for Megatron's forward_step signature; the caller applies it to the losses."""
+        is accepted for Megatron's forward_step signature; the caller applies it to the losses.
+
+        ``doc_start`` (int32 [b, s], ``train.utils.document_starts``) restricts attention to each
+        token's own document (Megatron's ``--reset-attention-mask``); every pipeline stage takes it.
+        The dense ``attention_mask`` is accepted for the signature and not read: attention is causal,
+        or per-document causal with ``doc_start``."""
         if self.pre_process:
             pos_start = getattr(position_ids, "_smdt_arange_start", None) if position_ids is not None else None
             if position_ids is None:
@@ -175,7 +181,7 @@ class GPTModel(nn.Module):
             x = self._embed(tokens, position_ids, pos_start)
         else:
             x = self.input_tensor
-        out = self.decoder(x, None, None)
+        out = self.decoder(x, None, None, doc_start=doc_start)
         if not self.post_process:
             px, pb, res = out
             return SF.bias_dropout_add(px, pb, res, self.cfg.hidden_dropout, self.training)

@@ -370,8 +370,10 @@ class ParallelAttention(nn.Module):
     def set_rope(self, cos, sin, rot):
         self.rope = (cos, sin, rot)
 
-    def core_attention_unfused(self, qkv, training):
-        """Megatron's unfused path: baddbmm -> fused causal softmax (K1) -> dropout -> bmm."""
+    def core_attention_unfused(self, qkv, training, doc_start=None):
+        """Megatron's unfused path: baddbmm -> fused causal softmax (K1) -> dropout -> bmm. With
+        ``doc_start`` ([b, s], per-document attention) the [b, 1, s, s] left-to-right mask is built
+        from it and the fused masked softmax (K2) runs instead."""
         s, b = qkv.shape[0], qkv.shape[1]
         q, k, v = SF._qkv_views(qkv, self.nh, self.nkv, self.hd, True)  # [b, s, h, d]
         if self.nkv != self.nh:
@@ -382,7 +384,10 @@ class ParallelAttention(nn.Module):
         kh = k.permute(0, 2, 3, 1).reshape(b * self.nh, self.hd, s)
         vh = v.permute(0, 2, 1, 3).reshape(b * self.nh, s, self.hd)
         scores = torch.bmm(qh, kh).view(b, self.nh, s, s)
-        probs = SF.scaled_masked_softmax(scores, None, 1.0 / math.sqrt(self.hd), causal=True)
+        if doc_start is None:
+            probs = SF.scaled_masked_softmax(scores, None, 1.0 / math.sqrt(self.hd), causal=True)
+        else:
+            probs = SF.scaled_masked_softmax(scores, SF.document_mask(doc_start), 1.0 / math.sqrt(self.hd))
         if training and self.cfg.attention_dropout > 0:
             probs = F.dropout(probs, p=self.cfg.attention_dropout, training=True)
         ctx = torch.bmm(probs.view(b * self.nh, s, s), vh)          # [b*nh, s, d]
@@ -403,13 +408,16 @@ class ParallelAttention(nn.Module):
                                 dropout_p=p, rng=get_rng("tp"))
         return ctx.reshape(ctx.shape[0], ctx.shape[1], self.nh * self.hd)
 
-    def forward(self, x, training=True):
+    def forward(self, x, training=True, doc_start=None):
         qkv = self.qkv(x)                                        # [s, b, (nh + 2 nkv) d]
         if _PACK["idx"] is not None:                              # padding-free micro-batch
+            if doc_start is not None:
+                raise NotImplementedError("per-document attention (doc_start / --reset-attention-mask) is not "
+                                          "supported in the padding-free length-grouped SFT layout")
             if self._groups_ok(qkv):
                 return self.proj(self._attend_groups(qkv, training))
             return self.proj(_pack_rows(self._attend(_unpack_rows(qkv), training)))
-        return self.proj(self._attend(qkv, training))            # (out, bias)
+        return self.proj(self._attend(qkv, training, doc_start))  # (out, bias)
 
     def _groups_ok(self, qkv) -> bool:
         g = _PACK.get("groups")
@@ -434,8 +442,11 @@ class ParallelAttention(nn.Module):
                                     g["blocks"])
         return _GatherRows.apply(ctx, g["pack"], g["inv"]).unsqueeze(1)         # [T, 1, nh hd]
 
-    def _attend(self, qkv, training):
+    def _attend(self, qkv, training, doc_start=None):
         cp = ps.get_state().cp
+        if cp > 1 and doc_start is not None:
+            raise NotImplementedError("per-document attention (doc_start / --reset-attention-mask) is not "
+                                      "supported with context parallelism (--context-parallel-size > 1)")
         if self.rope is not None:
             cos, sin, rot = self.rope
             if cp > 1:  # this rank's positions: chunk cp_rank of the full sequence
@@ -449,14 +460,14 @@ class ParallelAttention(nn.Module):
             # comes from the per-TP-rank stream (Megatron forks the model-parallel tracker here)
             p = self.cfg.attention_dropout if training else 0.0
             ctx = SF.flash_attention_qkv(qkv, self.nh, self.nkv, self.hd, seq_first=True, causal=True,
-                                         dropout_p=p, rng=get_rng("tp"))
+                                         dropout_p=p, rng=get_rng("tp"), doc_start=doc_start)
         elif training and self.cfg.recompute_granularity == "selective" and torch.is_grad_enabled():
             # Megatron's selective recompute: only the [b, np, s, s] scores / probabilities /
             # dropout of the unfused core attention are dropped and recomputed in backward (the
             # flash kernels never store them, so with flash there is nothing to recompute)
-            ctx = rng_checkpoint(lambda t: self.core_attention_unfused(t, training), qkv)
+            ctx = rng_checkpoint(lambda t: self.core_attention_unfused(t, training, doc_start), qkv)
         else:
-            ctx = self.core_attention_unfused(qkv, training)
+            ctx = self.core_attention_unfused(qkv, training, doc_start)
         return ctx
 
 
@@ -634,7 +645,7 @@ class ParallelTransformerLayer(nn.Module):
             # the SP norms hand their output to the all-gather, not back as a local residual
             raise NotImplementedError("--apply-residual-connection-post-layernorm with --sequence-parallel")
 
-    def forward(self, x, xbias, residual):
+    def forward(self, x, xbias, residual, doc_start=None):
         training = self.training
         p = self.cfg.hidden_dropout
         # sequence parallelism: each norm's output is all-gathered by the next column-parallel
@@ -645,7 +656,7 @@ class ParallelTransformerLayer(nn.Module):
                                               gather=None if g is None else g + (True, residual is not None))
         if self.post_ln_residual:           # Megatron's --apply-residual-connection-post-layernorm
             residual = ln1
-        a, ab = self.attention(ln1, training)
+        a, ab = self.attention(ln1, training, doc_start)
         ln2, residual = self.post_attention_norm.fused(a, ab, residual, p, training,
                                                        gather=None if g is None else g + (True, True))
         if self.post_ln_residual:
@@ -658,7 +669,8 @@ class ParallelTransformerLayer(nn.Module):
         (``ParallelTransformer._forward_subbatch``): each phase ends right after it STARTS an
         exchange (the norms' all-gathers by ``tp.ag_start``; the row-parallel linears' reduce-
         scatters are left in flight by ``rs_ring`` under ``tp.begin_subbatch``) and the next phase
-        of this half begins by completing it. ``st`` holds this half's (x, xbias, residual)."""
+        of this half begins by completing it. ``st`` holds this half's (x, xbias, residual) and its
+        rows of ``doc_start`` (or None)."""
         training = self.training
         p = self.cfg.hidden_dropout
         g = _sp_gather(self.cfg)
@@ -668,7 +680,7 @@ class ParallelTransformerLayer(nn.Module):
                                               gather=None if g is None else g + (True, residual is not None))
         tp.ag_start(ln1, group)
         yield
-        a, ab = self.attention(ln1, training)
+        a, ab = self.attention(ln1, training, st.get("doc_start"))
         yield
         ln2, residual = self.post_attention_norm.fused(tp.rs_finish(a), ab, residual, p, training,
                                                        gather=None if g is None else g + (True, True))
@@ -693,22 +705,24 @@ class ParallelTransformer(nn.Module):
         self.layers = nn.ModuleList([ParallelTransformerLayer(cfg, first_layer + i, device) for i in range(num_layers)])
         self.final_norm = Norm(cfg.hidden_size, cfg, device) if post_norm else None
 
-    def _run(self, i, x, xb, res):
+    def _run(self, i, x, xb, res, doc_start=None):
         layer = self.layers[i]
         cfg = self.cfg
         if self.training and cfg.recompute_granularity == "full":
             n = cfg.recompute_num_layers or len(self.layers)
             if cfg.recompute_method == "block" and i >= n:
-                return layer(x, xb, res)
+                return layer(x, xb, res, doc_start)
+            # doc_start (an integer tensor, no gradient) travels with the call: the closures bind
+            # THIS call's value, so the recompute in backward sees it whatever ran in between
             if cfg.distribute_saved_activations and ps.get_state().tp > 1 and not cfg.sequence_parallel:
                 from ..parallel.random import distributed_checkpoint
                 if res is None:
-                    return distributed_checkpoint(lambda a, b_: layer(a, b_, None), x, xb)
-                return distributed_checkpoint(layer, x, xb, res)
+                    return distributed_checkpoint(lambda a, b_: layer(a, b_, None, doc_start), x, xb)
+                return distributed_checkpoint(lambda a, b_, r: layer(a, b_, r, doc_start), x, xb, res)
             if xb is None:
-                return rng_checkpoint(lambda a, r: layer(a, None, r), x, res)
-            return rng_checkpoint(layer, x, xb, res)
-        return layer(x, xb, res)
+                return rng_checkpoint(lambda a, r: layer(a, None, r, doc_start), x, res)
+            return rng_checkpoint(lambda a, b_, r: layer(a, b_, r, doc_start), x, xb, res)
+        return layer(x, xb, res, doc_start)
 
     def _subbatch_ok(self, x) -> bool:
         cfg = self.cfg
@@ -718,7 +732,7 @@ class ParallelTransformer(nn.Module):
                 and tp.subbatch_capable(st) and x.dim() == 3 and x.shape[1] % 2 == 0
                 and len(self.layers) > 0)
 
-    def _forward_subbatch(self, x, xbias, residual):
+    def _forward_subbatch(self, x, xbias, residual, doc_start=None):
         """The layer stack on the two batch halves of the micro-batch, phase by phase alternately
         (see ``ParallelTransformerLayer.forward_phases``): half b's GEMMs / attention run while half
         a's exchange is in flight and vice versa. The halves meet again (one concat each) before
@@ -731,7 +745,8 @@ class ParallelTransformer(nn.Module):
         for i in range(2):
             sl = slice(i * hb, (i + 1) * hb)
             halves.append({"x": x[:, sl].contiguous(), "xbias": xbias,
-                           "residual": None if residual is None else residual[:, sl].contiguous()})
+                           "residual": None if residual is None else residual[:, sl].contiguous(),
+                           "doc_start": None if doc_start is None else doc_start[sl].contiguous()})
         tp.begin_subbatch()
         try:
             for layer in self.layers:
@@ -750,11 +765,13 @@ class ParallelTransformer(nn.Module):
         residual = torch.cat([h["residual"] for h in halves], dim=1)
         return x, xbias, residual
 
-    def forward(self, x, xbias=None, residual=None):
+    def forward(self, x, xbias=None, residual=None, doc_start=None):
         """Returns (pending_x, pending_bias, residual) or, with ``final_norm``, the normalised
-        output (the pending branch folded into the residual first)."""
+        output (the pending branch folded into the residual first). ``doc_start`` (int32 [b, s],
+        ``ops.functional.document_starts``) restricts every layer's attention to each token's own
+        document."""
         if self._subbatch_ok(x):
-            x, xbias, residual = self._forward_subbatch(x, xbias, residual)
+            x, xbias, residual = self._forward_subbatch(x, xbias, residual, doc_start)
         elif self.cfg.recompute_granularity != "full" and not tp.foreign_hooks(self):
             # every row-parallel output of the stack is consumed by the next fused norm (the
             # layers' own, or the final one): the ring reduce-scatters leave their combine to it.
@@ -764,10 +781,10 @@ class ParallelTransformer(nn.Module):
                 x = tp.PendingAddCheck.apply(x)
             with tp.defer_rs_add():
                 for i in range(len(self.layers)):
-                    x, xbias, residual = self._run(i, x, xbias, residual)
+                    x, xbias, residual = self._run(i, x, xbias, residual, doc_start)
         else:
             for i in range(len(self.layers)):
-                x, xbias, residual = self._run(i, x, xbias, residual)
+                x, xbias, residual = self._run(i, x, xbias, residual, doc_start)
         if self.final_norm is not None:
             g = _sp_gather(self.cfg)          # y feeds the LM head's column-parallel all-gather
             y, _ = self.final_norm.fused(x, xbias, residual, self.cfg.hidden_dropout, self.training,

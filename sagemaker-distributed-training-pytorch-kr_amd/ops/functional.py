@@ -333,9 +333,45 @@ def _qkv_views(qkv, nh, nkv, hd, seq_first):
     return q, k, v
 
 
+def document_ends(doc_start):
+    """The key-side twin of ``doc_start`` (int32 [B, S], the index of the first token of each
+    token's document): ``doc_end[b, k]`` is one past the last token of ``k``'s document, so query
+    ``q`` attends key ``k`` iff ``k <= q < doc_end[k]``  (<=> ``doc_start[q] <= k <= q``). The dK / dV
+    kernel reads it. Device ops only (no host sync, capturable); the result is kept on the
+    ``doc_start`` tensor object, so the layers of a model derive it once per batch — do not write
+    into a ``doc_start`` after it was used."""
+    de = getattr(doc_start, "_smdt_doc_end", None)
+    if de is None:
+        S = doc_start.shape[1]
+        ar = torch.arange(S, dtype=torch.int32, device=doc_start.device)
+        first = torch.where(doc_start == ar, ar, ar.new_full((), S))        # index of each first token, else S
+        nxt = torch.cat([first[:, 1:], first.new_full((first.shape[0], 1), S)], dim=1)   # ... of tokens > k
+        de = nxt.flip(1).cummin(dim=1).values.flip(1).to(torch.int32).contiguous()
+        doc_start._smdt_doc_end = de
+    return de
+
+
+def document_mask(doc_start):
+    """[B, 1, S, S] bool, True = masked: the left-to-right mask with per-document blocks (key after
+    the query, or before the query's document) for the unfused softmax path."""
+    S = doc_start.shape[1]
+    ar = torch.arange(S, device=doc_start.device)
+    m = (ar[None, None, :] > ar[None, :, None]) | (ar[None, None, :] < doc_start[:, :, None])
+    return m.unsqueeze(1)
+
+
+def _doc_check(doc_start, B, S, causal):
+    if not causal:
+        raise ValueError("doc_start (per-document attention) needs causal=True")
+    if doc_start.dtype != torch.int32 or tuple(doc_start.shape) != (B, S):
+        raise ValueError(f"doc_start must be int32 [B, S] = [{B}, {S}], got {doc_start.dtype} "
+                         f"{tuple(doc_start.shape)}")
+
+
 class _FlashAttnQKV(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, nh, nkv, hd, seq_first, scale, causal, dropout_p=0.0, seed=0, offset=0):
+    def forward(ctx, qkv, nh, nkv, hd, seq_first, scale, causal, dropout_p=0.0, seed=0, offset=0,
+                doc_start=None, doc_end=None):
         C = _ext.ext()
         q, k, v = _qkv_views(qkv, nh, nkv, hd, seq_first)
         if seq_first:
@@ -346,9 +382,10 @@ class _FlashAttnQKV(torch.autograd.Function):
             B, S = qkv.shape[0], qkv.shape[1]
             out = qkv.new_empty(B, S, nh, hd)
             ov = out
-        _, lse = C.flash_fwd(q, k, v, scale, causal, ov, dropout_p, seed, offset)
+        _, lse = C.flash_fwd(q, k, v, scale, causal, ov, dropout_p, seed, offset, doc_start)
         ctx.save_for_backward(qkv, out, lse)
         ctx.cfg = (nh, nkv, hd, seq_first, scale, causal, dropout_p, seed, offset)
+        ctx.doc = (doc_start, doc_end)      # integer descriptors: no gradient, no version tracking needed
         return out.flatten(-2)
 
     @staticmethod
@@ -364,25 +401,27 @@ class _FlashAttnQKV(torch.autograd.Function):
         if seq_first:
             do = do.transpose(0, 1)
             o = o.transpose(0, 1)
-        C.flash_bwd(q, k, v, o, do, lse, scale, causal, dq, dk, dv, dropout_p, seed, offset)
-        return dqkv, None, None, None, None, None, None, None, None, None
+        C.flash_bwd(q, k, v, o, do, lse, scale, causal, dq, dk, dv, dropout_p, seed, offset, *ctx.doc)
+        return dqkv, None, None, None, None, None, None, None, None, None, None, None
 
 
 class _FlashAttn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, scale, causal, dropout_p=0.0, seed=0, offset=0):
+    def forward(ctx, q, k, v, scale, causal, dropout_p=0.0, seed=0, offset=0, doc_start=None, doc_end=None):
         C = _ext.ext()
-        o, lse = C.flash_fwd(q, k, v, scale, causal, None, dropout_p, seed, offset)
+        o, lse = C.flash_fwd(q, k, v, scale, causal, None, dropout_p, seed, offset, doc_start)
         ctx.save_for_backward(q, k, v, o, lse)
         ctx.cfg = (scale, causal, dropout_p, seed, offset)
+        ctx.doc = (doc_start, doc_end)
         return o
 
     @staticmethod
     def backward(ctx, do):
         q, k, v, o, lse = ctx.saved_tensors
         scale, causal, p, seed, offset = ctx.cfg
-        dq, dk, dv = _ext.ext().flash_bwd(q, k, v, o, do, lse, scale, causal, None, None, None, p, seed, offset)
-        return dq, dk, dv, None, None, None, None, None
+        dq, dk, dv = _ext.ext().flash_bwd(q, k, v, o, do, lse, scale, causal, None, None, None, p, seed, offset,
+                                          *ctx.doc)
+        return dq, dk, dv, None, None, None, None, None, None, None
 
 
 _M32 = 0xFFFFFFFF
@@ -470,9 +509,10 @@ def flash_dropout_keep_mask(B: int, H: int, S: int, p: float, seed: int, offset:
     return keep.reshape(B, H, S, S)
 
 
-def attention_ref(q, k, v, scale, causal, dropout_p: float = 0.0, keep=None):
+def attention_ref(q, k, v, scale, causal, dropout_p: float = 0.0, keep=None, doc_start=None):
     """Reference attention on [B, S, H, D] (GQA by head repetition), fp32 math. ``keep``
-    ([B, H, S, S] bool) is the dropout keep-mask (``flash_dropout_keep_mask``)."""
+    ([B, H, S, S] bool) is the dropout keep-mask (``flash_dropout_keep_mask``). ``doc_start``
+    (int32 [B, S], causal only) also masks keys before the query's document: block-diagonal causal."""
     if q.is_cuda and os.environ.get("SMDT_ASSERT_FLASH") == "1":
         raise RuntimeError("SMDT_ASSERT_FLASH=1: reference attention reached on the GPU")
     B, S, H, D = q.shape
@@ -485,6 +525,10 @@ def attention_ref(q, k, v, scale, causal, dropout_p: float = 0.0, keep=None):
     if causal:
         cm = torch.ones(S, S, dtype=torch.bool, device=q.device).triu(1)
         s = s.masked_fill(cm, float("-inf"))
+    if doc_start is not None:
+        _doc_check(doc_start, B, S, causal)
+        ar = torch.arange(S, device=q.device)
+        s = s.masked_fill((ar[None, None, :] < doc_start[:, :, None]).unsqueeze(1), float("-inf"))
     p = torch.softmax(s, dim=-1)
     if dropout_p > 0:
         if keep is None:
@@ -533,28 +577,47 @@ def _pad_bshd(t, Sp, Dp):
     return torch.nn.functional.pad(t, (0, Dp - D, 0, 0, 0, Sp - S))
 
 
+def _doc_args(doc_start, S, Sp):
+    """(doc_start, doc_end) as the kernels take them at the padded length ``Sp``: the pad rows
+    S .. Sp - 1 form a document of their own, so no real token's bounds move."""
+    if doc_start is None:
+        return None, None
+    if Sp != S:
+        pad = doc_start.new_full((doc_start.shape[0], Sp - S), S)
+        doc_start = torch.cat([doc_start, pad], dim=1)
+    doc_start = doc_start.contiguous()
+    return doc_start, document_ends(doc_start)
+
+
 def flash_attention(q, k, v, scale: Optional[float] = None, causal: bool = True, dropout_p: float = 0.0,
-                    rng: Optional[PhiloxState] = None):
+                    rng: Optional[PhiloxState] = None, doc_start=None):
     """Attention over [B, S, H, D] tensors (any batch/seq/head strides, unit last stride);
-    ``k``/``v`` may have fewer heads (GQA)."""
+    ``k``/``v`` may have fewer heads (GQA). ``doc_start`` (int32 [B, S], non-decreasing along S,
+    ``doc_start[b, i] <= i``; causal only): per-document attention of packed samples, query ``q``
+    attends key ``k`` iff ``doc_start[b, q] <= k <= q``."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
+    if doc_start is not None:
+        _doc_check(doc_start, q.shape[0], q.shape[1], causal)
     seed, off = _rng(rng).next() if dropout_p > 0 else (0, 0)
     if _ext.use_kernels(q):
         S, D = q.shape[1], q.shape[3]
         Sp, Dp = _flash_plan(q, k, causal)
+        ds, de = _doc_args(doc_start, S, Sp)
         if (Sp, Dp) == (S, D) and flash_supported(q, k):
-            return _FlashAttn.apply(q, k, v, float(scale), bool(causal), float(dropout_p), int(seed), int(off))
+            return _FlashAttn.apply(q, k, v, float(scale), bool(causal), float(dropout_p), int(seed), int(off),
+                                    ds, de)
         qp, kp, vp = (_pad_bshd(t.contiguous() if t.stride(-1) != 1 else t, Sp, Dp) for t in (q, k, v))
-        o = _FlashAttn.apply(qp, kp, vp, float(scale), bool(causal), float(dropout_p), int(seed), int(off))
+        o = _FlashAttn.apply(qp, kp, vp, float(scale), bool(causal), float(dropout_p), int(seed), int(off), ds, de)
         return o[:, :S, :, :D]
     keep = flash_dropout_keep_mask(q.shape[0], q.shape[2], q.shape[1], dropout_p, seed, off, q.device) \
         if dropout_p > 0 else None
-    return attention_ref(q, k, v, scale, causal, dropout_p, keep)
+    return attention_ref(q, k, v, scale, causal, dropout_p, keep, doc_start)
 
 
 def flash_attention_qkv(qkv, nh: int, nkv: int, hd: int, seq_first: bool = True, causal: bool = True,
-                        scale: Optional[float] = None, dropout_p: float = 0.0, rng: Optional[PhiloxState] = None):
+                        scale: Optional[float] = None, dropout_p: float = 0.0, rng: Optional[PhiloxState] = None,
+                        doc_start=None):
     """Attention straight off a fused QKV projection output.
 
     ``qkv`` is [S, B, (nh + 2 nkv) hd] (``seq_first``) or [B, S, ...]; returns [S, B, nh hd]
@@ -562,22 +625,27 @@ def flash_attention_qkv(qkv, nh: int, nkv: int, hd: int, seq_first: bool = True,
     attention-probability dropout inside the kernels (mask re-derived from ``rng``'s
     (seed, offset) in backward — nothing is stored). Shapes the kernels cannot read in place
     (S % 128 != 0, head dim not 64 / 128) go through the padded separate-q/k/v path.
+    ``doc_start`` (int32 [B, S], batch-first whatever ``seq_first``): per-document attention, see
+    ``flash_attention``.
     """
     if scale is None:
         scale = 1.0 / math.sqrt(hd)
     q, k, v = _qkv_views(qkv, nh, nkv, hd, seq_first)
+    if doc_start is not None:
+        _doc_check(doc_start, q.shape[0], q.shape[1], causal)
     if _ext.use_kernels(qkv):
         if qkv.is_contiguous() and flash_supported(q, k) and (nh + 2 * nkv) * hd % 8 == 0:
             seed, off = _rng(rng).next() if dropout_p > 0 else (0, 0)
+            ds, de = _doc_args(doc_start, q.shape[1], q.shape[1])
             return _FlashAttnQKV.apply(qkv, nh, nkv, hd, bool(seq_first), float(scale), bool(causal),
-                                       float(dropout_p), int(seed), int(off))
-        o = flash_attention(q, k, v, scale, causal, dropout_p, rng)          # [B, S, H, D]
+                                       float(dropout_p), int(seed), int(off), ds, de)
+        o = flash_attention(q, k, v, scale, causal, dropout_p, rng, doc_start)          # [B, S, H, D]
     else:
         seed, off = _rng(rng).next() if dropout_p > 0 else (0, 0)
         keep = None
         if dropout_p > 0:
             keep = flash_dropout_keep_mask(q.shape[0], nh, q.shape[1], dropout_p, seed, off, qkv.device)
-        o = attention_ref(q, k, v, scale, causal, dropout_p, keep)  # [B, S, H, D]
+        o = attention_ref(q, k, v, scale, causal, dropout_p, keep, doc_start)  # [B, S, H, D]
     if seq_first:
         o = o.transpose(0, 1)
     return o.flatten(-2).contiguous()

@@ -399,6 +399,9 @@ def validate_args(args, defaults=None):
             "context parallelism re-shards attention heads: (heads / TP) must be divisible by CP"
         assert args.seq_length is None or args.seq_length % args.context_parallel_size == 0, \
             "sequence length must be divisible by the context-parallel size"
+        # per-document attention reads doc_start of the full sequence; the Ulysses re-shard does not carry it
+        assert not args.reset_attention_mask, \
+            "--reset-attention-mask (per-document attention) is not supported with --context-parallel-size > 1"
     assert args.batch_size is None, "--batch-size argument is no longer valid, use --micro-batch-size instead"
     assert args.warmup is None, "--warmup argument is no longer valid, use --lr-warmup-fraction instead"
     assert args.model_parallel_size is None, "--model-parallel-size is no longer valid, use --tensor-model-parallel-size"

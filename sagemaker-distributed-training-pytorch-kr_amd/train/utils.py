@@ -8,6 +8,7 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
+from ..ops.functional import document_ends, document_mask  # noqa: F401  (re-exported next to document_starts)
 from ..parallel import state as ps
 
 
@@ -47,6 +48,25 @@ def get_ltor_masks_and_position_ids(data, eod_token, reset_position_ids=False, r
         # (a tensor derived from this one by slicing / copying loses the mark and takes the gather)
         position_ids._smdt_arange_start = 0
     return attention_mask, loss_mask, position_ids
+
+
+def document_starts(tokens, eod_token):
+    """``doc_start`` int32 [b, s] for ``--reset-attention-mask``: ``doc_start[b, i]`` is the index of
+    the first token of the document token ``i`` belongs to. Megatron semantics: an EOD at position
+    ``j`` belongs to the document it ends, positions > ``j`` start a new document at ``j + 1``, and
+    query ``q`` may attend key ``k`` iff ``doc_start[q] <= k <= q`` — the block structure of the
+    dense mask of ``get_ltor_masks_and_position_ids(..., reset_attention_mask=True)`` in ``b s``
+    integers instead of ``b s^2`` entries.
+
+    Runs on the tokens' device without a Python loop or a host sync (a step that uses it stays
+    capturable as a HIP graph). The flash kernels and the unfused path both take it (``GPTModel``'s
+    ``doc_start``); ``document_ends`` is the key-side twin the dK / dV kernel reads."""
+    b, s = tokens.shape
+    ar = torch.arange(s, dtype=torch.int32, device=tokens.device)
+    after = torch.where(tokens == eod_token, ar + 1, torch.zeros_like(ar))       # an EOD at j opens j + 1
+    start = torch.cummax(after, dim=1).values                                     # ... for every i >= j
+    start = torch.cat([start.new_zeros(b, 1), start[:, :-1]], dim=1)              # ... but i > j only
+    return start.to(torch.int32).contiguous()
 
 
 def average_losses_across_data_parallel_group(losses):
