@@ -380,6 +380,55 @@ Tensor gather_rows(Tensor src, Tensor map) {
   return out;
 }
 
+// ------------------------------------------------------------------ FP8 quantisation (delayed scaling)
+// x [M, K] bf16 / fp16 -> q [M, K] (and qt [K, M] with transpose) in float8_e4m3fn (fmt 0) or
+// float8_e5m2 (fmt 1); scale / amax: one fp32 each on x's device (slots of the model's FP8 table).
+static void need_f32_slot(const Tensor& t, const Tensor& like, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device() && t.scalar_type() == at::kFloat && t.numel() == 1,
+              "fp8_quantize: '", name, "' must be one fp32 value on x's device");
+}
+
+std::vector<Tensor> fp8_quantize(Tensor x, Tensor scale, Tensor amax, int64_t fmt, bool transpose) {
+  need_contig(x, "x");
+  TORCH_CHECK(x.dim() == 2, "fp8_quantize: x must be 2-D, got ", x.dim(), "-D");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf, "fp8_quantize: bf16 / fp16 only");
+  TORCH_CHECK(fmt == 0 || fmt == 1, "fp8_quantize: fmt must be 0 (e4m3) or 1 (e5m2)");
+  const int64_t M = x.size(0), K = x.size(1);
+  TORCH_CHECK(M >= 1 && K >= 16 && K % 16 == 0, "fp8_quantize: need M >= 1 and K a multiple of 16, got [", M, ", ",
+              K, "]");
+  need_f32_slot(scale, x, "scale");
+  need_f32_slot(amax, x, "amax");
+  const auto qopt = x.options().dtype(fmt == 0 ? at::kFloat8_e4m3fn : at::kFloat8_e5m2);
+  auto q = torch::empty({M, K}, qopt);
+  Tensor qt;
+  if (transpose) qt = torch::empty({K, M}, qopt);
+  check(smdt_fp8_quantize(x.data_ptr(), q.data_ptr(), transpose ? qt.data_ptr() : nullptr, scale.data_ptr<float>(),
+                          amax.data_ptr<float>(), M, K, dcode(x), (int)fmt, cur_stream()),
+        "fp8_quantize");
+  if (transpose) return {q, qt};
+  return {q};
+}
+
+// In place on scale [T], hist [T, H], amax [T]; fmt_max [T] (448 or 57344 per tensor).
+void fp8_update_scales(Tensor scale, Tensor hist, Tensor amax, Tensor fmt_max, int64_t margin, bool use_max) {
+  need_contig(scale, "scale");
+  need_contig(hist, "amax_history");
+  need_contig(amax, "amax");
+  need_contig(fmt_max, "fmt_max");
+  TORCH_CHECK(scale.dim() == 1 && hist.dim() == 2 && amax.dim() == 1 && fmt_max.dim() == 1,
+              "fp8_update_scales: scale [T], amax_history [T, H], amax [T], fmt_max [T]");
+  const int64_t T = scale.size(0), H = hist.size(1);
+  TORCH_CHECK(T >= 1 && H >= 1 && hist.size(0) == T && amax.size(0) == T && fmt_max.size(0) == T,
+              "fp8_update_scales: table sizes do not match");
+  for (const Tensor* t : {&scale, &hist, &amax, &fmt_max})
+    TORCH_CHECK(t->scalar_type() == at::kFloat && t->device() == scale.device(), "fp8_update_scales: fp32 tables "
+                "on one device");
+  TORCH_CHECK(margin >= 0 && margin <= 64, "fp8_update_scales: margin out of range");
+  check(smdt_fp8_update_scales(scale.data_ptr<float>(), hist.data_ptr<float>(), amax.data_ptr<float>(),
+                               fmt_max.data_ptr<float>(), T, H, (int)margin, use_max ? 1 : 0, cur_stream()),
+        "fp8_update_scales");
+}
+
 // ------------------------------------------------------------------ 2-D transpose (16-bit)
 // out [C, R] = x [R, C]^T, contiguous (feeds the dgrad GEMMs in the TN layout).
 Tensor transpose2d(Tensor x) {
@@ -920,6 +969,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cast_", &cast_);
   m.def("rope_", &rope_);
   m.def("transpose2d", &transpose2d);
+  m.def("fp8_quantize", &fp8_quantize);
+  m.def("fp8_update_scales", &fp8_update_scales);
   m.def("paced_copy", &paced_copy);
   m.def("gather_rows", &gather_rows);
   m.def("aug_depthwise", &aug_depthwise);

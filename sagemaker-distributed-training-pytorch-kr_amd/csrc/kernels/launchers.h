@@ -74,6 +74,14 @@ hipError_t smdt_rope(int dtype, void* x, int64_t ntok, int nh, int64_t tok_strid
 
 // transpose.hip
 hipError_t smdt_transpose16(const void* in, void* out, int64_t R, int64_t C, hipStream_t st);
+// fp8_quant.hip: q[M, K] (and qt[K, M] when qt != nullptr) = fp8(clamp(x * *scale)), *amax =
+// max(*amax, max |x|). bf8 = 0: E4M3 (OCP e4m3fn), 1: E5M2. K % 16 == 0; dtype bf16 / fp16.
+hipError_t smdt_fp8_quantize(const void* x, void* q, void* qt, const float* scale, float* amax, int64_t M,
+                             int64_t K, int dtype, int bf8, hipStream_t st);
+// Delayed-scaling update of T tensors: roll hist [T, H], hist[:, 0] = amax, amax = 0,
+// scale = (fmt_max / reduce(hist)) / 2^margin (kept when the reduced amax is 0 or not finite).
+hipError_t smdt_fp8_update_scales(float* scale, float* hist, float* amax, const float* fmt_max, int64_t T,
+                                  int64_t H, int margin, int use_max, hipStream_t st);
 // link_standin.hip: paced copy standing in for a TP-pair exchange in single-GPU rank emulation
 hipError_t smdt_paced_copy(const void* src, void* dst, int64_t nbytes, int blocks, int64_t ns, hipStream_t st);
 // dst[r] = map[r] >= 0 ? src[map[r]] : 0 (rows of row_bytes, a multiple of 16)

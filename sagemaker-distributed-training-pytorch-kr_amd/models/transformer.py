@@ -79,8 +79,22 @@ class TransformerConfig:
     recompute_method: Optional[str] = None       # "uniform" | "block"
     recompute_num_layers: Optional[int] = None
     distribute_saved_activations: bool = False   # full recompute: saved layer inputs split across TP
+    # FP8 linears with delayed scaling (--fp8-e4m3 / --fp8-hybrid): QKV, proj, fc1, fc2 of every
+    # layer run their forward and input-gradient GEMMs on FP8 operands (tp.FP8State)
+    fp8: Optional[str] = None                    # None | "e4m3" | "hybrid" (dY in E5M2)
+    fp8_margin: int = 0
+    fp8_interval: int = 1
+    fp8_amax_history_len: int = 1
+    fp8_amax_compute_algo: str = "most_recent"   # or "max"
 
     def __post_init__(self):
+        if self.fp8 not in (None, "e4m3", "hybrid"):
+            raise ValueError(f"fp8 must be None, 'e4m3' or 'hybrid', got {self.fp8!r}")
+        if self.fp8 and self.params_dtype not in (torch.bfloat16, torch.float16):
+            raise ValueError("fp8 linears need bf16 or fp16 parameters")
+        if self.fp8 and self.num_experts:
+            raise ValueError("fp8 linears with num_experts are not supported (per-expert row counts are not "
+                             "multiples of 16)")
         if self.num_query_groups is None:
             self.num_query_groups = self.num_attention_heads
         if self.kv_channels is None:
@@ -539,14 +553,16 @@ class ParallelMLP(nn.Module):
 
     def forward(self, x):
         act = self.cfg.activation
-        if act == "gelu" and self.cfg.bias_gelu_fusion:
+        # FP8 linears take the unfused route: FP8 GEMM, then the bias-activation kernel
+        fused = act == "gelu" and self.cfg.bias_gelu_fusion and not self.cfg.fp8
+        if fused:
             # the fused forms read fc1 / fc2 weights without calling fc1(x) / fc2(x)
             _gather_wait(self.fc1, x)
             _gather_wait(self.fc2, x)
-        if act == "gelu" and self.cfg.bias_gelu_fusion and tp.sp_fused_gelu_mlp_ok(x, self):
+        if fused and tp.sp_fused_gelu_mlp_ok(x, self):
             # TP > 1 + sequence parallelism: the GeLU halves inside the ring-chunk GEMMs
             return tp.SPFusedGeLUMLP.apply(x, self.fc1.weight, self.fc1.bias, self.fc2.weight), self.fc2.bias
-        if act == "gelu" and self.cfg.bias_gelu_fusion and tp.linear_bias_gelu_ok(x, self.fc1):
+        if fused and tp.linear_bias_gelu_ok(x, self.fc1):
             if tp.fused_gelu_mlp_ok(x, self):
                 # both GeLU halves inside the GEMMs: fc1 + bias + GeLU forward, fc2 dgrad + GeLU
                 # backward (gemm_tn.hip epilogues)
@@ -704,6 +720,13 @@ class ParallelTransformer(nn.Module):
         self.cfg = cfg
         self.layers = nn.ModuleList([ParallelTransformerLayer(cfg, first_layer + i, device) for i in range(num_layers)])
         self.final_norm = Norm(cfg.hidden_size, cfg, device) if post_norm else None
+        if cfg.fp8 and num_layers > 0:
+            # QKV, projection, fc1 and fc2 of every layer; registered only with FP8 on, so the state
+            # dict of a 16-bit model keeps its keys
+            lins = [m for l in self.layers for m in (l.attention.qkv, l.attention.proj, l.mlp.fc1, l.mlp.fc2)]
+            self.fp8_state = tp.FP8State(len(lins), cfg.fp8, cfg.fp8_margin, cfg.fp8_interval,
+                                         cfg.fp8_amax_history_len, cfg.fp8_amax_compute_algo, device)
+            tp.attach_fp8(lins, self.fp8_state)
 
     def _run(self, i, x, xb, res, doc_start=None):
         layer = self.layers[i]

@@ -805,3 +805,82 @@ class _CERef(torch.autograd.Function):
 
 def _ce_ref(logits, target, vocab_start, group, ignore_index, vvalid=0):
     return _CERef.apply(logits, target, int(vocab_start), group, int(ignore_index), int(vvalid))
+
+
+# --------------------------------------------------------------------------------------------
+# FP8 with delayed per-tensor scaling (csrc/kernels/fp8_quant.hip). gfx950 uses the OCP encodings,
+# which are torch.float8_e4m3fn / torch.float8_e5m2. Every op has a pure-torch twin (``*_ref``)
+# that runs on the CPU and under SMDT_DISABLE_KERNELS=1 and is the reference of the GPU tests.
+
+FP8_MAX = {"e4m3": 448.0, "e5m2": 57344.0}
+FP8_DTYPE = {"e4m3": torch.float8_e4m3fn, "e5m2": torch.float8_e5m2}
+
+
+def fp8_quantize_ref(x, scale, amax, fmt: str, transpose: bool = False):
+    xf = x.float()
+    amax.copy_(torch.maximum(amax, xf.abs().max().reshape(amax.shape)))   # NaN / inf propagate
+    mx = FP8_MAX[fmt]
+    q = (xf * scale).clamp(-mx, mx).to(FP8_DTYPE[fmt])                    # clamp keeps NaN
+    if transpose:
+        return q, q.t().contiguous()
+    return q
+
+
+def fp8_quantize(x, scale, amax, fmt: str, transpose: bool = False):
+    """q = fp8(clamp(float(x) * scale, +-max)) for x [M, K] bf16 / fp16, round-to-nearest-even, in
+    ``fmt`` ("e4m3" | "e5m2"); with ``transpose`` also qt [K, M], the same bytes transposed.
+    ``scale`` and ``amax`` are one-element fp32 tensors on x's device; ``amax`` is updated in place
+    to max(amax, max |x|) (before scaling; a NaN / inf input leaves it non-finite)."""
+    if fmt not in FP8_MAX:
+        raise ValueError(f"fp8_quantize: fmt must be 'e4m3' or 'e5m2', got {fmt!r}")
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 16 or x.shape[1] % 16:
+        raise ValueError(f"fp8_quantize: need x [M >= 1, K multiple of 16], got {tuple(x.shape)}")
+    if x.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"fp8_quantize: bf16 / fp16 input only, got {x.dtype}")
+    if not _ext.use_kernels(x):
+        return fp8_quantize_ref(x, scale, amax, fmt, transpose)
+    out = _ext.ext().fp8_quantize(x.contiguous(), scale, amax, 0 if fmt == "e4m3" else 1, bool(transpose))
+    return (out[0], out[1]) if transpose else out[0]
+
+
+def fp8_update_scales_ref(scale, amax_history, amax, fmt_max, margin: int, algo: str):
+    amax_history[:, 1:] = amax_history[:, :-1].clone()
+    amax_history[:, 0] = amax
+    amax.zero_()
+    red = amax_history[:, 0] if algo == "most_recent" else amax_history.max(dim=1).values
+    new = (fmt_max / red) / float(2 ** margin)
+    ok = torch.isfinite(red) & (red > 0) & torch.isfinite(new)
+    scale.copy_(torch.where(ok, new, scale))
+
+
+def fp8_update_scales(scale, amax_history, amax, fmt_max, margin: int = 0, algo: str = "most_recent"):
+    """One delayed-scaling update of a table of T FP8 tensors, in place and without a host sync:
+    roll ``amax_history`` [T, H], write ``amax`` [T] into column 0 and zero it, reduce the history
+    (``most_recent`` | ``max``) and set ``scale`` [T] = (fmt_max / amax) / 2^margin. A reduced amax
+    of 0 or a non-finite one keeps the previous scale."""
+    if algo not in ("most_recent", "max"):
+        raise ValueError(f"fp8_update_scales: algo must be 'most_recent' or 'max', got {algo!r}")
+    if not _ext.use_kernels(scale):
+        return fp8_update_scales_ref(scale, amax_history, amax, fmt_max, int(margin), algo)
+    _ext.ext().fp8_update_scales(scale, amax_history, amax, fmt_max, int(margin), algo == "max")
+
+
+def fp8_gemm_ref(a, b, inv_a, inv_b, bias, out_dtype):
+    acc = a.float().matmul(b.float().t()) * (inv_a * inv_b)
+    if bias is not None:
+        acc = acc + bias.float()
+    return acc.to(out_dtype)
+
+
+def fp8_gemm(a, b, inv_a, inv_b, bias=None, out_dtype=torch.bfloat16):
+    """out [M, N] = (a [M, K] · b [N, K]^T) * inv_a * inv_b (+ bias), FP8 operands (E4M3 or E5M2,
+    row-major), fp32 accumulation, through hipBLASLt's per-tensor-scaled FP8 GEMM
+    (``torch._scaled_mm``). ``inv_a`` / ``inv_b``: one-element fp32 dequantisation factors on the
+    device. A shape the library refuses raises with the shape; there is no 16-bit fallback."""
+    if not _ext.use_kernels(a):
+        return fp8_gemm_ref(a, b, inv_a, inv_b, bias, out_dtype)
+    try:
+        return torch._scaled_mm(a, b.t(), scale_a=inv_a, scale_b=inv_b, bias=bias, out_dtype=out_dtype)
+    except RuntimeError as e:
+        raise RuntimeError(f"fp8_gemm: the library refused M x N x K = {a.shape[0]} x {b.shape[0]} x {a.shape[1]} "
+                           f"({a.dtype} x {b.dtype} -> {out_dtype}): {e}") from e

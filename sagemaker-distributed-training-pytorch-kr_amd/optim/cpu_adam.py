@@ -130,6 +130,7 @@ class CPUOffloadAdam(MixedPrecisionAdam):
                                       non_blocking=cuda)
         if self.zero:
             ddp.all_gather_params()
+        _tp.fp8_after_optimizer_step(self.ddp.module)
         return self.grad_norm
 
     def state_dict(self):

@@ -258,6 +258,7 @@ class MixedPrecisionAdam:
             self._step_overlapped(g, mul, t)
             if self.scaler is not None:
                 self.scaler.update(self.found_inf)
+            _tp.fp8_after_optimizer_step(self.ddp.module)
             return self.grad_norm
         for (s, e, key), mo in zip(self.pieces, self.master_off):
             if e <= s:
@@ -267,6 +268,7 @@ class MixedPrecisionAdam:
             self.scaler.update(self.found_inf)
         if self.zero:
             ddp.all_gather_params()
+        _tp.fp8_after_optimizer_step(self.ddp.module)
         return self.grad_norm
 
     _overlappable = True     # the per-bucket update may run on the overlapped side stream

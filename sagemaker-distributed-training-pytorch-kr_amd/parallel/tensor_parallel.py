@@ -21,6 +21,7 @@ import contextlib
 import hashlib
 import math
 import os
+import weakref
 from typing import Optional
 
 import torch
@@ -832,8 +833,10 @@ _WT_CACHE: dict = {}
 
 
 def params_changed():
-    """Invalidate every cached W^T (call before any out-of-autograd parameter write)."""
+    """Invalidate every cached W^T and FP8 q(W) (call before any out-of-autograd parameter write)."""
     _WT_CACHE.clear()
+    for s in list(_FP8_STATES):
+        s._wq.clear()
 
 
 def drop_cached_weight_t(params):
@@ -841,6 +844,8 @@ def drop_cached_weight_t(params):
     with it, or the cache would end up holding a full bf16 copy of the model on every rank)."""
     for p in params:
         _WT_CACHE.pop(id(p), None)
+        for s in list(_FP8_STATES):
+            s._wq.pop(id(p), None)      # q(W) and q(W)^T go with the gathered weight too
 
 
 def mm_rows(g, w):
@@ -1019,6 +1024,220 @@ def _linear_backward(ctx, g, x, weight):
         DEFERRED_WGRAD.flush_opportunistic()
         _wait_works([handle], group)
     return gi_out, dw, db
+
+
+# --------------------------------------------------------------------------------------------
+# FP8 linears with delayed scaling (--fp8-e4m3 / --fp8-hybrid). The forward and input-gradient
+# GEMMs of a transformer layer's four linears take FP8 operands with one scale per tensor:
+#   y  = dequant(q(x) · q(W)^T) + b         x, W in E4M3
+#   dX = dequant(q(dY) · q(W))              dY in E5M2 (hybrid) or E4M3
+# The operands are quantised by fp8_quant.hip, the GEMM is hipBLASLt's per-tensor-scaled FP8 GEMM.
+# The weight gradient is what it is without FP8: the 16-bit x and dY through ``_wgrad_and_bias``
+# into the fp32 main_grad. Scales are "delayed": a quantise uses the scale the last update derived
+# from earlier amax values and records its own amax for the next update, so no tensor is read
+# twice and nothing syncs with the host. TP = 1 only.
+
+_FP8_STATES: "weakref.WeakSet" = weakref.WeakSet()
+_FP8_SLOTS = 3          # per linear: input, weight, output gradient
+
+
+class FP8State(nn.Module):
+    """The FP8 tensors of one layer stack as one table: ``scale`` [T], ``amax_history`` [T, H] and
+    the current ``amax`` [T] slots, T = 3 per linear (x, W, dY). All three (and the step count the
+    update interval runs on) are persistent buffers, so they travel with the model's state dict; a
+    state dict without them loads as a fresh table (scales 1) with a notice.
+
+    Scales change only in ``after_optimizer_step`` (called by the optimizer at the end of its
+    step, through ``fp8_after_optimizer_step``): one ``fp8_update_scales`` launch every
+    ``interval`` steps. Every micro-batch of a step and every recomputed forward therefore sees the
+    same scales, and amax merges by max, so a recompute leaves the table unchanged. q(W) and
+    q(W)^T are made once per optimizer step and dropped by ``params_changed()`` like the cached
+    W^T of the 16-bit dgrad.
+
+    Data parallelism: before an update the amax slots are max-reduced over the data-parallel
+    (x context-parallel) group, so every replica of a weight derives the same scales from the
+    global batch, the tables stay identical across ranks, and the one table a checkpoint holds is
+    every rank's.
+
+    Captured steps: the update interval is counted on the host, which a graph replay does not
+    run. With ``interval`` 1 a captured step carries its own update and advances its scales on
+    every replay; ``interval`` > 1 inside a capture is refused. ``step_count`` counts the eager
+    calls only; it matters to the interval alone, so a replayed step loses nothing by it."""
+
+    def __init__(self, num_linears: int, fmt: str, margin: int = 0, interval: int = 1, history_len: int = 1,
+                 algo: str = "most_recent", device=None):
+        super().__init__()
+        if fmt not in ("e4m3", "hybrid"):
+            raise ValueError(f"FP8State: fmt must be 'e4m3' or 'hybrid', got {fmt!r}")
+        if algo not in ("most_recent", "max"):
+            raise ValueError(f"FP8State: unknown amax algorithm {algo!r}")
+        if _tp_size() > 1:
+            raise NotImplementedError("FP8 linears (--fp8-e4m3 / --fp8-hybrid) with --tensor-model-parallel-size > 1")
+        self.fmt, self.margin, self.interval, self.algo = fmt, int(margin), max(int(interval), 1), algo
+        self.grad_fmt = "e5m2" if fmt == "hybrid" else "e4m3"
+        T = _FP8_SLOTS * int(num_linears)
+        f32 = dict(dtype=torch.float32, device=device)
+        self.register_buffer("scale", torch.ones(T, **f32))
+        self.register_buffer("amax_history", torch.zeros(T, max(int(history_len), 1), **f32))
+        self.register_buffer("amax", torch.zeros(T, **f32))
+        self.register_buffer("step_count", torch.zeros(1, dtype=torch.int64, device=device))
+        fm = torch.full((T,), SF.FP8_MAX["e4m3"], **f32)
+        fm[2::_FP8_SLOTS] = SF.FP8_MAX[self.grad_fmt]
+        self.register_buffer("fmt_max", fm, persistent=False)
+        self.register_buffer("scale_inv", torch.ones(T, **f32), persistent=False)
+        self._step = 0
+        self._epoch = 0          # bumped whenever the scales may have changed: keys the q(W) cache
+        self._wq: dict = {}
+        _FP8_STATES.add(self)
+
+    def _apply(self, fn, recurse=True):
+        # model.to(dtype=bf16) / .half() must not touch the tables: scales and amax stay fp32
+        # (the kernels take fp32 slots, and a 16-bit scale would differ from the saved one)
+        keep = {n: b for n, b in self._buffers.items() if b is not None and b.dtype == torch.float32}
+        super()._apply(fn, recurse)
+        for n, old in keep.items():
+            new = self._buffers[n]
+            if new.dtype != torch.float32:
+                self._buffers[n] = old.to(new.device)
+        self._scales_changed()
+        return self
+
+    def reset(self):
+        self.scale.fill_(1.0)
+        self.scale_inv.fill_(1.0)
+        self.amax_history.zero_()
+        self.amax.zero_()
+        self.step_count.zero_()
+        self._step = 0
+        self._scales_changed()
+
+    def _scales_changed(self):
+        self._epoch += 1
+        self._wq.clear()
+
+    @torch.no_grad()
+    def after_optimizer_step(self):
+        if self.interval > 1 and self.scale.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FP8: --fp8-interval > 1 cannot be captured in a graph (the interval is counted on "
+                               "the host and a replay would update on every step or on none); use --fp8-interval 1 "
+                               "or run the step eagerly")
+        self._step += 1
+        if self._step % self.interval:
+            return
+        group = _fp8_amax_group()
+        if group is not None:
+            dist.all_reduce(self.amax, op=dist.ReduceOp.MAX, group=group)
+        SF.fp8_update_scales(self.scale, self.amax_history, self.amax, self.fmt_max, self.margin, self.algo)
+        torch.reciprocal(self.scale, out=self.scale_inv)
+        self._scales_changed()
+
+    def slot(self, t: int):
+        """(scale, amax, 1 / scale) one-element views of table row ``t``."""
+        return self.scale[t:t + 1], self.amax[t:t + 1], self.scale_inv[t:t + 1]
+
+    def weight_q(self, weight, t: int):
+        """(q(W) [out, in], q(W)^T [in, out]) in E4M3, made once per optimizer step."""
+        key = (weight.data_ptr(), weight._version, tuple(weight.shape), weight.dtype, self._epoch)
+        hit = self._wq.get(id(weight))
+        if hit is not None and hit[0] == key:
+            return hit[1], hit[2]
+        scale, amax, _ = self.slot(t)
+        with torch.no_grad():
+            q, qt = SF.fp8_quantize(weight.detach(), scale, amax, "e4m3", transpose=True)
+        self._wq[id(weight)] = (key, q, qt)
+        return q, qt
+
+    def _save_to_state_dict(self, destination, prefix, keep_vars):
+        self.step_count.fill_(self._step)
+        super()._save_to_state_dict(destination, prefix, keep_vars)
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
+                              error_msgs):
+        names = ("scale", "amax_history", "amax", "step_count")
+        if not any(prefix + n in state_dict for n in names):
+            if not dist.is_initialized() or dist.get_rank() == 0:
+                print(f"FP8: the checkpoint holds no scaling state ({prefix}*): starting from scales 1", flush=True)
+            with torch.no_grad():
+                self.reset()
+            return
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
+                                      error_msgs)
+        with torch.no_grad():
+            torch.reciprocal(self.scale, out=self.scale_inv)
+        self._step = int(self.step_count.item())
+        self._scales_changed()
+
+
+def _fp8_amax_group():
+    """The group over which replicas of one weight see different data (dp x cp), or None when
+    there is a single replica."""
+    if not dist.is_initialized():
+        return None
+    st = ps.get_state()
+    group = getattr(st, "dp_cp_group", None) or getattr(st, "dp_group", None)
+    if group is None or isinstance(group, _lb.LoopbackGroup) or dist.get_world_size(group) <= 1:
+        return None
+    return group
+
+
+def fp8_after_optimizer_step(model):
+    """Advance the FP8 tables of ``model`` (a module or a list of model chunks) by one optimizer
+    step; a no-op for a model without FP8 linears."""
+    if not _FP8_STATES:
+        return
+    for chunk in (model if isinstance(model, (list, tuple)) else [model]):
+        for m in chunk.modules():
+            if isinstance(m, FP8State):
+                m.after_optimizer_step()
+
+
+def _fp8_rows(t, what):
+    t2 = t.reshape(-1, t.shape[-1])
+    if not t2.is_contiguous():
+        t2 = t2.contiguous()
+    if t2.shape[0] % 16 or t2.shape[1] % 16:
+        raise ValueError(f"FP8 linear: {what} has {t2.shape[0]} rows x {t2.shape[1]} columns; the FP8 GEMM needs "
+                         "multiples of 16 in every dimension")
+    return t2
+
+
+class FP8Linear(torch.autograd.Function):
+    """y = x W^T (+ b) at TP = 1 with FP8 forward and dgrad GEMMs (see the section comment).
+    ``slot0`` is the row of x in ``state``'s table (W: + 1, dY: + 2). ``bias`` always gets its
+    gradient; ``add_bias`` False leaves the addition to the caller (skip_bias_add)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, add_bias, state, slot0):
+        ctx.state, ctx.slot0 = state, slot0
+        ctx.has_bias = bias is not None
+        ctx.bias_p = bias
+        ctx.save_for_backward(x, weight)
+        x2 = _fp8_rows(x, "the input")
+        sx, ax, ix = state.slot(slot0)
+        qx = SF.fp8_quantize(x2, sx, ax, "e4m3")
+        qw, _ = state.weight_q(weight, slot0 + 1)
+        y = SF.fp8_gemm(qx, qw, ix, state.slot(slot0 + 1)[2], bias if (add_bias and bias is not None) else None,
+                        weight.dtype)
+        return y.view(tuple(x.shape[:-1]) + (weight.shape[0],))
+
+    @staticmethod
+    def backward(ctx, g):
+        x, weight = ctx.saved_tensors
+        state, slot0 = ctx.state, ctx.slot0
+        g2 = _fp8_rows(g, "the output gradient")
+        sg, ag, ig = state.slot(slot0 + 2)
+        qg = SF.fp8_quantize(g2, sg, ag, state.grad_fmt)
+        _, qwt = state.weight_q(weight, slot0 + 1)
+        gi = SF.fp8_gemm(qg, qwt, ig, state.slot(slot0 + 1)[2], None, weight.dtype).view(x.shape)
+        t2 = x.reshape(-1, x.shape[-1])
+        dw, db = _wgrad_and_bias(weight, ctx.bias_p if ctx.has_bias else None, g2, t2)
+        return gi, dw, db, None, None, None
+
+
+def attach_fp8(linears, state: FP8State):
+    """Give each linear (Column / RowParallelLinear) its three rows of ``state``'s table."""
+    for i, lin in enumerate(linears):
+        object.__setattr__(lin, "_fp8", (state, _FP8_SLOTS * i))    # a reference, not a submodule
 
 
 # fc1 + bias + GeLU(tanh) as ONE GEMM launch (gemm_tn.hip EPI_BIAS_GELU): the epilogue writes the
@@ -1424,7 +1643,9 @@ _LM_HEAD_CE = os.environ.get("SMDT_LM_HEAD_CE", "1") == "1"
 
 
 def linear_with_grad_accumulation_and_async_allreduce(x, weight, bias, sequence_parallel=False,
-                                                      async_grad_allreduce=False, add_bias=True):
+                                                      async_grad_allreduce=False, add_bias=True, fp8=None):
+    if fp8 is not None:                 # (FP8State, first table row) from attach_fp8; TP = 1
+        return FP8Linear.apply(x, weight, bias, add_bias, fp8[0], fp8[1])
     if sequence_parallel and _TP_OVERLAP and _tp_size() > 1:
         return _ColumnSPLinear.apply(x, weight, bias, add_bias)
     return LinearWithGradAccumulationAndAsyncCommunication.apply(x, weight, bias, sequence_parallel,
@@ -2224,6 +2445,8 @@ def init_full_then_shard(shape, std: float, key: str, base_seed: int, dtype, dev
 class ColumnParallelLinear(nn.Module):
     """Y = X A with A split along its output dim: rank holds A[:, rank-slice]."""
 
+    _fp8 = None     # (FP8State, table row) once attach_fp8 made this an FP8 linear
+
     def __init__(self, input_size, output_size, bias=True, gather_output=False, init_std=0.02, key="col",
                  seed=1234, params_dtype=torch.float32, device=None, sequence_parallel=False,
                  skip_bias_add=False, chunks=None, async_tensor_model_parallel_allreduce=True,
@@ -2260,11 +2483,11 @@ class ColumnParallelLinear(nn.Module):
             x = copy_to_tensor_model_parallel_region(x)
         if self.bias_grad_from_output:
             y = linear_with_grad_accumulation_and_async_allreduce(x, self.weight, self.bias, self.sequence_parallel,
-                                                                  self.async_ar, add_bias=False)
+                                                                  self.async_ar, add_bias=False, fp8=self._fp8)
         else:
             b = None if self.skip_bias_add else self.bias
             y = linear_with_grad_accumulation_and_async_allreduce(x, self.weight, b, self.sequence_parallel,
-                                                                  self.async_ar)
+                                                                  self.async_ar, fp8=self._fp8)
         if self.gather_output:
             y = gather_from_tensor_model_parallel_region(y)
         if self.skip_bias_add:
@@ -2275,6 +2498,8 @@ class ColumnParallelLinear(nn.Module):
 class RowParallelLinear(nn.Module):
     """Y = X A with A split along its input dim; partial outputs are all-reduced (or
     reduce-scattered along the sequence with sequence parallelism)."""
+
+    _fp8 = None     # (FP8State, table row) once attach_fp8 made this an FP8 linear
 
     def __init__(self, input_size, output_size, bias=True, input_is_parallel=True, init_std=0.02, key="row",
                  seed=1234, params_dtype=torch.float32, device=None, sequence_parallel=False,
@@ -2308,7 +2533,7 @@ class RowParallelLinear(nn.Module):
             y = linear_with_grad_accumulation_and_async_allreduce(x, self.weight, None, False, False)
             y = reduce_scatter_to_sequence_parallel_region(y)
         else:
-            y = linear_with_grad_accumulation_and_async_allreduce(x, self.weight, None, False, False)
+            y = linear_with_grad_accumulation_and_async_allreduce(x, self.weight, None, False, False, fp8=self._fp8)
             y = reduce_from_tensor_model_parallel_region(y)
         if self.skip_bias_add:
             return y, self.bias

@@ -10,8 +10,12 @@ Front-end parity with /root/reference/3_training_megatron-lm/megatron/arguments.
   * deprecated flags (``--batch-size``, ``--warmup``, ``--model-parallel-size``,
     ``--checkpoint-activations``) are rejected with the same advice.
 
-Flags that only matter on NVIDIA stacks (``--transformer-impl``, fp8) are accepted and
-ignored; table-driven groups keep the list easy to audit against the reference.
+``--fp8-e4m3`` / ``--fp8-hybrid`` (with ``--fp8-margin``, ``--fp8-interval``,
+``--fp8-amax-history-len``, ``--fp8-amax-compute-algo``) switch the four linears of every
+transformer layer to FP8 with delayed scaling (``TransformerConfig.fp8``); the weight gradient
+stays 16-bit whatever ``--no-fp8-wgrad`` says. Flags that only matter on NVIDIA stacks
+(``--transformer-impl``) are accepted and ignored; table-driven groups keep the list easy to
+audit against the reference.
 """
 from __future__ import annotations
 
@@ -330,8 +334,6 @@ _NO_EFFECT = [
     ("--embedding-weights-in-fp32", ("embedding_weights_in_fp32", False)),
     ("--fp16-lm-cross-entropy", ("fp16_lm_cross_entropy", False)),
     ("--transformer-impl", ("transformer_impl", "local")),
-    ("--fp8-e4m3", ("fp8_e4m3", False)),
-    ("--fp8-hybrid", ("fp8_hybrid", False)),
 ]
 
 
@@ -381,6 +383,7 @@ def validate_args(args, defaults=None):
         import warnings
         warnings.warn("accepted but ignored (task families this framework does not train: vision, "
                       "biencoder / ICT, Retro, inference): " + " ".join(ignored), stacklevel=2)
+    requested_tp = args.tensor_model_parallel_size
     args.tensor_model_parallel_size = min(args.tensor_model_parallel_size, args.world_size)
     assert args.world_size % args.tensor_model_parallel_size == 0, "world size not divisible by TP"
     args.pipeline_model_parallel_size = min(args.pipeline_model_parallel_size,
@@ -446,6 +449,25 @@ def validate_args(args, defaults=None):
         args.accumulate_allreduce_grads_in_fp32 = True   # Megatron forces fp32 grads with bf16
     if args.use_distributed_optimizer:
         assert args.DDP_impl == "local", "distributed optimizer requires local DDP"
+    # FP8 linears with delayed scaling (parallel/tensor_parallel.py FP8Linear)
+    args.fp8 = None
+    if args.fp8_e4m3 and args.fp8_hybrid:
+        raise ValueError("--fp8-e4m3 and --fp8-hybrid are mutually exclusive: pick one gradient format")
+    if args.fp8_e4m3 or args.fp8_hybrid:
+        flag = "--fp8-hybrid" if args.fp8_hybrid else "--fp8-e4m3"
+        if not (args.bf16 or args.fp16):
+            raise ValueError(f"{flag} needs 16-bit parameters: add --bf16 or --fp16")
+        if requested_tp > 1:
+            raise ValueError(f"{flag} with --tensor-model-parallel-size > 1 is not supported yet")
+        if args.num_experts:
+            raise ValueError(f"{flag} with --num-experts is not supported: the per-expert row counts are not "
+                             "multiples of 16")
+        if args.fp8_margin < 0 or args.fp8_interval < 1 or args.fp8_amax_history_len < 1:
+            raise ValueError("--fp8-margin must be >= 0, --fp8-interval and --fp8-amax-history-len >= 1")
+        args.fp8 = "hybrid" if args.fp8_hybrid else "e4m3"
+        if args.fp8_wgrad and args.rank == 0:
+            print(f"{flag}: weight gradients stay in {'bf16' if args.bf16 else 'fp16'} (as with --no-fp8-wgrad); "
+                  "FP8 covers the forward and input-gradient GEMMs", flush=True)
     # iterations / samples
     if args.train_iters is not None:
         assert args.train_samples is None
@@ -495,6 +517,17 @@ def validate_args(args, defaults=None):
         args.end_weight_decay = args.weight_decay
     # Flash attention is the default on gfx950; --no-flash-attn forces the unfused K1 path.
     args.use_flash_attn = (args.use_flash_attn or not args.no_flash_attn) and not args.no_flash_attn
+    if args.fp8:
+        # the FP8 GEMM takes multiples of 16 in every dimension: say so here, not in the first forward
+        flag = "--fp8-hybrid" if args.fp8 == "hybrid" else "--fp8-e4m3"
+        tokens = args.seq_length * args.micro_batch_size // max(args.context_parallel_size, 1)
+        dims = (("--seq-length x --micro-batch-size (tokens per micro-batch)", tokens),
+                ("--hidden-size", args.hidden_size), ("--ffn-hidden-size", args.ffn_hidden_size),
+                ("--num-attention-heads x --kv-channels", args.num_attention_heads * args.kv_channels),
+                ("--num-query-groups x --kv-channels", args.num_query_groups * args.kv_channels))
+        for name, v in dims:
+            if v % 16:
+                raise ValueError(f"{flag} needs {name} to be a multiple of 16, got {v}")
     return args
 
 
@@ -539,7 +572,11 @@ def core_transformer_config_from_args(args) -> TransformerConfig:
         apply_query_key_layer_scaling=args.apply_query_key_layer_scaling,
         recompute_granularity=args.recompute_granularity, recompute_method=args.recompute_method,
         recompute_num_layers=args.recompute_num_layers,
-        distribute_saved_activations=bool(args.distribute_saved_activations))
+        distribute_saved_activations=bool(args.distribute_saved_activations),
+        fp8=getattr(args, "fp8", None), fp8_margin=getattr(args, "fp8_margin", 0),
+        fp8_interval=getattr(args, "fp8_interval", 1),
+        fp8_amax_history_len=getattr(args, "fp8_amax_history_len", 1),
+        fp8_amax_compute_algo=getattr(args, "fp8_amax_compute_algo", "most_recent"))
 
 
 # ------------------------------------------------------------------------ micro-batch calculator (U2)
