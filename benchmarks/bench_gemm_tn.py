@@ -58,7 +58,8 @@ def main():
     p.add_argument("--max-blocks", type=int, default=0)
     p.add_argument("--ablate", nargs="*", type=int, default=None,
                    help="diagnostic kernel variants (VAR bits: 1 no DMA, 2 no fragment reads, "
-                        "4 no stagger, 8 no stores) timed on the --only shapes instead of the A/B")
+                        "4 no stagger, 8 no stores) timed on the --only shapes instead of the A/B; "
+                        "fc1_fwd / fc2_dgrad also run their GeLU epilogues with the epilogue ablations")
     a = p.parse_args()
     if a.tunableop and os.path.exists(TUNED):
         import tempfile
@@ -129,6 +130,20 @@ def main():
                     t = sorted(ts)[len(ts) // 2]
                     out_ab[f"{n}/gelu/var{v}"] = round(t, 4)
                     print(f"{n:12s} gelu var {v:2d}: {t:.4f} ms ({fl / t / 1e9:.0f} TF/s)", flush=True)
+            # the GeLU epilogues with the epilogue ablations: where their excess over the plain GEMM
+            # goes (8 no stores, 16 no bias / activation math, 24 both, 32 sc1 stores; EPI_DGELU
+            # also 512 no loads of the pre-activation, 528 neither loads nor math)
+            epi = {"fc1_fwd": 2, "fc2_dgrad": 3}.get(n)
+            if epi is not None:
+                bb = torch.randn(N, device=dev, dtype=torch.bfloat16) * 0.1
+                o2 = torch.empty_like(out) if epi == 2 else None
+                aux = torch.randn(M, N, device=dev, dtype=torch.bfloat16) if epi == 3 else None
+                for v in [0, 8, 16, 24, 32] + ([512, 528] if epi == 3 else []):
+                    ts = [timeit(lambda: C.gemm_tn(x, w, epi, bb, out, o2, a.max_blocks, v, aux), a.reps)
+                          for _ in range(a.rounds)]
+                    t = sorted(ts)[len(ts) // 2]
+                    out_ab[f"{n}/epi{epi}/var{v}"] = round(t, 4)
+                    print(f"{n:12s} epi {epi} var {v:3d}: {t:.4f} ms ({fl / t / 1e9:.0f} TF/s)", flush=True)
         print(json.dumps({"M": M, "ablate_ms": out_ab}))
         return
     for r in range(a.rounds):

@@ -33,9 +33,16 @@
 //
 // Measured on MI355X at the GPT-2 345M step shapes (benchmarks/bench_gemm_tn.py): 0.85-0.92x
 // of hipBLASLt's tuned GEMM (MT256x256x64, 4 waves of 128 x 128 with AGPR accumulators, 1.3-1.5
-// PFLOP/s) alone, 1.02x (fc1 + bias + GeLU) and 1.05x (fc2 dgrad + GeLU backward) against the
+// PFLOP/s) alone, 1.07x (fc1 + bias + GeLU) and 1.11x (fc2 dgrad + GeLU backward) against the
 // library GEMM followed by the elementwise pass. A 4-wave 128 x 128-per-wave form of this kernel
 // (plain double buffering) measured 0.69 vs 0.47 ms on fc1 and was removed.
+//
+// The GeLU epilogues are VALU-issue-bound in their math (no MFMA runs beside them), so the
+// activation is the sigmoid form on packed fp32 (activations.h): 56 / 83 VALU instructions per
+// 16-byte chunk (bias-GeLU / GeLU backward) where the tanh form on single lanes took 100 / 127,
+// 0.60 -> 0.56 ms and 0.63 -> 0.59 ms per call at the fc1 / fc2-dgrad shapes. What is left of
+// their excess over the plain GEMM is the second output's stores and the pre-activation loads
+// (the VAR ablations with an epilogue; profiles/gelu_epilogue/).
 #include "activations.h"
 #include "common.h"
 #include "launchers.h"
@@ -198,8 +205,9 @@ __device__ __forceinline__ uint32_t lds_addr(const void* p) {
 
 // VAR: diagnostic ablations for benchmarks/bench_gemm_tn.py only (the library runs VAR = 0):
 // bit 0 no in-loop DMA, bit 1 no in-loop fragment reads, bit 2 no wave stagger, bit 3 no stores,
-// bit 5 sc1 (L2-bypassing) output stores instead of plain ones; (host) bit 7 / 8 tile groups of 1 / 4
-// row blocks instead of 8.
+// bit 4 no bias / activation math in the epilogue (loads and stores stay), bit 5 sc1
+// (L2-bypassing) output stores instead of plain ones, bit 9 EPI_DGELU without the loads of the
+// pre-activation; (host) bit 7 / 8 tile groups of 1 / 4 row blocks instead of 8.
 template <class E, int EPI, int VAR = 0>
 __global__ __launch_bounds__(kThreads, 1) void gemm_tn_kernel(const Args g) {
   using V = typename V8<E>::t;
@@ -308,8 +316,8 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_tn_kernel(const Args g) {
   int otile = rb;
   constexpr int NOUT = EPI == EPI_BIAS_GELU ? 2 : 1;
   constexpr int kStores = 16 * NOUT;   // 16-byte stores per wave of one epilogue
-  u32x4 bias_w;                        // 8 bias values of this lane's 16-byte column chunk
-  (void)bias_w;
+  f32x2 bias2[4];                      // 8 bias values of this lane's 16-byte column chunk
+  (void)bias2;
   const uint32_t epi_l = l0 + kNSlot * kSlot + wave * kEpiB;
 
   auto sync = [&]() {
@@ -401,37 +409,35 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_tn_kernel(const Args g) {
   auto lds_r16 = [&](uint32_t addr) -> u32x4 {
     return *(__attribute__((address_space(3))) const u32x4*)(uintptr_t)addr;
   };
-  // bias / activation on 8 consecutive values of one row (chunk rc), o = 0 the first output
+  // bias / activation on 8 consecutive values of one row (chunk rc), o = 0 the first output.
+  // The fp32 math runs on pairs (v_pk_*_f32: two elements per issue slot; activations.h), against
+  // the tile's bias unpacked once (bias2).
   auto finish8 = [&](u32x4 v, int o, u32x4 pv) -> u32x4 {
     if constexpr (EPI == EPI_NONE) {
       return v;
     } else {
       if (EPI == EPI_BIAS_GELU && o == 0) return v;   // the pre-activation
-      u32x2 lo = {v[0], v[1]}, hi = {v[2], v[3]};
-      if constexpr (EPI == EPI_DGELU) {   // v = d(activation), pv = pre-activation
-        u32x2 plo = {pv[0], pv[1]}, phi = {pv[2], pv[3]};
-        float x[8], z[8], b[8];
-        u32x2 blo = {bias_w[0], bias_w[1]}, bhi = {bias_w[2], bias_w[3]};
-        unpack4<E>(lo, *reinterpret_cast<float(*)[4]>(x));
-        unpack4<E>(hi, *reinterpret_cast<float(*)[4]>(x + 4));
-        unpack4<E>(plo, *reinterpret_cast<float(*)[4]>(z));
-        unpack4<E>(phi, *reinterpret_cast<float(*)[4]>(z + 4));
-        unpack4<E>(blo, *reinterpret_cast<float(*)[4]>(b));
-        unpack4<E>(bhi, *reinterpret_cast<float(*)[4]>(b + 4));
-#pragma unroll
-        for (int e = 0; e < 8; ++e) x[e] = x[e] * gelu_tanh_grad(z[e] + b[e]);
-        const u32x2 ol = pack4<E>(x[0], x[1], x[2], x[3]), oh = pack4<E>(x[4], x[5], x[6], x[7]);
-        return u32x4{ol[0], ol[1], oh[0], oh[1]};
+      if constexpr ((VAR & 16) != 0) {                // ablation: no bias / activation math
+        if constexpr (EPI == EPI_DGELU) asm volatile("" ::"v"(pv));   // (the loads stay)
+        return v;
       }
-      u32x2 blo = {bias_w[0], bias_w[1]}, bhi = {bias_w[2], bias_w[3]};
-      float x[8], b[8];
-      unpack4<E>(lo, *reinterpret_cast<float(*)[4]>(x));
-      unpack4<E>(hi, *reinterpret_cast<float(*)[4]>(x + 4));
-      unpack4<E>(blo, *reinterpret_cast<float(*)[4]>(b));
-      unpack4<E>(bhi, *reinterpret_cast<float(*)[4]>(b + 4));
+      float xf[8];
+      unpack4<E>(u32x2{v[0], v[1]}, *reinterpret_cast<float(*)[4]>(xf));
+      unpack4<E>(u32x2{v[2], v[3]}, *reinterpret_cast<float(*)[4]>(xf + 4));
+      f32x2 x[4];
 #pragma unroll
-      for (int e = 0; e < 8; ++e) x[e] = EPI == EPI_BIAS ? x[e] + b[e] : gelu_tanh(x[e] + b[e]);
-      const u32x2 ol = pack4<E>(x[0], x[1], x[2], x[3]), oh = pack4<E>(x[4], x[5], x[6], x[7]);
+      for (int e = 0; e < 4; ++e) x[e] = f32x2{xf[2 * e], xf[2 * e + 1]};
+      if constexpr (EPI == EPI_DGELU) {   // v = d(activation), pv = pre-activation
+        float zf[8];
+        unpack4<E>(u32x2{pv[0], pv[1]}, *reinterpret_cast<float(*)[4]>(zf));
+        unpack4<E>(u32x2{pv[2], pv[3]}, *reinterpret_cast<float(*)[4]>(zf + 4));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x[e] = x[e] * gelu_tanh_grad(f32x2{zf[2 * e], zf[2 * e + 1]} + bias2[e]);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x[e] = EPI == EPI_BIAS ? x[e] + bias2[e] : gelu_tanh(x[e] + bias2[e]);
+      }
+      const u32x2 ol = pack4<E>(x[0][0], x[0][1], x[1][0], x[1][1]), oh = pack4<E>(x[2][0], x[2][1], x[3][0], x[3][1]);
       return u32x4{ol[0], ol[1], oh[0], oh[1]};
     }
   };
@@ -443,7 +449,12 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_tn_kernel(const Args g) {
   auto epilogue = [&]() {
     if constexpr (EPI != EPI_NONE) {
       wait_vm<4 * kGl>();   // the bias DMA: older than stage u + 2's 4 halves (and retired already)
-      bias_w = lds_r16(epi_l + 2048 + (lane_now() & 7) * 16);
+      const u32x4 bias_w = lds_r16(epi_l + 2048 + (lane_now() & 7) * 16);
+      float bf[8];   // unpacked once per tile, not once per 16-byte chunk
+      unpack4<E>(u32x2{bias_w[0], bias_w[1]}, *reinterpret_cast<float(*)[4]>(bf));
+      unpack4<E>(u32x2{bias_w[2], bias_w[3]}, *reinterpret_cast<float(*)[4]>(bf + 4));
+#pragma unroll
+      for (int e = 0; e < 4; ++e) bias2[e] = f32x2{bf[2 * e], bf[2 * e + 1]};
     }
     int otm, otn;
     coords(otile, otm, otn);
@@ -451,7 +462,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_tn_kernel(const Args g) {
     // EPI_DGELU: the pre-activation rows of the whole wave tile (16 x 16 B per lane, in the
     // read-side layout), issued before any block so their latency overlaps the first blocks
     u32x4 pre_v[8][2];
-    if constexpr (EPI == EPI_DGELU) {
+    if constexpr (EPI == EPI_DGELU && !(VAR & 512)) {
       const int ln = lane_now(), rr = ln >> 3, rc = ln & 7;
       const E* pre = (const E*)g.aux + (int64_t)(otm * kT + 128 * wr + rr) * N + otn * kT + 64 * wc + 8 * rc;
 #pragma unroll
@@ -484,7 +495,8 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_tn_kernel(const Args g) {
 #pragma unroll
         for (int o = 0; o < NOUT; ++o) {
           E* dst = (E*)(o == 0 ? g.C : g.C2) + off + (int64_t)(8 * h) * N;
-          const u32x4 w = finish8(rv[h], o + (EPI == EPI_BIAS ? 1 : 0), pre_v[k][h]);
+          // (VAR bit 9, no aux load: the product stands in for the pre-activation, the math stays)
+          const u32x4 w = finish8(rv[h], o + (EPI == EPI_BIAS ? 1 : 0), (VAR & 512) ? rv[h] : pre_v[k][h]);
           if constexpr ((VAR & 8) != 0) asm volatile("" ::"v"(w));
           else if constexpr ((VAR & 32) != 0) store16_sc1(dst, w);
           else *(u32x4*)dst = w;
@@ -570,20 +582,42 @@ extern "C" hipError_t smdt_gemm_tn_var(int dtype, int epi, const void* a, const 
   if (max_blocks > 0 && max_blocks < grid) grid = max_blocks;
   if (grid > g.tiles) grid = g.tiles;
 #define SMDT_GT(E, P) hipLaunchKernelGGL((gt::gemm_tn_kernel<E, P>), dim3(grid), dim3(gt::kThreads), 0, st, g)
-#define SMDT_GTV(V) hipLaunchKernelGGL((gt::gemm_tn_kernel<bf16, 0, V>), dim3(grid), dim3(gt::kThreads), 0, st, g)
-  if (var != 0) {   // diagnostic ablations: bf16, no epilogue
-    if (dtype != 1 || epi != 0) return hipErrorInvalidValue;
-    switch (var) {
-      case 1: SMDT_GTV(1); break;
-      case 2: SMDT_GTV(2); break;
-      case 3: SMDT_GTV(3); break;
-      case 4: SMDT_GTV(4); break;
-      case 8: SMDT_GTV(8); break;
-      case 11: SMDT_GTV(11); break;
-      case 32: SMDT_GTV(32); break;
-      case 128: SMDT_GTV(0); break;    // (tile order only: g.gm)
-      case 256: SMDT_GTV(0); break;
-      default: return hipErrorInvalidValue;
+#define SMDT_GTV(P, V) hipLaunchKernelGGL((gt::gemm_tn_kernel<bf16, P, V>), dim3(grid), dim3(gt::kThreads), 0, st, g)
+  if (var != 0) {   // diagnostic ablations: bf16; main-loop variants without an epilogue, the
+                    // epilogue ones (8 no stores, 16 no math, 32 sc1 stores, 512 no aux load)
+                    // also with the GeLU epilogues
+    if (dtype != 1 || epi == 1) return hipErrorInvalidValue;
+    if (epi == 0) {
+      switch (var) {
+        case 1: SMDT_GTV(0, 1); break;
+        case 2: SMDT_GTV(0, 2); break;
+        case 3: SMDT_GTV(0, 3); break;
+        case 4: SMDT_GTV(0, 4); break;
+        case 8: SMDT_GTV(0, 8); break;
+        case 11: SMDT_GTV(0, 11); break;
+        case 32: SMDT_GTV(0, 32); break;
+        case 128: SMDT_GTV(0, 0); break;    // (tile order only: g.gm)
+        case 256: SMDT_GTV(0, 0); break;
+        default: return hipErrorInvalidValue;
+      }
+    } else if (epi == 2) {
+      switch (var) {
+        case 8: SMDT_GTV(2, 8); break;
+        case 16: SMDT_GTV(2, 16); break;
+        case 24: SMDT_GTV(2, 24); break;
+        case 32: SMDT_GTV(2, 32); break;
+        default: return hipErrorInvalidValue;
+      }
+    } else {
+      switch (var) {
+        case 8: SMDT_GTV(3, 8); break;
+        case 16: SMDT_GTV(3, 16); break;
+        case 24: SMDT_GTV(3, 24); break;
+        case 32: SMDT_GTV(3, 32); break;
+        case 512: SMDT_GTV(3, 512); break;
+        case 528: SMDT_GTV(3, 528); break;
+        default: return hipErrorInvalidValue;
+      }
     }
     return hipGetLastError();
   }

@@ -137,7 +137,8 @@ hipError_t smdt_flash_bwd_doc(int dtype, const void* q, const void* k, const voi
 int smdt_gemm_tn_supported(int64_t M, int64_t N, int64_t K);
 hipError_t smdt_gemm_tn(int dtype, int epi, const void* a, const void* b, void* c, void* c2, const void* bias,
                         const void* aux, int64_t M, int64_t N, int64_t K, int max_blocks, hipStream_t st);
-// diagnostic ablations of the same kernel (benchmarks only): var bits as gemm_tn_kernel's VAR
+// diagnostic ablations of the same kernel (benchmarks only): var bits as gemm_tn_kernel's VAR;
+// bf16, epi 0, or epi 2 / 3 with the epilogue variants (8, 16, 24, 32; epi 3 also 512, 528)
 hipError_t smdt_gemm_tn_var(int dtype, int epi, const void* a, const void* b, void* c, void* c2, const void* bias,
                             const void* aux, int64_t M, int64_t N, int64_t K, int max_blocks, int var,
                             hipStream_t st);
