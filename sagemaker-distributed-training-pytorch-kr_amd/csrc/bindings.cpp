@@ -517,6 +517,40 @@ std::vector<Tensor> gemm_tn(Tensor a, Tensor b, int64_t epi, OptT bias, OptT out
   return {c};
 }
 
+// The GeLU-backward epilogue (epi 3) that also makes the bias gradient of the linear whose dY it
+// writes: out = (a . b^T) * gelu_tanh'(aux + bias), and dbias[N] (fp32) = / += the column sums of
+// the fp32 output values before their 16-bit rounding (per-half-tile partials from the kernel,
+// added in a fixed order by the column-sum kernel: no atomics, bitwise reproducible).
+Tensor gemm_tn_dgelu_dbias(Tensor a, Tensor b, Tensor bias, Tensor aux, Tensor dbias, bool accumulate, OptT out,
+                           int64_t max_blocks) {
+  TORCH_CHECK(gemm_tn_supported(a, b), "gemm_tn_dgelu_dbias: unsupported operands");
+  const int64_t M = a.size(0), N = b.size(0), K = a.size(1);
+  need_contig(bias, "bias");
+  need_contig(aux, "aux");
+  TORCH_CHECK(bias.numel() == N && bias.scalar_type() == a.scalar_type(), "gemm_tn_dgelu_dbias: bias mismatch");
+  TORCH_CHECK(aux.numel() == M * N && aux.scalar_type() == a.scalar_type() && aux.device() == a.device(),
+              "gemm_tn_dgelu_dbias: pre-activation mismatch");
+  Tensor db = acc_target(dbias, N, "gemm_tn_dgelu_dbias dbias");
+  TORCH_CHECK(db.device() == a.device(), "gemm_tn_dgelu_dbias: dbias on another device");
+  Tensor c;
+  if (out) {
+    need_contig(*out, "out");
+    TORCH_CHECK(out->numel() == M * N && out->scalar_type() == a.scalar_type() && out->device() == a.device(),
+                "gemm_tn_dgelu_dbias: output buffer mismatch");
+    c = *out;
+  } else {
+    c = torch::empty({M, N}, a.options());
+  }
+  auto part = torch::empty({M / 128, N}, a.options().dtype(at::kFloat));
+  check(smdt_gemm_tn_dgelu_sums(dcode(a), a.data_ptr(), b.data_ptr(), c.data_ptr(), bias.data_ptr(), aux.data_ptr(),
+                                part.data_ptr<float>(), M, N, K, (int)max_blocks, cur_stream()),
+        "gemm_tn_dgelu_dbias");
+  check(smdt_col_sum(part.data_ptr<float>(), (int)(M / 128), (int)N, db.data_ptr<float>(), accumulate ? 1 : 0,
+                     cur_stream()),
+        "gemm_tn_dgelu_dbias column sums");
+  return c;
+}
+
 // ------------------------------------------------------------------ weight gradient (MFMA)
 // main_grad[N, K] (fp32) += dy[M, N]^T . x[M, K]; returns false when the shape is unsupported.
 bool wgrad_mfma(Tensor main_grad, Tensor dy, Tensor x, int64_t max_splits) {
@@ -709,9 +743,14 @@ std::vector<Tensor> flash_fwd(Tensor q, Tensor k, Tensor v, double scale, bool c
 
 // dq / dk / dv (optional) are preallocated [B, S, H(kv), D] views with any strides, typically
 // views into one fused d(QKV) buffer so the QKV projection backward needs no concatenation.
-std::vector<Tensor> flash_bwd(Tensor q, Tensor k, Tensor v, Tensor o, Tensor dout, Tensor lse,
-                              double scale, bool causal, OptT dq_out, OptT dk_out, OptT dv_out,
-                              double dropout_p, int64_t seed, int64_t offset, OptT doc_start, OptT doc_end) {
+// ``dbias`` (flash_bwd_dbias; fp32 [(H + 2 Hkv) D]): = / += the sums over all tokens of the fp32
+// dQ | dK | dV before their 16-bit rounding, i.e. the bias gradient of the fused QKV projection
+// whose output q / k / v are views of — per-block partials from the kernels, added in a fixed
+// order by the column-sum kernel (no atomics, bitwise reproducible).
+static std::vector<Tensor> flash_bwd_any(Tensor q, Tensor k, Tensor v, Tensor o, Tensor dout, Tensor lse,
+                                         double scale, bool causal, OptT dq_out, OptT dk_out, OptT dv_out,
+                                         double dropout_p, int64_t seed, int64_t offset, OptT doc_start,
+                                         OptT doc_end, OptT dbias, bool accumulate) {
   fa_check(q, "q"); fa_check(k, "k"); fa_check(v, "v"); fa_check(o, "o");
   TORCH_CHECK(k.scalar_type() == q.scalar_type() && v.scalar_type() == q.scalar_type() &&
               o.scalar_type() == q.scalar_type() && dout.scalar_type() == q.scalar_type(), "flash_bwd: dtypes differ");
@@ -740,6 +779,23 @@ std::vector<Tensor> flash_bwd(Tensor q, Tensor k, Tensor v, Tensor o, Tensor dou
   const int* ds = fa_doc_ptr(doc_start, q, "doc_start");
   const int* de = fa_doc_ptr(doc_end, q, "doc_end");
   TORCH_CHECK((ds == nullptr) == (de == nullptr), "flash_bwd: doc_start and doc_end come together");
+  if (dbias) {
+    TORCH_CHECK(!ds || causal, "flash_bwd: doc_start needs causal attention");
+    const int64_t N = (H + 2 * Hkv) * D, nblk = B * (S / 128);
+    Tensor db = acc_target(dbias, N, "flash_bwd_dbias dbias");
+    TORCH_CHECK(db.device() == q.device(), "flash_bwd_dbias: dbias on another device");
+    auto part = torch::empty({nblk, N}, q.options().dtype(at::kFloat));
+    check(smdt_flash_bwd_sums(dcode(q), q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), dout.data_ptr(),
+                              lse.data_ptr<float>(), delta.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(),
+                              dv.data_ptr(), (int)B, (int)H, (int)Hkv, (int)S, (int)D, st, (float)scale,
+                              causal ? 1 : 0, (float)dropout_p, (uint64_t)seed, (uint64_t)offset, ds, de,
+                              part.data_ptr<float>(), cur_stream()),
+          "flash_bwd_dbias");
+    check(smdt_col_sum(part.data_ptr<float>(), (int)nblk, (int)N, db.data_ptr<float>(), accumulate ? 1 : 0,
+                       cur_stream()),
+          "flash_bwd_dbias column sums");
+    return {dq, dk, dv};
+  }
   if (ds) {
     TORCH_CHECK(causal, "flash_bwd: doc_start needs causal attention");
     check(smdt_flash_bwd_doc(dcode(q), q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), dout.data_ptr(),
@@ -755,6 +811,21 @@ std::vector<Tensor> flash_bwd(Tensor q, Tensor k, Tensor v, Tensor o, Tensor dou
                        causal ? 1 : 0, (float)dropout_p, (uint64_t)seed, (uint64_t)offset, cur_stream()),
         "flash_bwd");
   return {dq, dk, dv};
+}
+
+std::vector<Tensor> flash_bwd(Tensor q, Tensor k, Tensor v, Tensor o, Tensor dout, Tensor lse,
+                              double scale, bool causal, OptT dq_out, OptT dk_out, OptT dv_out,
+                              double dropout_p, int64_t seed, int64_t offset, OptT doc_start, OptT doc_end) {
+  return flash_bwd_any(q, k, v, o, dout, lse, scale, causal, dq_out, dk_out, dv_out, dropout_p, seed, offset,
+                       doc_start, doc_end, c10::nullopt, false);
+}
+
+std::vector<Tensor> flash_bwd_dbias(Tensor q, Tensor k, Tensor v, Tensor o, Tensor dout, Tensor lse,
+                                    double scale, bool causal, Tensor dbias, bool accumulate, OptT dq_out,
+                                    OptT dk_out, OptT dv_out, double dropout_p, int64_t seed, int64_t offset,
+                                    OptT doc_start, OptT doc_end) {
+  return flash_bwd_any(q, k, v, o, dout, lse, scale, causal, dq_out, dk_out, dv_out, dropout_p, seed, offset,
+                       doc_start, doc_end, dbias, accumulate);
 }
 
 // ------------------------------------------------------------------ xGMI all-reduce (HIP IPC)
@@ -1022,4 +1093,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("lse"), py::arg("scale"), py::arg("causal"), py::arg("dq") = py::none(), py::arg("dk") = py::none(),
         py::arg("dv") = py::none(), py::arg("dropout_p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0,
         py::arg("doc_start") = py::none(), py::arg("doc_end") = py::none());
+  m.def("flash_bwd_dbias", &flash_bwd_dbias, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("dout"),
+        py::arg("lse"), py::arg("scale"), py::arg("causal"), py::arg("dbias"), py::arg("accumulate"),
+        py::arg("dq") = py::none(), py::arg("dk") = py::none(), py::arg("dv") = py::none(),
+        py::arg("dropout_p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0,
+        py::arg("doc_start") = py::none(), py::arg("doc_end") = py::none());
+  m.def("gemm_tn_dgelu_dbias", &gemm_tn_dgelu_dbias, py::arg("a"), py::arg("b"), py::arg("bias"), py::arg("aux"),
+        py::arg("dbias"), py::arg("accumulate"), py::arg("out") = py::none(), py::arg("max_blocks") = 0);
 }

@@ -573,6 +573,41 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fwd_kernel(const E* __re
 // separate streaming delta kernel: 1.6 ms per GPT-2 345M step)
 
 // ---------------------------------------------------------------------------------------
+// SUMS variants of the backward kernels: besides dQ (dK, dV) they emit the sums over the
+// workgroup's 128 tokens of the fp32 values they are about to round, one row of an fp32 partials
+// slab per workgroup ([B * S / 128, ld], a column per (head, d)). smdt_col_sum adds the rows in a
+// fixed order: that is the bias gradient of the QKV projection whose output the kernels read in
+// place, so the grouped wgrad needs no bias tiles for it (no atomics, bitwise reproducible). The
+// work is a once-per-workgroup epilogue after the tile loop; SUMS is a template flag and the plain
+// instantiations are unchanged.
+//
+// The token sits on the lane, so the sum crosses lanes: each wave transposes one 32 (d) x 32
+// (token) accumulator tile at a time through 4 KB of LDS of its own (the wave's LDS operations
+// retire in order: no workgroup barrier), lane l adds 16 tokens of column l / 2 and its
+// neighbour the other 16. out[0 .. D) receives the wave's sums of acc * c.
+template <int D>
+__device__ __forceinline__ void wave_token_sums(const f32x16 (&acc)[Geo<D>::DT], float c, float* slab,
+                                                float* out, int lane) {
+  const int q = lane & 31, h = lane >> 5;
+#pragma unroll
+  for (int dt = 0; dt < Geo<D>::DT; ++dt) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) slab[(8 * (i >> 2) + 4 * h + (i & 3)) * 32 + q] = acc[dt][i] * c;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the other lanes' values are in place
+    const f32x4* row = reinterpret_cast<const f32x4*>(slab + (lane >> 1) * 32 + 16 * (lane & 1));
+    float s = 0.f;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const f32x4 v = row[u];
+      s += (v[0] + v[1]) + (v[2] + v[3]);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // read before the next tile overwrites the slab
+    s += __uint_as_float(swap_lane1(__float_as_uint(s)));
+    if ((lane & 1) == 0) out[32 * dt + (lane >> 1)] = s;
+  }
+}
+
+// ---------------------------------------------------------------------------------------
 // dK / dV. Workgroup = 4 waves = 128 keys of one (b, kv-head); each wave keeps K, V of its 32
 // keys and dK^T, dV^T in registers while the workgroup sweeps the query heads of the group and
 // their 64-row query tiles (Q, dO, lse*log2e, delta staged in double-buffered LDS).
@@ -599,13 +634,14 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fwd_kernel(const E* __re
 #ifndef SMDT_FA_DKDV_OCC
 #define SMDT_FA_DKDV_OCC 2
 #endif
-template <int D, bool CAUSAL, bool DROP, class E, bool DOC = false>
+template <int D, bool CAUSAL, bool DROP, class E, bool DOC = false, bool SUMS = false>
 __global__ __launch_bounds__(256, D == 64 ? SMDT_FA_DKDV_OCC : 1) void bwd_dkdv_kernel(
     const E* __restrict__ Q, const E* __restrict__ K, const E* __restrict__ V,
     const E* __restrict__ dO, const E* __restrict__ RC3,
     const float* __restrict__ DELTA, E* __restrict__ dK, E* __restrict__ dV, int B, int H, int Hkv, int S,
     Strides qs, Strides ks_, Strides vs, Strides dos, Strides dks, Strides dvs, float scale, Drop drop,
-    const int* __restrict__ DEND = nullptr) {
+    const int* __restrict__ DEND = nullptr, float* __restrict__ SUMK = nullptr,
+    float* __restrict__ SUMV = nullptr, int64_t sum_ld = 0) {
   static_assert(!DOC || CAUSAL, "per-document attention is causal");
   using G = Geo<D>;
   using VF = v8_t<E>;
@@ -882,6 +918,25 @@ __global__ __launch_bounds__(256, D == 64 ? SMDT_FA_DKDV_OCC : 1) void bwd_dkdv_
 #endif
   wait_vm<0>();  // drain the trailing re-reads before the workgroup's LDS is released
 
+  if constexpr (SUMS) {
+    // sums over the block's 128 keys of the fp32 dK (scaled) and dV: row b * S / 128 + kblk of the
+    // partials, this kv-head's D columns (the group's query heads are summed in dk / dv already)
+    // The stage buffers are free now (every wave's DMA has landed and its last reads are behind
+    // the barrier): 4 KB of the Q slots per wave for the transposes, the first dO slot for the
+    // waves' sums, so the SUMS variants need no LDS of their own and keep the occupancy.
+    static_assert(G::TB >= 2 * 4096 && G::TB >= 4 * 2 * D * 4, "stage slots hold the sum buffers");
+    __syncthreads();
+    float* slab = reinterpret_cast<float*>(D == 64 ? (w < 2 ? Q0 : Q1) + (w & 1) * 4096 : Q0 + w * 4096);
+    float* wsum = reinterpret_cast<float*>(O0);   // [4][2 D]
+    wave_token_sums<D>(dk, scale, slab, wsum + w * 2 * D, lane);
+    wave_token_sums<D>(dv, 1.f, slab, wsum + w * 2 * D + D, lane);
+    __syncthreads();
+    if (threadIdx.x < 2 * D) {
+      const int t = threadIdx.x, d = t < D ? t : t - D;
+      const float s = ((wsum[t] + wsum[2 * D + t]) + wsum[4 * D + t]) + wsum[6 * D + t];
+      (t < D ? SUMK : SUMV)[((int64_t)b * nkb + kblk) * sum_ld + hk * D + d] = s;
+    }
+  }
 
   // dK[key, d] = scale * dK^T ; dV[key, d] = dV^T (key on lane, d in registers)
   E* dKb = dK + b * dks.sb + hk * dks.sh + (int64_t)my_key * dks.ss;
@@ -905,13 +960,14 @@ __global__ __launch_bounds__(256, D == 64 ? SMDT_FA_DKDV_OCC : 1) void bwd_dkdv_
 // ---------------------------------------------------------------------------------------
 // dQ. Workgroup = 4 waves = 128 query rows of one (b, h); K/V streamed in 64-key tiles,
 // double-buffered.
-template <int D, bool CAUSAL, bool DROP, class E, bool DOC = false>
+template <int D, bool CAUSAL, bool DROP, class E, bool DOC = false, bool SUMS = false>
 __global__ __launch_bounds__(256, D == 64 ? SMDT_FA_DQ_OCC : 1) void bwd_dq_kernel(
     const E* __restrict__ Q, const E* __restrict__ K, const E* __restrict__ V,
     const E* __restrict__ dO, const E* __restrict__ O, const float* __restrict__ LSE,
     float* __restrict__ DELTA, E* __restrict__ RC3, E* __restrict__ dQ, int B, int H, int Hkv,
     int S, Strides qs, Strides ks_, Strides vs, Strides dos, Strides os, Strides dqs, float scale,
-    float dscale, float lsub, Drop drop, const int* __restrict__ DSTART = nullptr) {
+    float dscale, float lsub, Drop drop, const int* __restrict__ DSTART = nullptr,
+    float* __restrict__ SUMQ = nullptr, int64_t sum_ld = 0) {
   static_assert(!DOC || CAUSAL, "per-document attention is causal");
   using G = Geo<D>;
   // D = 64: three [K | V] buffers, two tiles in flight; D = 128 (twice the bytes): two buffers,
@@ -1130,6 +1186,24 @@ __global__ __launch_bounds__(256, D == 64 ? SMDT_FA_DQ_OCC : 1) void bwd_dq_kern
   }
   wait_vm<0>();
 
+  if constexpr (SUMS) {
+    // sums over the block's 128 queries of the fp32 dQ (scaled): row b * S / 128 + qb of the
+    // partials, this head's D columns
+    // The K / V buffers are free now (every wave's DMA has landed and its last reads are behind
+    // the barrier): L0 holds the waves' 4 KB transposes, L1 their sums, so the SUMS variants need
+    // no LDS of their own and keep the occupancy.
+    static_assert(2 * G::TB >= 4 * 4096, "L0 holds the four transposes");
+    __syncthreads();
+    float* slab = reinterpret_cast<float*>(L0 + w * 4096);
+    float* wsum = reinterpret_cast<float*>(L1);   // [4][D]
+    wave_token_sums<D>(dq, scale, slab, wsum + w * D, lane);
+    __syncthreads();
+    if (threadIdx.x < D) {
+      const int t = threadIdx.x;
+      SUMQ[((int64_t)b * nqb + qb) * sum_ld + hq * D + t] = ((wsum[t] + wsum[D + t]) + wsum[2 * D + t]) + wsum[3 * D + t];
+    }
+  }
+
   E* dQb = dQ + b * dqs.sb + hq * dqs.sh + (int64_t)my_q * dqs.ss;
 #pragma unroll
   for (int dt = 0; dt < G::DT; ++dt) {
@@ -1260,9 +1334,15 @@ static hipError_t flash_bwd_impl(int dtype, const void* q, const void* k, const 
                                  float* delta, void* dq, void* dk, void* dv, int B, int H,
                                  int Hkv, int S, int D, const int64_t* strides, float scale,
                                  int causal, float dropout_p, uint64_t seed, uint64_t offset,
-                                 const int* doc_start, const int* doc_end, hipStream_t st) {
+                                 const int* doc_start, const int* doc_end, float* colpart, hipStream_t st) {
   if (!fa_shape_ok(dtype, H, Hkv, S, D) || dropout_p < 0.f || dropout_p >= 1.f) return hipErrorInvalidValue;
   if ((doc_start == nullptr) != (doc_end == nullptr) || (doc_start && !causal)) return hipErrorInvalidValue;
+  // colpart (may be null): fp32 [B * S / 128, (H + 2 Hkv) D], the token sums of dQ | dK | dV per
+  // 128-token block in the column order of a fused QKV projection output (the SUMS kernels)
+  const int64_t sum_ld = (int64_t)(H + 2 * Hkv) * D;
+  float* sumq = colpart;
+  float* sumk = colpart ? colpart + (int64_t)H * D : nullptr;
+  float* sumv = colpart ? sumk + (int64_t)Hkv * D : nullptr;
   const Drop dr = make_drop(dropout_p, seed, offset);
   const bool drop = dropout_p > 0.f;
   // strides: 8 x (batch, seq, head) element strides for q, k, v, o, dO, dQ, dK, dV.
@@ -1278,31 +1358,25 @@ static hipError_t flash_bwd_impl(int dtype, const void* q, const void* k, const 
   const float dscale = drop ? dr.keep : 1.f, lsub = drop ? dr.log2inv : 0.f;
   dim3 gkv((unsigned)((int64_t)B * Hkv * (S / kBlockRows)));
   dim3 gq((unsigned)((int64_t)B * H * (S / kBlockRows)));
-#define SMDT_FA_BWD_T(DD, CC, DR, ET)                                                            \
+#define SMDT_FA_BWD_K(DD, CC, DR, ET, DOCF, SM)                                                  \
   do {                                                                                           \
-    hipLaunchKernelGGL((bwd_dq_kernel<DD, CC, DR, ET>), gq, dim3(256), 0, st, (const ET*)q,      \
-                       (const ET*)k, (const ET*)v, (const ET*)dout, (const ET*)o, lse, delta,     \
-                       (ET*)rc3, (ET*)dq, B, H, Hkv, S, qs, ks, vs, dos, os, dqs,                 \
-                       scale, dscale, lsub, dr);                                                  \
-    hipLaunchKernelGGL((bwd_dkdv_kernel<DD, CC, DR, ET>), gkv, dim3(256), 0, st, (const ET*)q,  \
-                       (const ET*)k, (const ET*)v, (const ET*)dout, (const ET*)rc3, delta,        \
-                       (ET*)dk, (ET*)dv, B, H, Hkv, S, qs, ks, vs, dos, dks, dvs, scale, dr);     \
+    hipLaunchKernelGGL((bwd_dq_kernel<DD, CC, DR, ET, DOCF, SM>), gq, dim3(256), 0, st,          \
+                       (const ET*)q, (const ET*)k, (const ET*)v, (const ET*)dout, (const ET*)o,   \
+                       lse, delta, (ET*)rc3, (ET*)dq, B, H, Hkv, S, qs, ks, vs, dos, os, dqs,     \
+                       scale, dscale, lsub, dr, doc_start, sumq, sum_ld);                         \
+    hipLaunchKernelGGL((bwd_dkdv_kernel<DD, CC, DR, ET, DOCF, SM>), gkv, dim3(256), 0, st,       \
+                       (const ET*)q, (const ET*)k, (const ET*)v, (const ET*)dout, (const ET*)rc3, \
+                       delta, (ET*)dk, (ET*)dv, B, H, Hkv, S, qs, ks, vs, dos, dks, dvs, scale,   \
+                       dr, doc_end, sumk, sumv, sum_ld);                                          \
   } while (0)
+#define SMDT_FA_BWD_T(DD, CC, DR, ET) \
+  do { if (colpart) SMDT_FA_BWD_K(DD, CC, DR, ET, false, true); else SMDT_FA_BWD_K(DD, CC, DR, ET, false, false); } while (0)
 #define SMDT_FA_BWD(DD, CC, DR) \
   do { if (dtype == 2) SMDT_FA_BWD_T(DD, CC, DR, f16); else SMDT_FA_BWD_T(DD, CC, DR, bf16); } while (0)
 #define SMDT_FA_BWD2(DD, CC) \
   do { if (drop) SMDT_FA_BWD(DD, CC, true); else SMDT_FA_BWD(DD, CC, false); } while (0)
-#define SMDT_FA_BWD_DOC_T(DD, DR, ET)                                                            \
-  do {                                                                                           \
-    hipLaunchKernelGGL((bwd_dq_kernel<DD, true, DR, ET, true>), gq, dim3(256), 0, st,            \
-                       (const ET*)q, (const ET*)k, (const ET*)v, (const ET*)dout, (const ET*)o,   \
-                       lse, delta, (ET*)rc3, (ET*)dq, B, H, Hkv, S, qs, ks, vs, dos, os, dqs,     \
-                       scale, dscale, lsub, dr, doc_start);                                       \
-    hipLaunchKernelGGL((bwd_dkdv_kernel<DD, true, DR, ET, true>), gkv, dim3(256), 0, st,         \
-                       (const ET*)q, (const ET*)k, (const ET*)v, (const ET*)dout, (const ET*)rc3, \
-                       delta, (ET*)dk, (ET*)dv, B, H, Hkv, S, qs, ks, vs, dos, dks, dvs, scale,   \
-                       dr, doc_end);                                                              \
-  } while (0)
+#define SMDT_FA_BWD_DOC_T(DD, DR, ET) \
+  do { if (colpart) SMDT_FA_BWD_K(DD, true, DR, ET, true, true); else SMDT_FA_BWD_K(DD, true, DR, ET, true, false); } while (0)
 #define SMDT_FA_BWD_DOC(DD, DR) \
   do { if (dtype == 2) SMDT_FA_BWD_DOC_T(DD, DR, f16); else SMDT_FA_BWD_DOC_T(DD, DR, bf16); } while (0)
   if (doc_start) {
@@ -1315,6 +1389,7 @@ static hipError_t flash_bwd_impl(int dtype, const void* q, const void* k, const 
 #undef SMDT_FA_BWD2
 #undef SMDT_FA_BWD
 #undef SMDT_FA_BWD_T
+#undef SMDT_FA_BWD_K
   return hipGetLastError();
 }
 
@@ -1325,7 +1400,7 @@ extern "C" hipError_t smdt_flash_bwd(int dtype, const void* q, const void* k, co
                                      int causal, float dropout_p, uint64_t seed, uint64_t offset,
                                      hipStream_t st) {
   return flash_bwd_impl(dtype, q, k, v, o, dout, lse, delta, dq, dk, dv, B, H, Hkv, S, D, strides, scale,
-                        causal, dropout_p, seed, offset, nullptr, nullptr, st);
+                        causal, dropout_p, seed, offset, nullptr, nullptr, nullptr, st);
 }
 
 extern "C" hipError_t smdt_flash_bwd_doc(int dtype, const void* q, const void* k, const void* v,
@@ -1336,5 +1411,19 @@ extern "C" hipError_t smdt_flash_bwd_doc(int dtype, const void* q, const void* k
                                          const int* doc_start, const int* doc_end, hipStream_t st) {
   if (!doc_start || !doc_end) return hipErrorInvalidValue;
   return flash_bwd_impl(dtype, q, k, v, o, dout, lse, delta, dq, dk, dv, B, H, Hkv, S, D, strides, scale, 1,
-                        dropout_p, seed, offset, doc_start, doc_end, st);
+                        dropout_p, seed, offset, doc_start, doc_end, nullptr, st);
+}
+
+// The backward with the token sums of dQ | dK | dV (see flash_bwd_impl): doc_start / doc_end may
+// both be null (plain attention).
+extern "C" hipError_t smdt_flash_bwd_sums(int dtype, const void* q, const void* k, const void* v,
+                                          const void* o, const void* dout, const float* lse,
+                                          float* delta, void* dq, void* dk, void* dv, int B, int H,
+                                          int Hkv, int S, int D, const int64_t* strides, float scale,
+                                          int causal, float dropout_p, uint64_t seed, uint64_t offset,
+                                          const int* doc_start, const int* doc_end, float* colpart,
+                                          hipStream_t st) {
+  if (!colpart) return hipErrorInvalidValue;
+  return flash_bwd_impl(dtype, q, k, v, o, dout, lse, delta, dq, dk, dv, B, H, Hkv, S, D, strides, scale,
+                        causal, dropout_p, seed, offset, doc_start, doc_end, colpart, st);
 }

@@ -6,7 +6,11 @@
 //   EPI_BIAS       C = acc + bias[n]
 //   EPI_BIAS_GELU  C = acc (the pre-activation the backward needs) and C2 = gelu_tanh(C + bias[n])
 //   EPI_DGELU      C = acc * gelu_tanh'(pre[m, n] + bias[n]): the fc2 dgrad with the GeLU backward
-//                  of the fc1 activation in its epilogue
+//                  of the fc1 activation in its epilogue. Its SUMS form also emits the column sums
+//                  of C, the fc1 bias gradient: every wave adds the fp32 values it is about to pack
+//                  into running sums of the 8 columns its lanes own, and ends its 128 x 64 tile
+//                  with one row of the fp32 partials [M / 128, N] (smdt_col_sum adds the rows in a
+//                  fixed order), so the grouped wgrad needs no bias tiles for fc1
 // The last two are Megatron's bias_gelu fusion (/root/reference/3_training_megatron-lm/megatron/
 // arguments.py:819-821, bias_gelu_fusion=True in 3_training_megatron-lm.ipynb) moved into the fc1
 // and fc2-dgrad GEMMs: the separate bias_act_fwd / bias_act_bwd passes over the [tokens, 4h]
@@ -122,6 +126,7 @@ struct Args {
   void* C2;
   const void* bias;
   const void* aux;   // EPI_DGELU: the GeLU pre-activation [M, N] (without the bias)
+  float* colpart;    // SUMS: fp32 [M / 128, N] column sums of C per 128-row half tile
   int M, N, K;
   int ntn;      // N / 256
   int ntm;      // M / 256
@@ -208,8 +213,10 @@ __device__ __forceinline__ uint32_t lds_addr(const void* p) {
 // bit 4 no bias / activation math in the epilogue (loads and stores stay), bit 5 sc1
 // (L2-bypassing) output stores instead of plain ones, bit 9 EPI_DGELU without the loads of the
 // pre-activation; (host) bit 7 / 8 tile groups of 1 / 4 row blocks instead of 8.
-template <class E, int EPI, int VAR = 0>
+// SUMS (EPI_DGELU only): also write the column sums of the output, see the header.
+template <class E, int EPI, int VAR = 0, bool SUMS = false>
 __global__ __launch_bounds__(kThreads, 1) void gemm_tn_kernel(const Args g) {
+  static_assert(!SUMS || (EPI == EPI_DGELU && VAR == 0), "column sums come with the GeLU-backward epilogue");
   using V = typename V8<E>::t;
   // [A slot 0 | A slot 1 | B slot 0 | B slot 1] 32 KB each, then 4 KB of epilogue staging per
   // wave (160 KB: the whole LDS)
@@ -315,9 +322,11 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_tn_kernel(const Args g) {
 
   int otile = rb;
   constexpr int NOUT = EPI == EPI_BIAS_GELU ? 2 : 1;
-  constexpr int kStores = 16 * NOUT;   // 16-byte stores per wave of one epilogue
+  constexpr int kStores = 16 * NOUT + (SUMS ? 1 : 0);   // stores per wave of one epilogue
   f32x2 bias2[4];                      // 8 bias values of this lane's 16-byte column chunk
   (void)bias2;
+  f32x2 csum[4];                       // SUMS: this lane's 8 columns summed over its 16 rows of the tile
+  (void)csum;
   const uint32_t epi_l = l0 + kNSlot * kSlot + wave * kEpiB;
 
   auto sync = [&]() {
@@ -412,7 +421,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_tn_kernel(const Args g) {
   // bias / activation on 8 consecutive values of one row (chunk rc), o = 0 the first output.
   // The fp32 math runs on pairs (v_pk_*_f32: two elements per issue slot; activations.h), against
   // the tile's bias unpacked once (bias2).
-  auto finish8 = [&](u32x4 v, int o, u32x4 pv) -> u32x4 {
+  auto finish8 = [&](u32x4 v, int o, u32x4 pv, bool first_row) -> u32x4 {
     if constexpr (EPI == EPI_NONE) {
       return v;
     } else {
@@ -433,6 +442,10 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_tn_kernel(const Args g) {
         unpack4<E>(u32x2{pv[2], pv[3]}, *reinterpret_cast<float(*)[4]>(zf + 4));
 #pragma unroll
         for (int e = 0; e < 4; ++e) x[e] = x[e] * gelu_tanh_grad(f32x2{zf[2 * e], zf[2 * e + 1]} + bias2[e]);
+        if constexpr (SUMS) {   // the fp32 values, before the 16-bit rounding below
+#pragma unroll
+          for (int e = 0; e < 4; ++e) csum[e] = first_row ? x[e] : csum[e] + x[e];
+        }
       } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e) x[e] = EPI == EPI_BIAS ? x[e] + bias2[e] : gelu_tanh(x[e] + bias2[e]);
@@ -496,11 +509,33 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_tn_kernel(const Args g) {
         for (int o = 0; o < NOUT; ++o) {
           E* dst = (E*)(o == 0 ? g.C : g.C2) + off + (int64_t)(8 * h) * N;
           // (VAR bit 9, no aux load: the product stands in for the pre-activation, the math stays)
-          const u32x4 w = finish8(rv[h], o + (EPI == EPI_BIAS ? 1 : 0), (VAR & 512) ? rv[h] : pre_v[k][h]);
+          const u32x4 w = finish8(rv[h], o + (EPI == EPI_BIAS ? 1 : 0), (VAR & 512) ? rv[h] : pre_v[k][h],
+                                  k == 0 && h == 0);
           if constexpr ((VAR & 8) != 0) asm volatile("" ::"v"(w));
           else if constexpr ((VAR & 32) != 0) store16_sc1(dst, w);
           else *(u32x4*)dst = w;
         }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if constexpr (SUMS) {
+      // Lane (rr, rc) holds columns 8 rc .. 8 rc + 7 summed over rows rr, rr + 8, ... of the wave's
+      // 128: the 64 lanes' 32 bytes go through the first half of the wave's staging area (its
+      // reads are done; the wave's LDS operations retire in order), and lane c adds the 8 row
+      // groups of column c in a fixed order and stores its word of the partials row.
+      const int ln = lane_now();
+      const uint32_t mine = epi_l + (uint32_t)ln * 32;
+      *(__attribute__((address_space(3))) f32x4*)(uintptr_t)mine = f32x4{csum[0][0], csum[0][1], csum[1][0], csum[1][1]};
+      *(__attribute__((address_space(3))) f32x4*)(uintptr_t)(mine + 16) = f32x4{csum[2][0], csum[2][1], csum[3][0], csum[3][1]};
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      const uint32_t col = epi_l + (uint32_t)(ln >> 3) * 32 + (uint32_t)(ln & 7) * 4;   // lane (0, c / 8), word c % 8
+      float s = 0.f;
+#pragma unroll
+      for (int r = 0; r < 8; ++r) s += *(__attribute__((address_space(3))) const float*)(uintptr_t)(col + r * 256);
+      g.colpart[(int64_t)(2 * otm + wr) * N + otn * kT + 64 * wc + ln] = s;
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // before the next tile's pieces land here
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -539,6 +574,10 @@ extern "C" int smdt_gemm_tn_supported(int64_t M, int64_t N, int64_t K) {
          M * K < (1ll << 31) && N * K < (1ll << 31) && (M / gt::kT) * (N / gt::kT) < (1ll << 30);
 }
 
+static hipError_t gemm_tn_launch(int dtype, int epi, const void* a, const void* b, void* c, void* c2,
+                                 const void* bias, const void* aux, float* colpart, int64_t M, int64_t N,
+                                 int64_t K, int max_blocks, int var, hipStream_t st);
+
 static int gt_num_cus() {
   static int n = [] {
     int dev = 0, v = 0;
@@ -547,6 +586,14 @@ static int gt_num_cus() {
     return v;
   }();
   return n;
+}
+
+// EPI_DGELU with the column sums of c: colpart is fp32 [M / 128, N], every word of it is written.
+extern "C" hipError_t smdt_gemm_tn_dgelu_sums(int dtype, const void* a, const void* b, void* c, const void* bias,
+                                              const void* aux, float* colpart, int64_t M, int64_t N, int64_t K,
+                                              int max_blocks, hipStream_t st) {
+  if (!colpart) return hipErrorInvalidValue;
+  return gemm_tn_launch(dtype, gt::EPI_DGELU, a, b, c, nullptr, bias, aux, colpart, M, N, K, max_blocks, 0, st);
 }
 
 extern "C" hipError_t smdt_gemm_tn(int dtype, int epi, const void* a, const void* b, void* c, void* c2,
@@ -558,11 +605,17 @@ extern "C" hipError_t smdt_gemm_tn(int dtype, int epi, const void* a, const void
 extern "C" hipError_t smdt_gemm_tn_var(int dtype, int epi, const void* a, const void* b, void* c, void* c2,
                                        const void* bias, const void* aux, int64_t M, int64_t N, int64_t K,
                                        int max_blocks, int var, hipStream_t st) {
+  return gemm_tn_launch(dtype, epi, a, b, c, c2, bias, aux, nullptr, M, N, K, max_blocks, var, st);
+}
+
+static hipError_t gemm_tn_launch(int dtype, int epi, const void* a, const void* b, void* c, void* c2,
+                                 const void* bias, const void* aux, float* colpart, int64_t M, int64_t N,
+                                 int64_t K, int max_blocks, int var, hipStream_t st) {
   if (dtype != 1 && dtype != 2) return hipErrorInvalidValue;
   if (!smdt_gemm_tn_supported(M, N, K)) return hipErrorInvalidValue;
   if (epi < 0 || epi > 3 || (epi >= 1 && !bias) || (epi == 2 && !c2) || (epi == 3 && !aux)) return hipErrorInvalidValue;
   gt::Args g;
-  g.A = a; g.B = b; g.C = c; g.C2 = c2; g.bias = bias; g.aux = aux;
+  g.A = a; g.B = b; g.C = c; g.C2 = c2; g.bias = bias; g.aux = aux; g.colpart = colpart;
   g.M = (int)M; g.N = (int)N; g.K = (int)K;
   g.ntn = (int)(N / gt::kT);
   g.ntm = (int)(M / gt::kT);
@@ -622,6 +675,11 @@ extern "C" hipError_t smdt_gemm_tn_var(int dtype, int epi, const void* a, const 
     return hipGetLastError();
   }
 #undef SMDT_GTV
+  if (colpart) {
+    if (dtype == 1) hipLaunchKernelGGL((gt::gemm_tn_kernel<bf16, gt::EPI_DGELU, 0, true>), dim3(grid), dim3(gt::kThreads), 0, st, g);
+    else hipLaunchKernelGGL((gt::gemm_tn_kernel<f16, gt::EPI_DGELU, 0, true>), dim3(grid), dim3(gt::kThreads), 0, st, g);
+    return hipGetLastError();
+  }
   if (dtype == 1) {
     if (epi == 0) SMDT_GT(bf16, 0); else if (epi == 1) SMDT_GT(bf16, 1); else if (epi == 2) SMDT_GT(bf16, 2); else SMDT_GT(bf16, 3);
   } else {

@@ -129,6 +129,14 @@ hipError_t smdt_flash_bwd_doc(int dtype, const void* q, const void* k, const voi
                               void* dv, int B, int H, int Hkv, int S, int D, const int64_t* strides,
                               float scale, float dropout_p, uint64_t seed, uint64_t offset,
                               const int* doc_start, const int* doc_end, hipStream_t st);
+// the backward (plain, or per-document with doc_start / doc_end) that also writes colpart, fp32
+// [B * S / 128, (H + 2 Hkv) D]: per 128-token block the sums over its tokens of the fp32 dQ | dK |
+// dV before their 16-bit rounding, in a fused QKV output's column order (smdt_col_sum adds the rows)
+hipError_t smdt_flash_bwd_sums(int dtype, const void* q, const void* k, const void* v, const void* o,
+                               const void* dout, const float* lse, float* delta, void* dq, void* dk,
+                               void* dv, int B, int H, int Hkv, int S, int D, const int64_t* strides,
+                               float scale, int causal, float dropout_p, uint64_t seed, uint64_t offset,
+                               const int* doc_start, const int* doc_end, float* colpart, hipStream_t st);
 
 // gemm_tn.hip: C[M, N] = A[M, K] . B[N, K]^T (16-bit in / out, fp32 accumulate) with an epilogue:
 // epi 0 none, 1 + bias[n], 2 C = pre-activation and C2 = gelu_tanh(C + bias[n]) (bias_gelu fusion),
@@ -142,6 +150,11 @@ hipError_t smdt_gemm_tn(int dtype, int epi, const void* a, const void* b, void* 
 hipError_t smdt_gemm_tn_var(int dtype, int epi, const void* a, const void* b, void* c, void* c2, const void* bias,
                             const void* aux, int64_t M, int64_t N, int64_t K, int max_blocks, int var,
                             hipStream_t st);
+// epi 3 that also writes colpart, fp32 [M / 128, N]: per 128-row half tile the column sums of the
+// fp32 output values before their 16-bit rounding (smdt_col_sum adds the rows: the fc1 bias gradient)
+hipError_t smdt_gemm_tn_dgelu_sums(int dtype, const void* a, const void* b, void* c, const void* bias,
+                                   const void* aux, float* colpart, int64_t M, int64_t N, int64_t K,
+                                   int max_blocks, hipStream_t st);
 
 // wgrad_gemm.hip: main_grad[N, K] (fp32) += dy[M, N]^T . x[M, K] (bf16, or fp16 with dtype 2)
 int smdt_wgrad_supported(int64_t M, int64_t N, int64_t K);

@@ -104,7 +104,9 @@ struct Glds {
 // branch around an MFMA per fragment (bias tiles ~2.5x slower: 37.0 -> 43.8 ms); the re-read
 // fragment times an all-ones B operand (one extra MFMA per 8), or the re-read fragment summed by
 // VALU, both cost ~2.7 ms (39.7 / 40.4 ms): the tiles of a launch run in rounds of 256, so a slower
-// k = 0 tile in every round stretches every round.
+// k = 0 tile in every round stretches every round. For that reason the flagship step no longer
+// passes a bias here: the QKV and fc1 sums come from the kernels that write those dY (flash_attn.hip
+// and gemm_tn.hip SUMS, profiles/bias_from_producer/); FP8, TP / SP and unfused paths still do.
 // Sum of the 8 16-bit values of an operand fragment, in fp32.
 template <class V>
 __device__ __forceinline__ float sum8(V x) {

@@ -422,7 +422,31 @@ class ParallelAttention(nn.Module):
                                 dropout_p=p, rng=get_rng("tp"))
         return ctx.reshape(ctx.shape[0], ctx.shape[1], self.nh * self.hd)
 
+    def _qkv_bias_from_attention(self, x):
+        """The QKV bias Parameter if the flash attention backward is to make its gradient
+        (``tp.bias_from_producer``), else None. Strict: d(qkv) of the linear must BE what the
+        backward kernels write, so only the in-place fused-QKV flash path with nothing between the
+        linear and attention (no RoPE, no padding-free repacking, no context parallelism, a plain
+        16-bit linear) and a shape the kernels take as it is."""
+        lin = self.qkv
+        if (_PACK["idx"] is not None or self.rope is not None or not self.cfg.use_flash_attn
+                or ps.get_state().cp != 1 or lin._fp8 is not None or lin.sequence_parallel or lin.gather_output
+                or lin.skip_bias_add or not torch.is_grad_enabled() or x.dim() != 3
+                or lin.bias is None or lin.weight.dtype != x.dtype or lin.bias.dtype != x.dtype):
+            return None
+        W = (self.nh + 2 * self.nkv) * self.hd
+        if self.hd not in (64, 128) or x.shape[0] % 128 or W % 8 or self.nh % self.nkv or lin.out_local != W:
+            return None
+        return lin.bias if tp.bias_from_producer(lin.bias, x) else None
+
     def forward(self, x, training=True, doc_start=None):
+        qkv_bias = self._qkv_bias_from_attention(x)
+        if qkv_bias is not None:
+            qkv = self.qkv(x, bias_grad=False)
+            p = self.cfg.attention_dropout if training else 0.0
+            return self.proj(SF.flash_attention_qkv(qkv, self.nh, self.nkv, self.hd, seq_first=True, causal=True,
+                                                    dropout_p=p, rng=get_rng("tp"), doc_start=doc_start,
+                                                    bias_p=qkv_bias))
         qkv = self.qkv(x)                                        # [s, b, (nh + 2 nkv) d]
         if _PACK["idx"] is not None:                              # padding-free micro-batch
             if doc_start is not None:

@@ -369,9 +369,15 @@ def _doc_check(doc_start, B, S, causal):
 
 
 class _FlashAttnQKV(torch.autograd.Function):
+    """``bias_p`` (the bias Parameter of the QKV projection whose output ``qkv`` is, or None): the
+    backward kernels also emit the token sums of the fp32 dQ | dK | dV (flash_attn.hip SUMS), and
+    their fixed-order reduction goes straight into the bias' fp32 ``main_grad`` — the projection
+    then queues its weight gradient without bias tiles (tensor_parallel.bias_from_producer)."""
+
     @staticmethod
     def forward(ctx, qkv, nh, nkv, hd, seq_first, scale, causal, dropout_p=0.0, seed=0, offset=0,
-                doc_start=None, doc_end=None):
+                doc_start=None, doc_end=None, bias_p=None):
+        ctx.bias_p = bias_p
         C = _ext.ext()
         q, k, v = _qkv_views(qkv, nh, nkv, hd, seq_first)
         if seq_first:
@@ -401,8 +407,18 @@ class _FlashAttnQKV(torch.autograd.Function):
         if seq_first:
             do = do.transpose(0, 1)
             o = o.transpose(0, 1)
-        C.flash_bwd(q, k, v, o, do, lse, scale, causal, dq, dk, dv, dropout_p, seed, offset, *ctx.doc)
-        return dqkv, None, None, None, None, None, None, None, None, None, None, None
+        bias_p = ctx.bias_p
+        if bias_p is None:
+            C.flash_bwd(q, k, v, o, do, lse, scale, causal, dq, dk, dv, dropout_p, seed, offset, *ctx.doc)
+        else:
+            tgt = grad_accumulate_target(bias_p)
+            if tgt is None or tgt.numel() != qkv.shape[-1]:
+                raise RuntimeError("flash attention: the QKV bias gradient was left to the attention backward but "
+                                   "the bias has no fp32 main_grad to receive it")
+            C.flash_bwd_dbias(q, k, v, o, do, lse, scale, causal, tgt, True, dq, dk, dv, dropout_p, seed, offset,
+                              *ctx.doc)
+            bias_p._smdt_grad_ready(bias_p)
+        return dqkv, None, None, None, None, None, None, None, None, None, None, None, None
 
 
 class _FlashAttn(torch.autograd.Function):
@@ -617,7 +633,7 @@ def flash_attention(q, k, v, scale: Optional[float] = None, causal: bool = True,
 
 def flash_attention_qkv(qkv, nh: int, nkv: int, hd: int, seq_first: bool = True, causal: bool = True,
                         scale: Optional[float] = None, dropout_p: float = 0.0, rng: Optional[PhiloxState] = None,
-                        doc_start=None):
+                        doc_start=None, bias_p=None):
     """Attention straight off a fused QKV projection output.
 
     ``qkv`` is [S, B, (nh + 2 nkv) hd] (``seq_first``) or [B, S, ...]; returns [S, B, nh hd]
@@ -626,19 +642,25 @@ def flash_attention_qkv(qkv, nh: int, nkv: int, hd: int, seq_first: bool = True,
     (seed, offset) in backward — nothing is stored). Shapes the kernels cannot read in place
     (S % 128 != 0, head dim not 64 / 128) go through the padded separate-q/k/v path.
     ``doc_start`` (int32 [B, S], batch-first whatever ``seq_first``): per-document attention, see
-    ``flash_attention``.
+    ``flash_attention``. ``bias_p``: see ``_FlashAttnQKV``; the caller has left the QKV bias
+    gradient to this call, so a shape that misses the in-place kernels is an error.
     """
     if scale is None:
         scale = 1.0 / math.sqrt(hd)
     q, k, v = _qkv_views(qkv, nh, nkv, hd, seq_first)
     if doc_start is not None:
         _doc_check(doc_start, q.shape[0], q.shape[1], causal)
+    fused = (_ext.use_kernels(qkv) and qkv.is_contiguous() and flash_supported(q, k)
+             and (nh + 2 * nkv) * hd % 8 == 0)
+    if bias_p is not None and not fused:
+        raise RuntimeError("flash_attention_qkv: the QKV bias gradient was left to the attention backward, but "
+                           "this call does not run the in-place flash kernels")
     if _ext.use_kernels(qkv):
-        if qkv.is_contiguous() and flash_supported(q, k) and (nh + 2 * nkv) * hd % 8 == 0:
+        if fused:
             seed, off = _rng(rng).next() if dropout_p > 0 else (0, 0)
             ds, de = _doc_args(doc_start, q.shape[1], q.shape[1])
             return _FlashAttnQKV.apply(qkv, nh, nkv, hd, bool(seq_first), float(scale), bool(causal),
-                                       float(dropout_p), int(seed), int(off), ds, de)
+                                       float(dropout_p), int(seed), int(off), ds, de, bias_p)
         o = flash_attention(q, k, v, scale, causal, dropout_p, rng, doc_start)          # [B, S, H, D]
     else:
         seed, off = _rng(rng).next() if dropout_p > 0 else (0, 0)

@@ -793,8 +793,37 @@ def _wgrad(weight, g2, t2):
 
 # The bias gradient of a column-parallel linear (the column sums of dY) comes out of the grouped
 # wgrad launch that reads dY anyway (csrc/kernels/wgrad_gemm.hip ``bias``) instead of a separate
-# pass over dY; SMDT_WGRAD_BIAS=0 keeps the separate column-sum kernel.
+# pass over dY; SMDT_WGRAD_BIAS=0 keeps the separate column-sum kernel. Where dY is written by a
+# kernel of ours with nothing in between, that kernel makes the sums instead (below) and the
+# linear queues its weight gradient without a bias: the wgrad's bias tiles are the slow tile of
+# every round of 256 (profiles/bias_from_producer/).
 _WGRAD_BIAS = os.environ.get("SMDT_WGRAD_BIAS", "1") == "1"
+
+# The QKV and fc1 bias gradients from the kernels that PRODUCE those linears' dY: the flash
+# attention backward (flash_attn.hip SUMS: token sums of the fp32 dQ | dK | dV) and the fc2 dgrad's
+# GeLU-backward epilogue (gemm_tn.hip SUMS), each followed by the fixed-order column-sum kernel
+# straight into the bias' fp32 main_grad. SMDT_BIAS_FROM_PRODUCER=0 restores the wgrad bias tiles.
+_BIAS_FROM_PRODUCER = os.environ.get("SMDT_BIAS_FROM_PRODUCER", "1") == "1"
+
+
+def bias_from_producer(bias_p, like) -> bool:
+    """Whether the kernel that writes a linear's dY (16-bit ``like``-typed, on its device) may
+    also make the linear's bias gradient: TP = 1 without sequence parallelism, a bias with a plain
+    fp32 ``main_grad`` and a readiness callback (not the lazily zeroed ZeRO-2 slices, whose first
+    write is a store the wgrad queue owns), and no accumulation window / sub-batch merge / split
+    backward of the wgrad queue (those report a parameter's readiness once per window). The caller
+    checks that its producer kernel really runs."""
+    if not _BIAS_FROM_PRODUCER or bias_p is None or not like.is_cuda or not _ext.use_kernels(like):
+        return False
+    if like.dtype not in (torch.bfloat16, torch.float16):
+        return False
+    if _tp_size() != 1 or isinstance(getattr(type(bias_p), "main_grad", None), property):
+        return False
+    q = DEFERRED_WGRAD
+    if q.hold or q.merge_repeats or q.defer:
+        return False
+    tgt = SF.grad_accumulate_target(bias_p)
+    return tgt is not None and tgt.device == like.device and tgt.numel() == bias_p.numel()
 
 
 def _wgrad_and_bias(weight, bias_p, g2, t2):
@@ -982,10 +1011,12 @@ class LinearWithGradAccumulationAndAsyncCommunication(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, x, weight, bias, sequence_parallel, async_grad_allreduce, add_bias=True):
+    def forward(ctx, x, weight, bias, sequence_parallel, async_grad_allreduce, add_bias=True, bias_grad=True):
         ctx.sp = sequence_parallel
         ctx.async_ar = async_grad_allreduce
-        ctx.has_bias = bias is not None
+        # bias_grad False: the consumer of this linear's output makes the bias gradient
+        # (``bias_from_producer``); the backward then produces the weight gradient alone
+        ctx.has_bias = bias is not None and bias_grad
         ctx.bias_p = bias
         ctx.save_for_backward(x, weight)
         total = _gather_dim0(x, _tp_group()) if sequence_parallel else x
@@ -997,7 +1028,7 @@ class LinearWithGradAccumulationAndAsyncCommunication(torch.autograd.Function):
     def backward(ctx, g):
         x, weight = ctx.saved_tensors
         gi_out, dw, db = _linear_backward(ctx, g, x, weight)
-        return gi_out, dw, db, None, None, None
+        return gi_out, dw, db, None, None, None, None
 
 
 def _linear_backward(ctx, g, x, weight):
@@ -1303,14 +1334,22 @@ class FusedGeLUMLP(torch.autograd.Function):
         b1 = ctx.b1
         dy2 = dy.reshape(-1, dy.shape[-1]).contiguous()
         w2t = _dgrad_weight_t(w2)
+        b1_grad = b1      # who still owes fc1's bias gradient: the wgrad launch, unless the epilogue makes it
         if w2t is not None and C.gemm_tn_supported(dy2, w2t):
-            dz = C.gemm_tn(dy2, w2t, 3, b1.detach(), None, None, 0, 0, pre)[0]
+            if bias_from_producer(b1, dy2):
+                # d(pre) and its column sums (fc1's bias gradient, straight into main_grad) from
+                # the one epilogue; fc1's weight gradient is then queued without bias tiles
+                dz = C.gemm_tn_dgelu_dbias(dy2, w2t, b1.detach(), pre, SF.grad_accumulate_target(b1), True)
+                b1._smdt_grad_ready(b1)
+                b1_grad = None
+            else:
+                dz = C.gemm_tn(dy2, w2t, 3, b1.detach(), None, None, 0, 0, pre)[0]
         else:
             dz = C.bias_act_bwd(dgrad(dy2, w2, w2t).contiguous(), pre, b1.detach(), 0, False, None)[0]
         dw2, _ = _wgrad_and_bias(w2, None, dy2, act)
         x2 = x.reshape(-1, x.shape[-1])
         dx = dgrad(dz, w1, _dgrad_weight_t(w1))
-        dw1, db1 = _wgrad_and_bias(w1, b1, dz, x2)
+        dw1, db1 = _wgrad_and_bias(w1, b1_grad, dz, x2)
         return dx.view(x.shape), dw1, db1, dw2
 
 
@@ -1643,13 +1682,17 @@ _LM_HEAD_CE = os.environ.get("SMDT_LM_HEAD_CE", "1") == "1"
 
 
 def linear_with_grad_accumulation_and_async_allreduce(x, weight, bias, sequence_parallel=False,
-                                                      async_grad_allreduce=False, add_bias=True, fp8=None):
+                                                      async_grad_allreduce=False, add_bias=True, fp8=None,
+                                                      bias_grad=True):
+    if not bias_grad and (fp8 is not None or sequence_parallel):
+        raise RuntimeError("bias_grad=False (the bias gradient from the consumer's kernel) is for the plain "
+                           "16-bit linear at TP = 1")
     if fp8 is not None:                 # (FP8State, first table row) from attach_fp8; TP = 1
         return FP8Linear.apply(x, weight, bias, add_bias, fp8[0], fp8[1])
     if sequence_parallel and _TP_OVERLAP and _tp_size() > 1:
         return _ColumnSPLinear.apply(x, weight, bias, add_bias)
     return LinearWithGradAccumulationAndAsyncCommunication.apply(x, weight, bias, sequence_parallel,
-                                                                 async_grad_allreduce, add_bias)
+                                                                 async_grad_allreduce, add_bias, bias_grad)
 
 
 # --------------------------------------------------------------------------------------------
@@ -2478,10 +2521,16 @@ class ColumnParallelLinear(nn.Module):
         else:
             self.register_parameter("bias", None)
 
-    def forward(self, x):
+    def forward(self, x, bias_grad=True):
+        """``bias_grad`` False: the caller's next kernel makes this linear's bias gradient
+        (``bias_from_producer``), the backward here makes the weight gradient alone."""
         if not (self.async_ar or self.sequence_parallel):
             x = copy_to_tensor_model_parallel_region(x)
-        if self.bias_grad_from_output:
+        if not bias_grad:       # only the plain linear that adds its bias (the fused-QKV projection)
+            assert not self.bias_grad_from_output and not self.skip_bias_add
+            y = linear_with_grad_accumulation_and_async_allreduce(x, self.weight, self.bias, self.sequence_parallel,
+                                                                  self.async_ar, fp8=self._fp8, bias_grad=False)
+        elif self.bias_grad_from_output:
             y = linear_with_grad_accumulation_and_async_allreduce(x, self.weight, self.bias, self.sequence_parallel,
                                                                   self.async_ar, add_bias=False, fp8=self._fp8)
         else:
