@@ -605,6 +605,48 @@ bool wgrad_grouped(std::vector<Tensor> main_grads, std::vector<Tensor> dys, std:
   return true;
 }
 
+// FP8 form (wgrad_fp8.hip): main_grads[i] (+)= (inv_dys[i] * inv_xs[i]) * dys[i]^T . xs[i] with
+// dys in float8_e5m2 or float8_e4m3fn (one format per call) and xs in float8_e4m3fn. inv_dys /
+// inv_xs are one-element fp32 device tensors the kernel reads (no host sync). Returns false (and
+// does nothing) when any problem is unsupported. The targets must not overlap.
+bool wgrad_fp8_grouped(std::vector<Tensor> main_grads, std::vector<Tensor> dys, std::vector<Tensor> xs,
+                       std::vector<Tensor> inv_dys, std::vector<Tensor> inv_xs, std::vector<bool> overwrite,
+                       int64_t cus) {
+  const size_t n = main_grads.size();
+  TORCH_CHECK(dys.size() == n && xs.size() == n && inv_dys.size() == n && inv_xs.size() == n,
+              "wgrad_fp8_grouped: list lengths differ");
+  TORCH_CHECK(overwrite.empty() || overwrite.size() == n, "wgrad_fp8_grouped: overwrite list length");
+  std::vector<SmdtWgradFp8Problem> probs(n);
+  for (size_t i = 0; i < n; ++i) {
+    const Tensor &mg = main_grads[i], &dy = dys[i], &x = xs[i], &idy = inv_dys[i], &ix = inv_xs[i];
+    if (!mg.is_cuda() || mg.scalar_type() != at::kFloat || !mg.is_contiguous()) return false;
+    if (dy.dim() != 2 || x.dim() != 2 || !dy.is_contiguous() || !x.is_contiguous()) return false;
+    if ((dy.scalar_type() != at::kFloat8_e5m2 && dy.scalar_type() != at::kFloat8_e4m3fn) ||
+        x.scalar_type() != at::kFloat8_e4m3fn || dy.scalar_type() != dys[0].scalar_type())
+      return false;
+    if (dy.get_device() != mg.get_device() || x.get_device() != mg.get_device()) return false;
+    for (const Tensor* t : {&idy, &ix})
+      TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->numel() == 1 &&
+                      t->get_device() == mg.get_device(),
+                  "wgrad_fp8_grouped: a dequantisation factor must be one fp32 value on the target's device");
+    const int64_t M = dy.size(0), N = dy.size(1), K = x.size(1);
+    if (x.size(0) != M || mg.numel() != N * K || !smdt_wgrad_fp8_supported(M, N, K)) return false;
+    for (size_t j = 0; j < i; ++j) {    // overlapping targets would race
+      const char *a0 = (const char*)mg.data_ptr(), *b0 = (const char*)main_grads[j].data_ptr();
+      if (a0 < b0 + main_grads[j].numel() * 4 && b0 < a0 + mg.numel() * 4) return false;
+    }
+    probs[i] = SmdtWgradFp8Problem{dy.data_ptr(), x.data_ptr(), mg.data_ptr<float>(), M, N, K,
+                                   idy.data_ptr<float>(), ix.data_ptr<float>(),
+                                   dy.scalar_type() == at::kFloat8_e5m2 ? 1 : 0,
+                                   (!overwrite.empty() && overwrite[i]) ? 1 : 0};
+  }
+  if (n == 0) return true;
+  check(smdt_wgrad_fp8_grouped_cus(probs.data(), (int)n, (int)cus, cur_stream()), "wgrad_fp8_grouped");
+  return true;
+}
+
+bool wgrad_fp8_supported(int64_t M, int64_t N, int64_t K) { return smdt_wgrad_fp8_supported(M, N, K) != 0; }
+
 // ------------------------------------------------------------------ bias gradient
 // out[N] (fp32) = / += column sums of dy [.., N]
 void bias_grad(Tensor dy, Tensor out, bool accumulate) {
@@ -1054,6 +1096,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("wgrad_mfma", &wgrad_mfma, arg("main_grad"), arg("dy"), arg("x"), arg("max_splits") = 0);
   m.def("wgrad_grouped", &wgrad_grouped, arg("main_grads"), arg("dys"), arg("xs"),
         arg("biases") = std::vector<Tensor>{}, arg("overwrite") = std::vector<bool>{}, arg("cus") = 0);
+  m.def("wgrad_fp8_grouped", &wgrad_fp8_grouped, arg("main_grads"), arg("dys"), arg("xs"), arg("inv_dys"),
+        arg("inv_xs"), arg("overwrite") = std::vector<bool>{}, arg("cus") = 0);
+  m.def("wgrad_fp8_supported", &wgrad_fp8_supported);
   m.def("ce_stats", &ce_stats);
   m.def("set_rng_step", &set_rng_step);
   m.def("adam_capturable", &adam_capturable);

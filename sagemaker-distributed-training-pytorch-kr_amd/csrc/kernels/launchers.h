@@ -177,6 +177,23 @@ hipError_t smdt_wgrad_grouped_t(int dtype, const SmdtWgradProblem* probs, int n,
 // the same with the tail split sized for `cus` concurrently usable CUs (0: 256, the whole chip)
 hipError_t smdt_wgrad_grouped_cus(int dtype, const SmdtWgradProblem* probs, int n, int cus, hipStream_t st);
 
+// wgrad_fp8.hip: main_grad[N, K] (fp32) (+)= (*inv_dy * *inv_x) * dy[M, N]^T . x[M, K] on FP8 bytes
+// (the OCP encodings fp8_quant.hip writes). M % 64 == 0, N and K multiples of 16.
+struct SmdtWgradFp8Problem {
+  const void* dy;        // [M, N] E5M2 or E4M3 (dy_fmt), row-major
+  const void* x;         // [M, K] E4M3, row-major
+  float* main_grad;      // [N, K] fp32
+  int64_t M, N, K;
+  const float* inv_dy;   // device pointers to the dequantisation factors: read by the kernel,
+  const float* inv_x;    // never by the host
+  int dy_fmt;            // 0: E4M3, 1: E5M2 (the same for every problem of a call)
+  int overwrite;         // 1: main_grad holds no data yet, store instead of adding (no read)
+};
+int smdt_wgrad_fp8_supported(int64_t M, int64_t N, int64_t K);
+// Grouped launch (one per 32 problems), tail split sized for `cus` CUs (0: the whole chip). The
+// main_grad targets of one call must not overlap.
+hipError_t smdt_wgrad_fp8_grouped_cus(const SmdtWgradFp8Problem* probs, int n, int cus, hipStream_t st);
+
 // xgmi_allreduce.hip: single-node all-reduce over HIP-IPC-mapped peer buffers.
 int smdt_ar_max_ranks();
 int smdt_ar_max_blocks();

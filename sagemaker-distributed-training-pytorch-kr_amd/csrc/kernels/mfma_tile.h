@@ -104,6 +104,58 @@ struct Frag {
   }
 };
 
+// ---------------------------------------------------------------------------------------------
+// 1-byte (FP8) tiles: the 8-bit forms of the transposed read and of the 32x32x16 MFMA.
+//
+//   * v_mfma_f32_32x32x16_{fp8,bf8}_fp8: the lane / register maps of the bf16 form above with 8
+//     one-byte values per lane (two VGPRs per operand): lane l holds A[i = l & 31][k = 8 (l >> 5) + j].
+//   * ds_read_b64_tr_b8 reads, per group of 16 consecutive lanes, a block of 8 rows x 16 columns of
+//     bytes and delivers it column-major. Lane 2q + p of the group (q = 0..7, p = 0..1) supplies the
+//     address of the block's row q, columns 8p .. 8p + 7 (8-byte aligned); lane i of the group
+//     (0..15) receives column i of the 8 rows, row q in its byte q. (Lane map read off the hardware:
+//     LDS bytes holding their own offset, every lane dumping its 8 bytes, profiles/fp8_wgrad/.)
+//     One read is therefore one whole operand fragment: lane half h takes stage rows 8h .. 8h + 7
+//     of a 16-row k-step, in order. As with the 16-bit form, only "the A and B fragments of one MFMA
+//     hold the same rows in the same order" matters to a product that sums over the rows.
+//   * Geo8<D>: rows of D bytes (D = 256: one 64-bank line per row, so unswizzled every row of a
+//     column block would sit on the same banks). The 16-byte chunk index is XORed with 2 (r & 7):
+//     a 32-lane half (the bank-conflict group of the read) holds the 8 rows q of both 16-column
+//     blocks g of a fragment, chunks (2 dt + g) ^ 2q, which are 16 distinct chunks = all 64 banks
+//     once. The swizzle depends on row bits 0..2 only, so k-steps differ by a constant offset.
+using i32x2 = __attribute__((ext_vector_type(2))) int;
+using lds_i32x2 = __attribute__((address_space(3))) i32x2;
+
+// a: E5M2 (BF8 = true) or E4M3 values, b: E4M3 values (the OCP encodings on gfx950)
+template <bool BF8>
+__device__ __forceinline__ f32x16 mfma8(long a, long b, f32x16 c) {
+  if constexpr (BF8) return __builtin_amdgcn_mfma_f32_32x32x16_bf8_fp8(a, b, c, 0, 0, 0);
+  else return __builtin_amdgcn_mfma_f32_32x32x16_fp8_fp8(a, b, c, 0, 0, 0);
+}
+
+template <int D>
+struct Geo8 {
+  static_assert(D % 256 == 0, "the swizzle needs at least 16 chunks per row");
+  static constexpr int RB = D;                 // bytes per tile row
+  static constexpr int CH = D / 16;            // 16-byte chunks per row
+  __device__ static __forceinline__ int f(int r) { return (r & 7) << 1; }
+  __device__ static __forceinline__ int off(int r, int c) { return r * RB + 16 * (c ^ f(r)); }
+};
+
+template <int D>
+struct Frag8 {
+  // Offset of the transposed read of 32-column tile dt for k-step 0: row 8 h + q, columns
+  // 32 dt + 16 g + 8 p .. + 7 (lane = 32 h + 16 g + 2 q + p).
+  __device__ static __forceinline__ int tr_off(int lane, int dt) {
+    const int h = lane >> 5, g = (lane >> 4) & 1, q = (lane >> 1) & 7, p = lane & 1;
+    return Geo8<D>::off(8 * h + q, 2 * dt + g) + 8 * p;
+  }
+  // Operand fragment of k-step s (stage rows 16 s .. 16 s + 15) at a precomputed tr_off offset.
+  __device__ static __forceinline__ long trf_at(const char* stage, int s, int o) {
+    const i32x2 v = __builtin_amdgcn_ds_read_tr8_b64_v2i32((lds_i32x2*)(stage + 16 * s * Geo8<D>::RB + o));
+    return __builtin_bit_cast(long, v);
+  }
+};
+
 // Pack accumulator registers 8 s .. 8 s + 7 into a 16-bit operand fragment.
 template <class E = bf16>
 __device__ __forceinline__ v8_t<E> pack8(const f32x16& x, int s) {

@@ -30,13 +30,13 @@
 //     single small GEMM cannot. Only the tiles past the last full round of 256 are split along m
 //     with fp32 atomics (see wgrad_grouped_kernel).
 // Work items are ordered (problem, n-group, k, n-in-group) and remapped so that the consecutive
-// items an XCD runs share A and B strips in that XCD's L2. Partial tiles (N or K not a multiple
+// items an XCD runs share A and B strips in that XCD's L2 (wgrad_sched.h, shared with the FP8 form
+// of this kernel, wgrad_fp8.hip). Partial tiles (N or K not a multiple
 // of 256, as the 50304-row LM head) load clamped columns and skip their stores.
-#include <cstdlib>
-
 #include "common.h"
 #include "launchers.h"
 #include "mfma_tile.h"
+#include "wgrad_sched.h"
 
 namespace smdt {
 namespace wg {
@@ -50,15 +50,6 @@ constexpr int kThreads = 512;
 constexpr int kWaves = kThreads / 64;
 constexpr int kGlds = SB / 1024 / kWaves;  // 1 KB wave-instructions per operand per stage per wave (2)
 constexpr int kNBuf = 4;
-
-using lds_void = __attribute__((address_space(3))) void;
-
-// s_waitcnt with vmcnt = n and the other counters left alone (gfx9 encoding).
-template <int n>
-__device__ __forceinline__ void wait_vm() {
-  static_assert(n >= 0 && n < 64, "vmcnt range");
-  __builtin_amdgcn_s_waitcnt((n & 15) | ((n >> 4) << 14) | (7 << 4) | (15 << 8));
-}
 
 // Copy one 32 x 256 bf16 stage of an operand into its LDS image. Wave instruction i (of 16)
 // fills image rows 2i, 2i+1; lane l lands at slot (row 2i + l/32, chunk l%32) and therefore
@@ -264,22 +255,6 @@ __device__ __forceinline__ void tile_gemm(const E* __restrict__ A, const E* __re
   }
 }
 
-// XCD-aware bijective remap: hardware dispatches block b to XCD b % 8; give each XCD a
-// contiguous range of work items.
-__device__ __forceinline__ int xcd_remap(int orig, int nblocks) {
-  const int xcd = orig & 7, q = nblocks >> 3, rem = nblocks & 7;
-  return (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (orig >> 3);
-}
-
-// Tile t of an ntn x ntk grid in groups of gn n-tiles x all k-tiles, n fastest inside a group.
-__device__ __forceinline__ void tile_coords(int t, int ntn, int ntk, int gn, int& tn, int& tk) {
-  const int grp = t / (gn * ntk);
-  const int gn_eff = min(gn, ntn - grp * gn);
-  const int tg = t - grp * gn * ntk;
-  tn = grp * gn + tg % gn_eff;
-  tk = tg / gn_eff;
-}
-
 #define WG_LDS                                                    \
   __shared__ __attribute__((aligned(1024))) char L0[2 * SB];      \
   __shared__ __attribute__((aligned(1024))) char L1[2 * SB];      \
@@ -365,8 +340,6 @@ __global__ __launch_bounds__(kThreads, 1) void wgrad_grouped_kernel(const Group 
   }
 }
 
-inline int group_width(int ntk) { return ntk <= 4 ? 8 : 4; }
-
 }  // namespace wg
 }  // namespace smdt
 
@@ -424,14 +397,6 @@ extern "C" hipError_t smdt_wgrad_accumulate_t(int dtype, const void* dy, const v
   return hipGetLastError();
 }
 
-static bool wg_tail_split_enabled() {
-  static const int on = [] {
-    const char* v = getenv("SMDT_WGRAD_TAIL_SPLIT");
-    return (v && v[0] == '0') ? 0 : 1;
-  }();
-  return on != 0;
-}
-
 // Grouped form: one launch per 32 problems, the table passed by value.
 extern "C" hipError_t smdt_wgrad_grouped(const SmdtWgradProblem* probs, int n, hipStream_t st) {
   return smdt_wgrad_grouped_t(1, probs, n, st);
@@ -476,18 +441,10 @@ extern "C" hipError_t smdt_wgrad_grouped_cus(int dtype, const SmdtWgradProblem* 
     // Tail split (see wgrad_grouped_kernel): r = tiles mod 256 tail tiles, ~256 / r pieces each
     // of at least 8 stages; off with SMDT_WGRAD_TAIL_SPLIT=0.
     const int r = tiles % R;
-    int splits = 1, mps = 0;
-    if (r > 0 && wg_tail_split_enabled()) {
-      int max_stages = 0;
-      for (int i = 0; i < cnt; ++i) max_stages = max_stages > g.p[i].M / wg::BM ? max_stages : g.p[i].M / wg::BM;
-      splits = R / r;
-      if (splits > 16) splits = 16;
-      if (splits > max_stages / 8) splits = max_stages / 8;
-      if (splits > 1) {
-        mps = (max_stages + splits - 1) / splits;
-        splits = (max_stages + mps - 1) / mps;
-      }
-    }
+    int max_stages = 0;
+    for (int i = 0; i < cnt; ++i) max_stages = max_stages > g.p[i].M / wg::BM ? max_stages : g.p[i].M / wg::BM;
+    int splits, mps;
+    wg::tail_split(tiles, R, max_stages, splits, mps);
     if (splits <= 1) {
       g.nfull = tiles;
       g.splits = 1;

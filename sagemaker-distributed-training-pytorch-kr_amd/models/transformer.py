@@ -82,6 +82,7 @@ class TransformerConfig:
     # FP8 linears with delayed scaling (--fp8-e4m3 / --fp8-hybrid): QKV, proj, fc1, fc2 of every
     # layer run their forward and input-gradient GEMMs on FP8 operands (tp.FP8State)
     fp8: Optional[str] = None                    # None | "e4m3" | "hybrid" (dY in E5M2)
+    fp8_wgrad: bool = False                      # --fp8-wgrad: the weight-gradient GEMM on FP8 operands too
     fp8_margin: int = 0
     fp8_interval: int = 1
     fp8_amax_history_len: int = 1
@@ -90,6 +91,8 @@ class TransformerConfig:
     def __post_init__(self):
         if self.fp8 not in (None, "e4m3", "hybrid"):
             raise ValueError(f"fp8 must be None, 'e4m3' or 'hybrid', got {self.fp8!r}")
+        if self.fp8_wgrad and not self.fp8:
+            raise ValueError("fp8_wgrad needs fp8 linears (fp8 = 'e4m3' or 'hybrid')")
         if self.fp8 and self.params_dtype not in (torch.bfloat16, torch.float16):
             raise ValueError("fp8 linears need bf16 or fp16 parameters")
         if self.fp8 and self.num_experts:
@@ -749,7 +752,8 @@ class ParallelTransformer(nn.Module):
             # dict of a 16-bit model keeps its keys
             lins = [m for l in self.layers for m in (l.attention.qkv, l.attention.proj, l.mlp.fc1, l.mlp.fc2)]
             self.fp8_state = tp.FP8State(len(lins), cfg.fp8, cfg.fp8_margin, cfg.fp8_interval,
-                                         cfg.fp8_amax_history_len, cfg.fp8_amax_compute_algo, device)
+                                         cfg.fp8_amax_history_len, cfg.fp8_amax_compute_algo, device,
+                                         fp8_wgrad=cfg.fp8_wgrad)
             tp.attach_fp8(lins, self.fp8_state)
 
     def _run(self, i, x, xb, res, doc_start=None):

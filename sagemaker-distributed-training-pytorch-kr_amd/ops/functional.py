@@ -906,3 +906,32 @@ def fp8_gemm(a, b, inv_a, inv_b, bias=None, out_dtype=torch.bfloat16):
     except RuntimeError as e:
         raise RuntimeError(f"fp8_gemm: the library refused M x N x K = {a.shape[0]} x {b.shape[0]} x {a.shape[1]} "
                            f"({a.dtype} x {b.dtype} -> {out_dtype}): {e}") from e
+
+
+def fp8_wgrad_ref(mg, qdy, qx, inv_dy, inv_x, overwrite: bool = False):
+    """Torch twin of ``fp8_wgrad``: the fp32 matmul of the dequantised operands."""
+    prod = (qdy.float() * inv_dy).t().matmul(qx.float() * inv_x).view_as(mg)
+    if overwrite:
+        mg.copy_(prod)
+    else:
+        mg.add_(prod)
+    return mg
+
+
+def fp8_wgrad_supported(M: int, N: int, K: int) -> bool:
+    """Whether the FP8 wgrad kernel takes dY [M, N] x [M, K] (M a multiple of its 64-row stage)."""
+    return M > 0 and M % 64 == 0 and N >= 16 and K >= 16 and N % 16 == 0 and K % 16 == 0 and N * K < 2 ** 31
+
+
+def fp8_wgrad(mg, qdy, qx, inv_dy, inv_x, overwrite: bool = False):
+    """mg [N, K] fp32 (+)= (inv_dy * inv_x) * qdy [M, N]^T · qx [M, K] on FP8 bytes (qdy E5M2 or
+    E4M3, qx E4M3; csrc/kernels/wgrad_fp8.hip), fp32 accumulation; ``overwrite`` stores instead of
+    adding. ``inv_dy`` / ``inv_x``: one-element fp32 dequantisation factors on the device, read by
+    the kernel. A shape the kernel refuses raises; there is no 16-bit fallback."""
+    if not _ext.use_kernels(qdy):
+        return fp8_wgrad_ref(mg, qdy, qx, inv_dy, inv_x, overwrite)
+    if not _ext.ext().wgrad_fp8_grouped([mg], [qdy], [qx], [inv_dy], [inv_x], [bool(overwrite)]):
+        raise RuntimeError(f"fp8_wgrad: the kernel refused M x N x K = {qdy.shape[0]} x {qdy.shape[1]} x "
+                           f"{qx.shape[1]} ({qdy.dtype} x {qx.dtype} -> {mg.dtype}, M must be a multiple of 64, "
+                           "N and K of 16, contiguous operands, fp32 contiguous target)")
+    return mg

@@ -301,6 +301,16 @@ def _wgrad_impl(C, mg, g2, t2):
     return impl
 
 
+_FP8_DTYPES = (torch.float8_e5m2, torch.float8_e4m3fn)
+
+
+def _cat_rows(ts):
+    """torch.cat along the rows; FP8 segments are concatenated as bytes."""
+    if ts[0].dtype in _FP8_DTYPES:
+        return torch.cat([t.view(torch.uint8) for t in ts]).view(ts[0].dtype)
+    return torch.cat(ts)
+
+
 class DeferredWgrad:
     """Deferred, grouped weight-gradient GEMMs.
 
@@ -316,6 +326,12 @@ class DeferredWgrad:
     ``start/finish_grad_sync`` before any gradient is read. A weight is reported ready to DDP
     only when its GEMM has been issued. Tensors are version-checked at flush time: an in-place
     write into a queued dY or X raises instead of producing a wrong gradient.
+
+    FP8 items (``push(..., scales=)``, the FP8 linears under --fp8-wgrad) hold q(dY) / q(x) bytes
+    and their two dequantisation factors; a flush round issues them as their own grouped launch of
+    the FP8 kernel (csrc/kernels/wgrad_fp8.hip) beside the launch of the round's 16-bit items.
+    Everything else (version checks, fresh / overwrite, segment rounds, hold / merge, readiness,
+    defer) treats them like 16-bit items; the TP exchange fillers pass over them.
     """
 
     def __init__(self):
@@ -365,6 +381,10 @@ class DeferredWgrad:
         M, N, K = g2.shape[0], g2.shape[1], t2.shape[1]
         if M % 32 or N % 8 or K % 8 or mg.numel() != N * K:
             return False
+        if g2.dtype in _FP8_DTYPES:      # an FP8 item (push(..., scales=...)): the FP8 grouped launch
+            if t2.dtype != torch.float8_e4m3fn or not SF.fp8_wgrad_supported(M, N, K):
+                return False
+            return (_FUSED_WGRAD and _ext.use_kernels(g2)) if g2.is_cuda else self.allow_cpu
         if g2.is_cuda:
             return (_FUSED_WGRAD and g2.dtype in (torch.bfloat16, torch.float16) and t2.dtype == g2.dtype
                     and _ext.use_kernels(g2))
@@ -378,11 +398,17 @@ class DeferredWgrad:
             return int(0.25 * torch.cuda.mem_get_info(dev)[0])
         return 64 * 2 ** 30
 
-    def push(self, weight, mg, g2, t2, bias=None, fresh=False):
+    def push(self, weight, mg, g2, t2, bias=None, fresh=False, scales=None):
         """Queue mg += g2^T t2; ``bias`` (a bias Parameter with an fp32 main_grad, or None): its
         gradient, the column sums of g2, comes out of the same grouped launch. ``fresh``: mg holds
         no data yet (a lazily zeroed ZeRO-2 gradient buffer) — the first GEMM into it stores
-        instead of adding."""
+        instead of adding. ``scales`` = (inv_dy, inv_x), one-element fp32 tensors: g2 / t2 are FP8
+        bytes (--fp8-wgrad) and the item goes to the FP8 grouped launch, without a bias (a bias
+        gradient is never summed from FP8 bytes). The scales of one weight are the same for every
+        segment of a step, so merged segments keep the first pair."""
+        if (scales is not None) != (g2.dtype in _FP8_DTYPES) or (scales is not None and bias is not None):
+            raise ValueError("deferred wgrad: FP8 operands come with scales=(inv_dy, inv_x) and no bias, "
+                             "16-bit operands without scales")
         if self.hold_bytes_cap is None:
             self.hold_bytes_cap = self._hold_cap(g2.device)
         key = mg.data_ptr()
@@ -400,7 +426,8 @@ class DeferredWgrad:
                 self.flush()
             # [weight, main_grad, segments, held (created inside a window), has its segment of
             # the synchronising pass, bias parameter or None, main_grad unwritten (store)]
-            it = [weight, mg, [seg], self.hold, not self.hold, bias, bool(fresh)]
+            # FP8 item: (1 / scale of dY, 1 / scale of x), else None]
+            it = [weight, mg, [seg], self.hold, not self.hold, bias, bool(fresh), scales]
             self.items.append(it)
             self.by_key[key] = it
             self.tiles += -(-g2.shape[1] // 256) * -(-t2.shape[1] // 256)
@@ -442,18 +469,18 @@ class DeferredWgrad:
         self.held_bytes = sum(sg[0].numel() * sg[0].element_size() + sg[1].numel() * sg[1].element_size()
                               for it in keep for sg in it[2])
         work = []
-        for weight, mg, segs, _held, complete, bias, fresh in items:
+        for weight, mg, segs, _held, complete, bias, fresh, scales in items:
             for g2, t2, vg, vt in segs:
                 if g2._version != vg or t2._version != vt:
                     raise RuntimeError("deferred wgrad: a queued dY / X tensor was modified in place before the "
                                        "flush; disable with SMDT_DEFER_WGRAD=0 and report the op that did it")
             if len(segs) == 1:
-                work.append((weight, mg, [(segs[0][0], segs[0][1])], complete, bias, fresh))
+                work.append((weight, mg, [(segs[0][0], segs[0][1])], complete, bias, fresh, scales))
             elif self.concat_segments and _held:
-                work.append((weight, mg, [(torch.cat([sg[0] for sg in segs]), torch.cat([sg[1] for sg in segs]))],
-                             complete, bias, fresh))
+                work.append((weight, mg, [(_cat_rows([sg[0] for sg in segs]), _cat_rows([sg[1] for sg in segs]))],
+                             complete, bias, fresh, scales))
             else:
-                work.append((weight, mg, [(sg[0], sg[1]) for sg in segs], complete, bias, fresh))
+                work.append((weight, mg, [(sg[0], sg[1]) for sg in segs], complete, bias, fresh, scales))
         self.stats["flushes"] += 1
         self.stats["items"] += len(work)
         self.stats["max_segments"] = max(self.stats["max_segments"], max(len(w[2]) for w in work))
@@ -461,15 +488,27 @@ class DeferredWgrad:
         # segments of one main_grad never run in the same launch (no write race, no atomics)
         for i in range(max(len(w[2]) for w in work)):
             # round 0 of an unwritten main_grad stores (overwrite), later rounds add
-            rnd = [(mg, sg[i], b, fr and i == 0) for _, mg, sg, _, b, fr in work if len(sg) > i]
+            rnd = [(mg, sg[i], b, fr and i == 0, sc) for _, mg, sg, _, b, fr, sc in work if len(sg) > i]
             self.stats["stores"] += sum(1 for r in rnd if r[3])
-            cuda = [(mg, g2, t2, b, ow) for mg, (g2, t2), b, ow in rnd if g2.is_cuda]
+            # one launch for the round's 16-bit items and one for its FP8 items (wgrad_fp8.hip)
+            cuda = [(mg, g2, t2, b, ow) for mg, (g2, t2), b, ow, sc in rnd if g2.is_cuda and sc is None]
             done = False
             if cuda:
                 bts = [b.main_grad if b is not None else _NO_BIAS.get(g2.device) for _, g2, _, b, _ in cuda]
                 done = _ext.ext().wgrad_grouped([c[0] for c in cuda], [c[1] for c in cuda], [c[2] for c in cuda], bts,
                                                 [c[4] for c in cuda])
-            for mg, (g2, t2), b, ow in rnd:
+            for fmt in _FP8_DTYPES:      # one MFMA opcode per launch: E5M2 and E4M3 dY apart
+                f8 = [(mg, g2, t2, sc, ow) for mg, (g2, t2), _, ow, sc in rnd
+                      if g2.is_cuda and sc is not None and g2.dtype == fmt]
+                if f8 and not _ext.ext().wgrad_fp8_grouped([c[0] for c in f8], [c[1] for c in f8], [c[2] for c in f8],
+                                                           [c[3][0] for c in f8], [c[3][1] for c in f8],
+                                                           [c[4] for c in f8]):
+                    raise RuntimeError("deferred wgrad: the FP8 grouped launch refused a queued item")
+            for mg, (g2, t2), b, ow, sc in rnd:
+                if sc is not None:
+                    if not g2.is_cuda:       # CPU (tests: allow_cpu): the twin
+                        SF.fp8_wgrad_ref(mg, g2, t2, sc[0], sc[1], ow)
+                    continue
                 if not (g2.is_cuda and done):
                     prod = g2.t().matmul(t2).view_as(mg)
                     if ow:
@@ -478,7 +517,7 @@ class DeferredWgrad:
                         mg.add_(prod)
                     if b is not None:
                         b.main_grad.add_(g2.float().sum(0))
-        for weight, _, _, complete, b, _ in work:
+        for weight, _, _, complete, b, _, _ in work:
             if not complete:
                 continue
             for p in (weight, b):
@@ -493,12 +532,13 @@ class DeferredWgrad:
         ONE weight's gradient GEMM — as its own grouped launch sized for ``cus`` CUs (the ones an
         in-flight TP exchange leaves; its tail split into pieces that fill them), and report its
         readiness. Returns False when there was nothing to issue."""
-        pick = next((it for it in self.items if it[4] and not it[3]), None)
+        # FP8 items (TP = 1 only, so never beside a TP exchange) are passed over: flush() issues them
+        pick = next((it for it in self.items if it[4] and not it[3] and it[7] is None), None)
         if pick is None:
             return False
         self.items = [it for it in self.items if it is not pick]
         self.by_key.pop(pick[1].data_ptr(), None)
-        weight, mg, segs, _held, _complete, bias, fresh = pick
+        weight, mg, segs, _held, _complete, bias, fresh, _ = pick
         self.tiles -= -(-segs[0][0].shape[1] // 256) * -(-segs[0][1].shape[1] // 256)
         self.held_bytes -= sum(sg[0].numel() * sg[0].element_size() + sg[1].numel() * sg[1].element_size()
                                for sg in segs)
@@ -547,8 +587,8 @@ class DeferredWgrad:
         and ``fire_ready`` reports the items' readiness afterwards. Returns the items issued."""
         picks, spent = [], 0.0
         for it in self.items:
-            if not (it[4] and not it[3] and len(it[2]) == 1 and it[1].is_cuda):
-                continue
+            if not (it[4] and not it[3] and len(it[2]) == 1 and it[1].is_cuda) or it[7] is not None:
+                continue                    # FP8 items are passed over (see fill_one)
             if picks and spent + _item_us(it, cus) > budget_us:
                 break
             picks.append(it)
@@ -655,7 +695,7 @@ def fill_exchange_wait():
     if not (_FILL["on"] and DEFERRED_WGRAD.items):
         return
     cus = gemm_tn_blocks()
-    it0 = next((x for x in DEFERRED_WGRAD.items if x[4] and not x[3]), None)
+    it0 = next((x for x in DEFERRED_WGRAD.items if x[4] and not x[3] and x[7] is None), None)
     if it0 is not None and it0[1].is_cuda and len(it0[2]) == 1:
         if _FILL_STREAM_ON:
             dev = it0[1].device
@@ -668,7 +708,7 @@ def fill_exchange_wait():
         return
     spent = 0.0
     while spent < _FILL_US:
-        it = next((x for x in DEFERRED_WGRAD.items if x[4] and not x[3]), None)
+        it = next((x for x in DEFERRED_WGRAD.items if x[4] and not x[3] and x[7] is None), None)
         if it is None:
             return
         spent += _item_us(it, cus)
@@ -1064,7 +1104,13 @@ def _linear_backward(ctx, g, x, weight):
 #   dX = dequant(q(dY) · q(W))              dY in E5M2 (hybrid) or E4M3
 # The operands are quantised by fp8_quant.hip, the GEMM is hipBLASLt's per-tensor-scaled FP8 GEMM.
 # The weight gradient is what it is without FP8: the 16-bit x and dY through ``_wgrad_and_bias``
-# into the fp32 main_grad. Scales are "delayed": a quantise uses the scale the last update derived
+# into the fp32 main_grad. With ``FP8State.fp8_wgrad`` (--fp8-wgrad, opt-in) it takes the FP8
+# operands as well:
+#   dW += dequant(q(dY)^T · q(x))           wgrad_fp8.hip, fp32 accumulation into main_grad
+# The forward then saves q(x) instead of the 16-bit x (scales move only after the optimizer step,
+# so the saved bytes are what a re-quantise in the backward would give), the backward's one q(dY)
+# feeds both the dgrad and the wgrad, and the bias gradient still comes from the 16-bit dY.
+# Scales are "delayed": a quantise uses the scale the last update derived
 # from earlier amax values and records its own amax for the next update, so no tensor is read
 # twice and nothing syncs with the host. TP = 1 only.
 
@@ -1096,8 +1142,9 @@ class FP8State(nn.Module):
     calls only; it matters to the interval alone, so a replayed step loses nothing by it."""
 
     def __init__(self, num_linears: int, fmt: str, margin: int = 0, interval: int = 1, history_len: int = 1,
-                 algo: str = "most_recent", device=None):
+                 algo: str = "most_recent", device=None, fp8_wgrad: bool = False):
         super().__init__()
+        self.fp8_wgrad = bool(fp8_wgrad)     # the weight-gradient GEMM on q(dY) / q(x) too
         if fmt not in ("e4m3", "hybrid"):
             raise ValueError(f"FP8State: fmt must be 'e4m3' or 'hybrid', got {fmt!r}")
         if algo not in ("most_recent", "max"):
@@ -1242,10 +1289,12 @@ class FP8Linear(torch.autograd.Function):
         ctx.state, ctx.slot0 = state, slot0
         ctx.has_bias = bias is not None
         ctx.bias_p = bias
-        ctx.save_for_backward(x, weight)
+        ctx.x_shape = x.shape
         x2 = _fp8_rows(x, "the input")
         sx, ax, ix = state.slot(slot0)
         qx = SF.fp8_quantize(x2, sx, ax, "e4m3")
+        ctx.fp8_wgrad = state.fp8_wgrad
+        ctx.save_for_backward(qx if state.fp8_wgrad else x, weight)
         qw, _ = state.weight_q(weight, slot0 + 1)
         y = SF.fp8_gemm(qx, qw, ix, state.slot(slot0 + 1)[2], bias if (add_bias and bias is not None) else None,
                         weight.dtype)
@@ -1259,10 +1308,35 @@ class FP8Linear(torch.autograd.Function):
         sg, ag, ig = state.slot(slot0 + 2)
         qg = SF.fp8_quantize(g2, sg, ag, state.grad_fmt)
         _, qwt = state.weight_q(weight, slot0 + 1)
-        gi = SF.fp8_gemm(qg, qwt, ig, state.slot(slot0 + 1)[2], None, weight.dtype).view(x.shape)
+        gi = SF.fp8_gemm(qg, qwt, ig, state.slot(slot0 + 1)[2], None, weight.dtype).view(ctx.x_shape)
+        bias_p = ctx.bias_p if ctx.has_bias else None
+        if ctx.fp8_wgrad:        # x is q(x): the wgrad on the FP8 operands, the bias from the 16-bit dY
+            dw = _fp8_wgrad(weight, qg, x, ig, state.slot(slot0)[2])
+            return gi, dw, _bias_grad(bias_p, g2), None, None, None
         t2 = x.reshape(-1, x.shape[-1])
-        dw, db = _wgrad_and_bias(weight, ctx.bias_p if ctx.has_bias else None, g2, t2)
+        dw, db = _wgrad_and_bias(weight, bias_p, g2, t2)
         return gi, dw, db, None, None, None
+
+
+def _fp8_wgrad(weight, qg, qx, inv_dy, inv_x):
+    """dW = dequant(q(dY)^T q(x)) as ``_wgrad`` does it for 16-bit operands: queued for the FP8
+    grouped launch, or one launch into ``main_grad`` now, or (no main_grad) returned to autograd."""
+    raw = getattr(weight, "_smdt_mg_raw", None)     # lazily zeroed ZeRO-2 buffer (distributed.py)
+    mg = raw() if raw is not None else getattr(weight, "main_grad", None)
+    if mg is None:
+        dw = torch.empty(qg.shape[1], qx.shape[1], dtype=torch.float32, device=qg.device)
+        return SF.fp8_wgrad(dw, qg, qx, inv_dy, inv_x, overwrite=True).to(weight.dtype)
+    if DEFERRED_WGRAD.eligible(mg, qg, qx):
+        DEFERRED_WGRAD.push(weight, mg, qg, qx, fresh=raw is not None and weight._smdt_mg_claim(),
+                            scales=(inv_dy, inv_x))
+        return None
+    if raw is not None:
+        mg = weight.main_grad                          # zeroes the slice if it is still unwritten
+    SF.fp8_wgrad(mg.view(qg.shape[1], qx.shape[1]), qg, qx, inv_dy, inv_x)
+    cb = getattr(weight, "_smdt_grad_ready", None)
+    if cb is not None:
+        cb(weight)
+    return None
 
 
 def attach_fp8(linears, state: FP8State):

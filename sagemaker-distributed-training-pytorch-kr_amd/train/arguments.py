@@ -13,7 +13,8 @@ Front-end parity with /root/reference/3_training_megatron-lm/megatron/arguments.
 ``--fp8-e4m3`` / ``--fp8-hybrid`` (with ``--fp8-margin``, ``--fp8-interval``,
 ``--fp8-amax-history-len``, ``--fp8-amax-compute-algo``) switch the four linears of every
 transformer layer to FP8 with delayed scaling (``TransformerConfig.fp8``); the weight gradient
-stays 16-bit whatever ``--no-fp8-wgrad`` says. Flags that only matter on NVIDIA stacks
+stays 16-bit unless ``--fp8-wgrad`` (ours, opt-in) puts it on the FP8 operands too
+(``TransformerConfig.fp8_wgrad``); the reference's ``--no-fp8-wgrad`` asks for what is the default here. Flags that only matter on NVIDIA stacks
 (``--transformer-impl``) are accepted and ignored; table-driven groups keep the list easy to
 audit against the reference.
 """
@@ -174,6 +175,9 @@ _GROUPS = {
         ("--attention-softmax-in-fp32", dict(action="store_true")),
         ("--accumulate-allreduce-grads-in-fp32", dict(action="store_true")),
         ("--fp16-lm-cross-entropy", dict(action="store_true")),
+        # ours: the weight-gradient GEMM of the FP8 linears on their FP8 operands (opt-in; the
+        # reference's --no-fp8-wgrad below keeps dest fp8_wgrad)
+        ("--fp8-wgrad", dict(action="store_true", dest="use_fp8_wgrad")),
     ],
     "distributed": [
         ("--tensor-model-parallel-size", dict(type=int, default=1)),
@@ -451,6 +455,11 @@ def validate_args(args, defaults=None):
         assert args.DDP_impl == "local", "distributed optimizer requires local DDP"
     # FP8 linears with delayed scaling (parallel/tensor_parallel.py FP8Linear)
     args.fp8 = None
+    use_fp8_wgrad = bool(getattr(args, "use_fp8_wgrad", False))
+    if use_fp8_wgrad and not args.fp8_wgrad:
+        raise ValueError("--fp8-wgrad and --no-fp8-wgrad contradict each other: drop one")
+    if use_fp8_wgrad and not (args.fp8_e4m3 or args.fp8_hybrid):
+        raise ValueError("--fp8-wgrad needs FP8 linears: add --fp8-hybrid or --fp8-e4m3")
     if args.fp8_e4m3 and args.fp8_hybrid:
         raise ValueError("--fp8-e4m3 and --fp8-hybrid are mutually exclusive: pick one gradient format")
     if args.fp8_e4m3 or args.fp8_hybrid:
@@ -465,9 +474,10 @@ def validate_args(args, defaults=None):
         if args.fp8_margin < 0 or args.fp8_interval < 1 or args.fp8_amax_history_len < 1:
             raise ValueError("--fp8-margin must be >= 0, --fp8-interval and --fp8-amax-history-len >= 1")
         args.fp8 = "hybrid" if args.fp8_hybrid else "e4m3"
-        if args.fp8_wgrad and args.rank == 0:
+        if args.fp8_wgrad and not use_fp8_wgrad and args.rank == 0:
             print(f"{flag}: weight gradients stay in {'bf16' if args.bf16 else 'fp16'} (as with --no-fp8-wgrad); "
-                  "FP8 covers the forward and input-gradient GEMMs", flush=True)
+                  "FP8 covers the forward and input-gradient GEMMs (--fp8-wgrad adds the weight-gradient GEMM)",
+                  flush=True)
     # iterations / samples
     if args.train_iters is not None:
         assert args.train_samples is None
@@ -528,6 +538,9 @@ def validate_args(args, defaults=None):
         for name, v in dims:
             if v % 16:
                 raise ValueError(f"{flag} needs {name} to be a multiple of 16, got {v}")
+        if use_fp8_wgrad and tokens % 64:
+            raise ValueError("--fp8-wgrad needs --seq-length x --micro-batch-size (tokens per micro-batch) to be a "
+                             f"multiple of 64 (the FP8 weight-gradient kernel's stage), got {tokens}")
     return args
 
 
@@ -573,7 +586,8 @@ def core_transformer_config_from_args(args) -> TransformerConfig:
         recompute_granularity=args.recompute_granularity, recompute_method=args.recompute_method,
         recompute_num_layers=args.recompute_num_layers,
         distribute_saved_activations=bool(args.distribute_saved_activations),
-        fp8=getattr(args, "fp8", None), fp8_margin=getattr(args, "fp8_margin", 0),
+        fp8=getattr(args, "fp8", None), fp8_wgrad=bool(getattr(args, "use_fp8_wgrad", False)),
+        fp8_margin=getattr(args, "fp8_margin", 0),
         fp8_interval=getattr(args, "fp8_interval", 1),
         fp8_amax_history_len=getattr(args, "fp8_amax_history_len", 1),
         fp8_amax_compute_algo=getattr(args, "fp8_amax_compute_algo", "most_recent"))
