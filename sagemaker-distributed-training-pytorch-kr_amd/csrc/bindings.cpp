@@ -551,6 +551,116 @@ Tensor gemm_tn_dgelu_dbias(Tensor a, Tensor b, Tensor bias, Tensor aux, Tensor d
   return c;
 }
 
+// ------------------------------------------------------------------ Switch MLP: device routing + grouped GEMM
+// Top-1 routing of logits [T, E] (fp32 / bf16 / fp16, E <= 64) into the expert-sorted, tile-padded
+// layout (kernels/moe_route.hip). Returns (top_p fp32 [T], expert_of_token int32 [T], row_of_token
+// int32 [T], token_of_row int64 [R], tile_expert int32 [R / 256], seg int32 [E, 2], counts int32 [E]);
+// the tables are allocated uninitialised and every word is written.
+std::vector<Tensor> moe_route(Tensor logits) {
+  need_contig(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) > 0 && logits.size(1) > 0 && logits.size(1) <= 64,
+              "moe_route: logits must be [T, E] with E <= 64");
+  const int64_t T = logits.size(0), E = logits.size(1), R = smdt_moe_rows(T, E);
+  auto i32 = logits.options().dtype(at::kInt);
+  Tensor top_p = torch::empty({T}, logits.options().dtype(at::kFloat));
+  Tensor top_e = torch::empty({T}, i32), row_of = torch::empty({T}, i32);
+  Tensor tok_of = torch::empty({R}, logits.options().dtype(at::kLong));
+  Tensor tile_e = torch::empty({R / 256}, i32), seg = torch::empty({E, 2}, i32), counts = torch::empty({E}, i32);
+  Tensor hist = torch::empty({(T + 255) / 256, E}, i32);
+  check(smdt_moe_route(dcode(logits), logits.data_ptr(), T, E, top_p.data_ptr<float>(), top_e.data_ptr<int>(),
+                       row_of.data_ptr<int>(), tok_of.data_ptr<int64_t>(), tile_e.data_ptr<int>(),
+                       seg.data_ptr<int>(), counts.data_ptr<int>(), hist.data_ptr<int>(), cur_stream()),
+        "moe_route");
+  return {top_p, top_e, row_of, tok_of, tile_e, seg, counts};
+}
+
+// The same into caller-made buffers (any prior contents; every word is overwritten).
+void moe_route_into(Tensor logits, Tensor top_p, Tensor top_e, Tensor row_of, Tensor tok_of, Tensor tile_e, Tensor seg,
+                    Tensor counts) {
+  need_contig(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) > 0 && logits.size(1) > 0 && logits.size(1) <= 64,
+              "moe_route: logits must be [T, E] with E <= 64");
+  const int64_t T = logits.size(0), E = logits.size(1), R = smdt_moe_rows(T, E);
+  auto ok = [&](const Tensor& t, at::ScalarType ty, int64_t n) {
+    return t.is_cuda() && t.is_contiguous() && t.scalar_type() == ty && t.numel() == n && t.device() == logits.device();
+  };
+  TORCH_CHECK(ok(top_p, at::kFloat, T) && ok(top_e, at::kInt, T) && ok(row_of, at::kInt, T) && ok(tok_of, at::kLong, R) &&
+                  ok(tile_e, at::kInt, R / 256) && ok(seg, at::kInt, 2 * E) && ok(counts, at::kInt, E),
+              "moe_route_into: table buffer mismatch");
+  Tensor hist = torch::empty({(T + 255) / 256, E}, logits.options().dtype(at::kInt));
+  check(smdt_moe_route(dcode(logits), logits.data_ptr(), T, E, top_p.data_ptr<float>(), top_e.data_ptr<int>(),
+                       row_of.data_ptr<int>(), tok_of.data_ptr<int64_t>(), tile_e.data_ptr<int>(),
+                       seg.data_ptr<int>(), counts.data_ptr<int>(), hist.data_ptr<int>(), cur_stream()),
+        "moe_route");
+}
+
+// The device table of the base pointers of same-shaped, same-typed contiguous GPU tensors (one per
+// expert) that gemm_tn_grouped picks its B / bias from. The caller keeps the tensors alive and
+// rebuilds the table when one of them is reallocated.
+Tensor ptr_table(std::vector<Tensor> ts) {
+  TORCH_CHECK(!ts.empty(), "ptr_table: empty list");
+  std::vector<int64_t> p(ts.size());
+  for (size_t i = 0; i < ts.size(); ++i) {
+    need_contig(ts[i], "ptr_table entry");
+    TORCH_CHECK(ts[i].sizes() == ts[0].sizes() && ts[i].scalar_type() == ts[0].scalar_type() &&
+                    ts[i].device() == ts[0].device(),
+                "ptr_table: entries must share shape, dtype and device");
+    p[i] = (int64_t)reinterpret_cast<uintptr_t>(ts[i].data_ptr());
+  }
+  return torch::tensor(p, torch::dtype(at::kLong)).to(ts[0].device());
+}
+
+// out[M, n] = a[M, K] . B_e^T per 256-row tile, e = tile_expert[tile] (an entry < 0: an unused tail
+// tile, computed on expert 0), B_e the [n, K] tensor btab[e] points to, with gemm_tn's epilogues
+// (bias from biastab[e]). sums (epi 3): also returns the fp32 [M / 128, n] column sums per half tile.
+std::vector<Tensor> gemm_tn_grouped(Tensor a, Tensor btab, int64_t n, Tensor tile_expert, int64_t epi, OptT biastab,
+                                    OptT aux, bool sums, int64_t max_blocks) {
+  need_contig(a, "a");
+  need_contig(btab, "btab");
+  need_contig(tile_expert, "tile_expert");
+  TORCH_CHECK(a.dim() == 2 && (a.scalar_type() == at::kBFloat16 || a.scalar_type() == at::kHalf),
+              "gemm_tn_grouped: a must be a 2-D bf16 / fp16 tensor");
+  const int64_t M = a.size(0), K = a.size(1), N = n;
+  TORCH_CHECK(smdt_gemm_tn_supported(M, N, K) != 0, "gemm_tn_grouped: unsupported shape");
+  TORCH_CHECK(btab.scalar_type() == at::kLong && btab.dim() == 1 && btab.numel() >= 1 && btab.device() == a.device(),
+              "gemm_tn_grouped: btab must be an int64 pointer table on a's device");
+  const int64_t E = btab.numel();
+  TORCH_CHECK(tile_expert.scalar_type() == at::kInt && tile_expert.numel() == M / 256 &&
+                  tile_expert.device() == a.device(),
+              "gemm_tn_grouped: tile_expert must be int32 [M / 256] on a's device");
+  TORCH_CHECK(epi >= 0 && epi <= 3 && (!sums || epi == 3), "gemm_tn_grouped: epilogue");
+  if (epi >= 1) {
+    TORCH_CHECK(biastab.has_value(), "gemm_tn_grouped: the epilogue needs a bias table");
+    need_contig(*biastab, "biastab");
+    TORCH_CHECK(biastab->scalar_type() == at::kLong && biastab->numel() == E && biastab->device() == a.device(),
+                "gemm_tn_grouped: biastab mismatch");
+  }
+  if (epi == 3) {
+    TORCH_CHECK(aux.has_value(), "gemm_tn_grouped: the GeLU-backward epilogue needs the pre-activation");
+    need_contig(*aux, "aux");
+    TORCH_CHECK(aux->numel() == M * N && aux->scalar_type() == a.scalar_type() && aux->device() == a.device(),
+                "gemm_tn_grouped: pre-activation mismatch");
+  }
+  Tensor c = torch::empty({M, N}, a.options());
+  const void* const* bt = reinterpret_cast<const void* const*>(btab.data_ptr<int64_t>());
+  const void* const* bi = epi >= 1 ? reinterpret_cast<const void* const*>(biastab->data_ptr<int64_t>()) : nullptr;
+  if (sums) {
+    Tensor part = torch::empty({M / 128, N}, a.options().dtype(at::kFloat));
+    check(smdt_gemm_tn_grouped_dgelu_sums(dcode(a), a.data_ptr(), bt, c.data_ptr(), bi, aux->data_ptr(),
+                                          part.data_ptr<float>(), tile_expert.data_ptr<int>(), (int)E, M, N, K,
+                                          (int)max_blocks, cur_stream()),
+          "gemm_tn_grouped (sums)");
+    return {c, part};
+  }
+  Tensor c2 = epi == 2 ? torch::empty({M, N}, a.options()) : Tensor();
+  check(smdt_gemm_tn_grouped(dcode(a), (int)epi, a.data_ptr(), bt, c.data_ptr(), epi == 2 ? c2.data_ptr() : nullptr,
+                             bi, epi == 3 ? aux->data_ptr() : nullptr, tile_expert.data_ptr<int>(), (int)E, M, N, K,
+                             (int)max_blocks, cur_stream()),
+        "gemm_tn_grouped");
+  if (epi == 2) return {c, c2};
+  return {c};
+}
+
 // ------------------------------------------------------------------ weight gradient (MFMA)
 // main_grad[N, K] (fp32) += dy[M, N]^T . x[M, K]; returns false when the shape is unsupported.
 bool wgrad_mfma(Tensor main_grad, Tensor dy, Tensor x, int64_t max_splits) {
@@ -572,9 +682,13 @@ bool wgrad_mfma(Tensor main_grad, Tensor dy, Tensor x, int64_t max_splits) {
 // the column sums of dy — the bias gradient — from the same launch.
 // overwrite (optional, per problem): the main_grad holds no data yet (a lazily zeroed gradient
 // buffer): the kernel stores dy^T x instead of adding it (no read of the target).
+// mranges / experts (optional, per problem; an empty tensor = none): a ranged problem, whose m range
+// is the segment of `experts[i]` in the int32 [nexp, 2] device table `mranges[i]` (moe_route's seg).
 bool wgrad_grouped(std::vector<Tensor> main_grads, std::vector<Tensor> dys, std::vector<Tensor> xs,
-                   std::vector<Tensor> biases, std::vector<bool> overwrite, int64_t cus) {
+                   std::vector<Tensor> biases, std::vector<bool> overwrite, int64_t cus,
+                   std::vector<Tensor> mranges, std::vector<int64_t> experts) {
   const size_t n = main_grads.size();
+  TORCH_CHECK(mranges.empty() || (mranges.size() == n && experts.size() == n), "wgrad_grouped: mranges / experts list length");
   TORCH_CHECK(dys.size() == n && xs.size() == n, "wgrad_grouped: list lengths differ");
   TORCH_CHECK(biases.empty() || biases.size() == n, "wgrad_grouped: biases list length");
   TORCH_CHECK(overwrite.empty() || overwrite.size() == n, "wgrad_grouped: overwrite list length");
@@ -597,8 +711,18 @@ bool wgrad_grouped(std::vector<Tensor> main_grads, std::vector<Tensor> dys, std:
         return false;
       bg = bt.data_ptr<float>();
     }
+    const int* mr = nullptr;
+    int ex = 0;
+    if (!mranges.empty() && mranges[i].numel() > 0) {
+      const Tensor& sg = mranges[i];
+      if (!sg.is_cuda() || sg.scalar_type() != at::kInt || !sg.is_contiguous() || sg.dim() != 2 || sg.size(1) != 2 ||
+          sg.get_device() != mg.get_device() || experts[i] < 0 || experts[i] >= sg.size(0) || M % 256 != 0)
+        return false;
+      mr = sg.data_ptr<int>();
+      ex = (int)experts[i];
+    }
     probs[i] = SmdtWgradProblem{dy.data_ptr(), x.data_ptr(), mg.data_ptr<float>(), M, N, K, bg,
-                                (!overwrite.empty() && overwrite[i]) ? 1 : 0};
+                                (!overwrite.empty() && overwrite[i]) ? 1 : 0, mr, ex};
   }
   if (n == 0) return true;
   check(smdt_wgrad_grouped_cus(dcode(dys[0]), probs.data(), (int)n, (int)cus, cur_stream()), "wgrad_grouped");
@@ -1095,7 +1219,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         arg("var") = 0, arg("aux") = pybind11::none());
   m.def("wgrad_mfma", &wgrad_mfma, arg("main_grad"), arg("dy"), arg("x"), arg("max_splits") = 0);
   m.def("wgrad_grouped", &wgrad_grouped, arg("main_grads"), arg("dys"), arg("xs"),
-        arg("biases") = std::vector<Tensor>{}, arg("overwrite") = std::vector<bool>{}, arg("cus") = 0);
+        arg("biases") = std::vector<Tensor>{}, arg("overwrite") = std::vector<bool>{}, arg("cus") = 0,
+        arg("mranges") = std::vector<Tensor>{}, arg("experts") = std::vector<int64_t>{});
+  m.def("moe_rows", [](int64_t T, int64_t E) { return smdt_moe_rows(T, E); });
+  m.def("gemm_tn_shape_supported", [](int64_t M, int64_t N, int64_t K) { return smdt_gemm_tn_supported(M, N, K) != 0; });
+  m.def("moe_route", &moe_route);
+  m.def("moe_route_into", &moe_route_into);
+  m.def("ptr_table", &ptr_table);
+  m.def("gemm_tn_grouped", &gemm_tn_grouped, arg("a"), arg("btab"), arg("n"), arg("tile_expert"), arg("epi") = 0,
+        arg("biastab") = pybind11::none(), arg("aux") = pybind11::none(), arg("sums") = false,
+        arg("max_blocks") = 0);
   m.def("wgrad_fp8_grouped", &wgrad_fp8_grouped, arg("main_grads"), arg("dys"), arg("xs"), arg("inv_dys"),
         arg("inv_xs"), arg("overwrite") = std::vector<bool>{}, arg("cus") = 0);
   m.def("wgrad_fp8_supported", &wgrad_fp8_supported);

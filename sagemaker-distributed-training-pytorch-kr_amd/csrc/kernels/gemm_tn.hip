@@ -134,6 +134,12 @@ struct Args {
   int tiles;    // (M / 256) * ntn
   int nt;       // K / 64 (even)
   int skew;     // odd workgroups start this many ~8k-cycle sleeps late (de-phased epilogues), 0 none
+  // GROUPED (appended: the other instantiations' argument offsets stay): B and the bias of a row
+  // tile come from per-expert pointer tables on the device, picked by tile_expert[row tile]
+  const void* const* btab;      // [nexp] B bases, each [N, K]
+  const void* const* biastab;   // [nexp] bias bases, each [N] (null with EPI_NONE)
+  const int* tile_expert;       // [M / 256], -1: an unused tail tile (computed on expert 0's weight)
+  int nexp;
 };
 
 // Stream cursor: K-step `pos` of this workgroup's tile sequence (wave-uniform).
@@ -208,15 +214,30 @@ __device__ __forceinline__ uint32_t lds_addr(const void* p) {
   return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)p;
 }
 
+// GROUPED: tab[clamp(tile_expert[tm])] as a wave-uniform 64-bit value (the index is uniform; the
+// readfirstlanes tell the compiler so, the buffer descriptor made from it lives in SGPRs).
+__device__ __forceinline__ uint64_t table_entry(const void* const* tab, const int* tile_expert, int tm, int nexp) {
+  const int x = __builtin_amdgcn_readfirstlane(min(max(tile_expert[tm], 0), nexp - 1));
+  const uint64_t p = (uint64_t)tab[x];
+  return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(p >> 32)) << 32) |
+         (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)p);
+}
+
 // VAR: diagnostic ablations for benchmarks/bench_gemm_tn.py only (the library runs VAR = 0):
 // bit 0 no in-loop DMA, bit 1 no in-loop fragment reads, bit 2 no wave stagger, bit 3 no stores,
 // bit 4 no bias / activation math in the epilogue (loads and stores stay), bit 5 sc1
 // (L2-bypassing) output stores instead of plain ones, bit 9 EPI_DGELU without the loads of the
 // pre-activation; (host) bit 7 / 8 tile groups of 1 / 4 row blocks instead of 8.
 // SUMS (EPI_DGELU only): also write the column sums of the output, see the header.
-template <class E, int EPI, int VAR = 0, bool SUMS = false>
+// GROUPED: the Switch MLP's expert GEMMs over the expert-sorted, tile-padded rows (moe_route.hip):
+// one wave-uniform load of tile_expert and of the table entry when the DMA cursor enters a tile
+// (and once more for the bias in the tile's last stage), nothing added to the stages. A tail tile
+// (tile_expert < 0) runs on expert 0's weight: its rows are padding nobody reads, and an early
+// exit would break the persistent stage stream for at most nexp wasted row tiles.
+template <class E, int EPI, int VAR = 0, bool SUMS = false, bool GROUPED = false>
 __global__ __launch_bounds__(kThreads, 1) void gemm_tn_kernel(const Args g) {
   static_assert(!SUMS || (EPI == EPI_DGELU && VAR == 0), "column sums come with the GeLU-backward epilogue");
+  static_assert(!GROUPED || VAR == 0, "the ablations are for the plain kernel");
   using V = typename V8<E>::t;
   // [A slot 0 | A slot 1 | B slot 0 | B slot 1] 32 KB each, then 4 KB of epilogue staging per
   // wave (160 KB: the whole LDS)
@@ -279,7 +300,9 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_tn_kernel(const Args g) {
     int tm, tn;
     coords(c.tile, tm, tn);
     c.a = Ab + (uint64_t)tm * kT * rowb;
-    c.b = Bb + (uint64_t)tn * kT * rowb;
+    uint64_t bb = Bb;
+    if constexpr (GROUPED) bb = table_entry(g.btab, g.tile_expert, tm, g.nexp);
+    c.b = bb + (uint64_t)tn * kT * rowb;
     c.k = 0;
   };
   auto advance = [&](Cur& c) {
@@ -358,7 +381,9 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_tn_kernel(const Args g) {
       // staging area (lanes 8.. re-load the same 128 bytes): no register held through the stage
       int otm, otn;
       coords(otile, otm, otn);
-      dma1(srd((uint64_t)((const E*)g.bias + otn * kT + 64 * wc)), 0u, (uint32_t)(lane_now() & 7) * 16,
+      const E* bias = (const E*)g.bias;
+      if constexpr (GROUPED) bias = (const E*)table_entry(g.biastab, g.tile_expert, otm, g.nexp);
+      dma1(srd((uint64_t)(bias + otn * kT + 64 * wc)), 0u, (uint32_t)(lane_now() & 7) * 16,
            epi_l + 2048);
     }
     // ---------------- p0
@@ -616,6 +641,7 @@ static hipError_t gemm_tn_launch(int dtype, int epi, const void* a, const void* 
   if (epi < 0 || epi > 3 || (epi >= 1 && !bias) || (epi == 2 && !c2) || (epi == 3 && !aux)) return hipErrorInvalidValue;
   gt::Args g;
   g.A = a; g.B = b; g.C = c; g.C2 = c2; g.bias = bias; g.aux = aux; g.colpart = colpart;
+  g.btab = nullptr; g.biastab = nullptr; g.tile_expert = nullptr; g.nexp = 0;
   g.M = (int)M; g.N = (int)N; g.K = (int)K;
   g.ntn = (int)(N / gt::kT);
   g.ntm = (int)(M / gt::kT);
@@ -687,4 +713,66 @@ static hipError_t gemm_tn_launch(int dtype, int epi, const void* a, const void* 
   }
 #undef SMDT_GT
   return hipGetLastError();
+}
+
+// The grouped form (Switch MLP experts): row tile tm of a [M, K] multiplies btab[tile_expert[tm]]
+// ([N, K]) and takes its bias from biastab[tile_expert[tm]]; the tables and tile_expert live on
+// the device (moe_route.hip writes tile_expert), so no launch parameter depends on the routing.
+static hipError_t gemm_tn_grouped_launch(int dtype, int epi, const void* a, const void* const* btab, void* c, void* c2,
+                                         const void* const* biastab, const void* aux, float* colpart,
+                                         const int* tile_expert, int nexp, int64_t M, int64_t N, int64_t K,
+                                         int max_blocks, hipStream_t st) {
+  if (dtype != 1 && dtype != 2) return hipErrorInvalidValue;
+  if (!smdt_gemm_tn_supported(M, N, K)) return hipErrorInvalidValue;
+  if (!btab || !tile_expert || nexp <= 0) return hipErrorInvalidValue;
+  if (epi < 0 || epi > 3 || (epi >= 1 && !biastab) || (epi == 2 && !c2) || (epi == 3 && !aux) || (colpart && epi != 3))
+    return hipErrorInvalidValue;
+  gt::Args g;
+  g.A = a; g.B = nullptr; g.C = c; g.C2 = c2; g.bias = nullptr; g.aux = aux; g.colpart = colpart;
+  g.btab = btab; g.biastab = biastab; g.tile_expert = tile_expert; g.nexp = nexp;
+  g.M = (int)M; g.N = (int)N; g.K = (int)K;
+  g.ntn = (int)(N / gt::kT);
+  g.ntm = (int)(M / gt::kT);
+  g.gm = 8;
+  g.tiles = g.ntm * g.ntn;
+  g.nt = (int)(K / gt::kBK);
+  g.skew = 0;
+  int grid = gt_num_cus();
+  if (max_blocks > 0 && max_blocks < grid) grid = max_blocks;
+  if (grid > g.tiles) grid = g.tiles;
+#define SMDT_GTG(E, P, S) \
+  hipLaunchKernelGGL((gt::gemm_tn_kernel<E, P, 0, S, true>), dim3(grid), dim3(gt::kThreads), 0, st, g)
+  if (dtype == 1) {
+    if (colpart) SMDT_GTG(bf16, 3, true);
+    else if (epi == 0) SMDT_GTG(bf16, 0, false);
+    else if (epi == 1) SMDT_GTG(bf16, 1, false);
+    else if (epi == 2) SMDT_GTG(bf16, 2, false);
+    else SMDT_GTG(bf16, 3, false);
+  } else {
+    if (colpart) SMDT_GTG(f16, 3, true);
+    else if (epi == 0) SMDT_GTG(f16, 0, false);
+    else if (epi == 1) SMDT_GTG(f16, 1, false);
+    else if (epi == 2) SMDT_GTG(f16, 2, false);
+    else SMDT_GTG(f16, 3, false);
+  }
+#undef SMDT_GTG
+  return hipGetLastError();
+}
+
+extern "C" hipError_t smdt_gemm_tn_grouped(int dtype, int epi, const void* a, const void* const* btab, void* c,
+                                           void* c2, const void* const* biastab, const void* aux,
+                                           const int* tile_expert, int nexp, int64_t M, int64_t N, int64_t K,
+                                           int max_blocks, hipStream_t st) {
+  return gemm_tn_grouped_launch(dtype, epi, a, btab, c, c2, biastab, aux, nullptr, tile_expert, nexp, M, N, K,
+                                max_blocks, st);
+}
+
+// EPI_DGELU with the column sums of c per 128-row half tile: colpart fp32 [M / 128, N], every word written.
+extern "C" hipError_t smdt_gemm_tn_grouped_dgelu_sums(int dtype, const void* a, const void* const* btab, void* c,
+                                                      const void* const* biastab, const void* aux, float* colpart,
+                                                      const int* tile_expert, int nexp, int64_t M, int64_t N,
+                                                      int64_t K, int max_blocks, hipStream_t st) {
+  if (!colpart) return hipErrorInvalidValue;
+  return gemm_tn_grouped_launch(dtype, 3, a, btab, c, nullptr, biastab, aux, colpart, tile_expert, nexp, M, N, K,
+                                max_blocks, st);
 }

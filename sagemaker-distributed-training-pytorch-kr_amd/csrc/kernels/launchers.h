@@ -156,6 +156,25 @@ hipError_t smdt_gemm_tn_dgelu_sums(int dtype, const void* a, const void* b, void
                                    const void* aux, float* colpart, int64_t M, int64_t N, int64_t K,
                                    int max_blocks, hipStream_t st);
 
+// The grouped form (Switch MLP experts): row tile tm multiplies btab[tile_expert[tm]] ([N, K]) and
+// takes its bias from biastab[tile_expert[tm]] (null with epi 0); btab / biastab ([nexp] pointers)
+// and tile_expert (int32 [M / 256], -1 = unused tail tile) are device memory.
+hipError_t smdt_gemm_tn_grouped(int dtype, int epi, const void* a, const void* const* btab, void* c, void* c2,
+                                const void* const* biastab, const void* aux, const int* tile_expert, int nexp,
+                                int64_t M, int64_t N, int64_t K, int max_blocks, hipStream_t st);
+hipError_t smdt_gemm_tn_grouped_dgelu_sums(int dtype, const void* a, const void* const* btab, void* c,
+                                           const void* const* biastab, const void* aux, float* colpart,
+                                           const int* tile_expert, int nexp, int64_t M, int64_t N, int64_t K,
+                                           int max_blocks, hipStream_t st);
+
+// moe_route.hip: top-1 routing of logits [T, E] (dtype 0 / 1 / 2, E <= 64) into the expert-sorted,
+// tile-padded layout of smdt_moe_rows(T, E) = (T / 256 + E) * 256 rows. Every word of every table is
+// written; hist is int32 scratch of ceil(T / 256) * E words. Three launches, no atomics.
+int64_t smdt_moe_rows(int64_t T, int64_t E);
+hipError_t smdt_moe_route(int dtype, const void* logits, int64_t T, int64_t E, float* top_p, int* expert_of_token,
+                          int* row_of_token, int64_t* token_of_row, int* tile_expert, int* seg, int* counts,
+                          int* hist, hipStream_t st);
+
 // wgrad_gemm.hip: main_grad[N, K] (fp32) += dy[M, N]^T . x[M, K] (bf16, or fp16 with dtype 2)
 int smdt_wgrad_supported(int64_t M, int64_t N, int64_t K);
 hipError_t smdt_wgrad_accumulate_t(int dtype, const void* dy, const void* x, float* main_grad, int64_t M,
@@ -169,6 +188,11 @@ struct SmdtWgradProblem {
   int64_t M, N, K;
   float* bias_grad;    // [N] fp32, += column sums of dy (the linear's bias gradient), or null
   int overwrite;       // 1: main_grad holds no data yet — write dy^T x instead of adding (no read)
+  // Ranged problem (null: the host M above is the range): the m range is rows [mrange[2 expert],
+  // + mrange[2 expert + 1]) of dy / x, int32 words on the device (moe_route.hip's seg table); M is
+  // then the row count of dy / x that bounds it. Never tail-split; a launch of their own.
+  const int* mrange;
+  int expert;
 };
 // Many independent wgrad accumulations in one launch per 32 (no split-K, no atomics). The
 // main_grad targets of one call must not overlap.

@@ -38,6 +38,8 @@
 #include "mfma_tile.h"
 #include "wgrad_sched.h"
 
+#include <vector>
+
 namespace smdt {
 namespace wg {
 
@@ -340,6 +342,61 @@ __global__ __launch_bounds__(kThreads, 1) void wgrad_grouped_kernel(const Group 
   }
 }
 
+// Ranged problems (the Switch MLP's experts under --moe-grouped-gemm): the m range of a problem is
+// not known on the host. It is the segment of expert `expert` in the expert-sorted, tile-padded row
+// layout, (start, rows) = mrange[2 expert], mrange[2 expert + 1], written on the device by
+// moe_route.hip (rows is a multiple of 256, so of BM). Every block reads its problem's range and
+// runs tile_gemm over it: whole tiles only (a tail split would need the length on the host), the
+// grid is ntn x ntk per problem whatever the routing was, deterministic. An expert without tokens
+// (rows == 0) leaves its gradient as it is, or stores zeros with `ovw`; the block returns before
+// any barrier. Problem and wgrad_grouped_kernel<E> above stay as they are (a table of their own,
+// so the existing kernel's argument layout does not move).
+struct RProblem {
+  const void* A;
+  const void* B;
+  float* C;
+  float* bias;
+  const int* mrange;   // int32 [nexp, 2] on the device
+  int expert;
+  int M;               // rows of A / B: a range outside [0, M] is ignored
+  int N, K, ntn, ntk, gn, tile0, ovw;
+};
+struct RGroup {
+  RProblem p[kMaxGroup];
+  int nprob;
+};
+
+template <class E>
+__global__ __launch_bounds__(kThreads, 1) void wgrad_ranged_kernel(const RGroup g) {
+  WG_LDS
+  const int w = xcd_remap(blockIdx.x, gridDim.x);
+  int pi = 0;
+  while (pi + 1 < g.nprob && w >= g.p[pi + 1].tile0) ++pi;
+  const RProblem& P = g.p[pi];
+  int tn, tk;
+  tile_coords(w - P.tile0, P.ntn, P.ntk, P.gn, tn, tk);
+  const int mstart = P.mrange[2 * P.expert], rows = P.mrange[2 * P.expert + 1];
+  const bool bias_tile = P.bias != nullptr && tk == 0;
+  if (mstart < 0 || rows < 0 || rows % BM != 0 || (int64_t)mstart + rows > P.M) return;
+  if (rows == 0) {
+    if (P.ovw) {   // the target holds no data yet: this expert's gradient is zero
+      for (int i = threadIdx.x; i < BT * BT; i += kThreads) {
+        const int n = tn * BT + i / BT, k = tk * BT + i % BT;
+        if (n < P.N && k < P.K) P.C[(int64_t)n * P.K + k] = 0.f;
+      }
+    }
+    return;
+  }
+  const E* A = (const E*)P.A;
+  const E* B = (const E*)P.B;
+  if (bias_tile)
+    tile_gemm<false, 0, true, E>(A, B, P.C, P.N, P.K, tn * BT, 0, mstart, rows / BM, L0, L1, L2, L3, P.bias,
+                                 P.ovw != 0);
+  else
+    tile_gemm<false, 0, false, E>(A, B, P.C, P.N, P.K, tn * BT, tk * BT, mstart, rows / BM, L0, L1, L2, L3, nullptr,
+                                  P.ovw != 0);
+}
+
 }  // namespace wg
 }  // namespace smdt
 
@@ -406,6 +463,42 @@ extern "C" hipError_t smdt_wgrad_grouped_t(int dtype, const SmdtWgradProblem* pr
   return smdt_wgrad_grouped_cus(dtype, probs, n, 0, st);
 }
 
+// Problems with `mrange` (see wgrad_ranged_kernel): one launch per 32, ntn x ntk blocks per problem.
+static hipError_t wgrad_ranged_launch(int dtype, const SmdtWgradProblem* probs, int n, hipStream_t st) {
+  for (int base = 0; base < n; base += wg::kMaxGroup) {
+    wg::RGroup g;
+    const int cnt = n - base < wg::kMaxGroup ? n - base : wg::kMaxGroup;
+    int tiles = 0;
+    for (int i = 0; i < cnt; ++i) {
+      const SmdtWgradProblem& q = probs[base + i];
+      if (q.expert < 0) return hipErrorInvalidValue;
+      wg::RProblem& p = g.p[i];
+      p.A = q.dy;
+      p.B = q.x;
+      p.C = q.main_grad;
+      p.bias = q.bias_grad;
+      p.mrange = q.mrange;
+      p.expert = q.expert;
+      p.M = (int)q.M;
+      p.N = (int)q.N;
+      p.K = (int)q.K;
+      p.ntn = (int)((q.N + wg::BT - 1) / wg::BT);
+      p.ntk = (int)((q.K + wg::BT - 1) / wg::BT);
+      p.gn = wg::group_width(p.ntk);
+      p.tile0 = tiles;
+      p.ovw = q.overwrite ? 1 : 0;
+      tiles += p.ntn * p.ntk;
+    }
+    for (int i = cnt; i < wg::kMaxGroup; ++i) g.p[i] = g.p[cnt - 1];
+    g.nprob = cnt;
+    if (dtype == 2)
+      hipLaunchKernelGGL((wg::wgrad_ranged_kernel<f16>), dim3(tiles), dim3(wg::kThreads), 0, st, g);
+    else
+      hipLaunchKernelGGL((wg::wgrad_ranged_kernel<bf16>), dim3(tiles), dim3(wg::kThreads), 0, st, g);
+  }
+  return hipGetLastError();
+}
+
 // `cus`: the CUs this launch can use at once (0 = 256). A launch beside a transfer that holds CUs
 // (a filler in a TP exchange wait, parallel/tensor_parallel.DeferredWgrad.fill_one) sizes its
 // rounds and its tail split to what is left, so no tail piece waits for the transfer to end.
@@ -415,6 +508,17 @@ extern "C" hipError_t smdt_wgrad_grouped_cus(int dtype, const SmdtWgradProblem* 
   const int R = (cus > 0 && cus < 256) ? cus : 256;
   for (int i = 0; i < n; ++i)
     if (!smdt_wgrad_supported(probs[i].M, probs[i].N, probs[i].K)) return hipErrorInvalidValue;
+  bool any_ranged = false;
+  for (int i = 0; i < n; ++i) any_ranged = any_ranged || probs[i].mrange != nullptr;
+  if (any_ranged) {   // ranged problems (device-side m range) go to launches of their own
+    std::vector<SmdtWgradProblem> plain, ranged;
+    for (int i = 0; i < n; ++i) (probs[i].mrange ? ranged : plain).push_back(probs[i]);
+    if (!plain.empty()) {
+      hipError_t e = smdt_wgrad_grouped_cus(dtype, plain.data(), (int)plain.size(), cus, st);
+      if (e != hipSuccess) return e;
+    }
+    return wgrad_ranged_launch(dtype, ranged.data(), (int)ranged.size(), st);
+  }
   for (int base = 0; base < n; base += wg::kMaxGroup) {
     wg::Group g;
     const int cnt = n - base < wg::kMaxGroup ? n - base : wg::kMaxGroup;

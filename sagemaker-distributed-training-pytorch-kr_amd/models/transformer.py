@@ -51,6 +51,7 @@ class TransformerConfig:
     normalization: str = "LayerNorm"            # or "RMSNorm"
     activation: str = "gelu"                     # gelu | swiglu | squared_relu | gelu_erf
     num_experts: Optional[int] = None            # --num-experts: Switch MLP (top-1 routed experts)
+    moe_grouped_gemm: bool = False               # --moe-grouped-gemm: device routing + grouped expert GEMMs
     add_bias_linear: bool = True
     position_embedding_type: str = "learned_absolute"   # or "rope"
     rotary_percent: float = 1.0
@@ -98,6 +99,8 @@ class TransformerConfig:
         if self.fp8 and self.num_experts:
             raise ValueError("fp8 linears with num_experts are not supported (per-expert row counts are not "
                              "multiples of 16)")
+        if self.moe_grouped_gemm and not self.num_experts:
+            raise ValueError("moe_grouped_gemm needs num_experts")
         if self.num_query_groups is None:
             self.num_query_groups = self.num_attention_heads
         if self.kv_channels is None:
@@ -624,7 +627,14 @@ class SwitchMLP(nn.Module):
     (output + bias) scaled by the router probability. Tokens are sorted by expert once, so each
     expert runs ONE contiguous GEMM chain on its slice (no per-expert masks or scatters), and one
     gather puts the rows back. The per-expert token counts are read on the host (one sync per layer),
-    so an MoE step is not graph-captured."""
+    so an MoE step is not graph-captured.
+
+    ``--moe-grouped-gemm`` (opt-in, TP = 1, bf16 / fp16, gelu, biases on): the router runs on the
+    device (csrc/kernels/moe_route.hip) into an expert-sorted, tile-padded row buffer, and the
+    experts' GEMMs are grouped launches that pick their weight per 256-row tile from device tables
+    (gemm_tn.hip GROUPED, wgrad_gemm.hip's ranged kernel): no host sync, launch shapes independent
+    of the routing, so the step can be captured (train/graphs.CapturedStep). Same parameters and
+    checkpoint layout. Where a condition fails the layer raises; it never falls back."""
 
     def __init__(self, cfg: TransformerConfig, layer_number: int, device=None):
         super().__init__()
@@ -640,13 +650,71 @@ class SwitchMLP(nn.Module):
         self.router_bias = nn.Parameter(torch.zeros(e, dtype=cfg.params_dtype, device=device))
         self.experts = nn.ModuleList(ParallelMLP(cfg, layer_number, device, key=f"layers.{layer_number}.experts.{i}")
                                      for i in range(e))
+        self._tabs = None      # --moe-grouped-gemm: the experts' pointer tables, built at first use
 
     def route(self, flat):
         """(top-1 probability [n] fp32, expert index [n]) of each token row."""
         prob = torch.softmax(F.linear(flat, self.router, self.router_bias).float(), dim=-1)
         return prob.max(dim=-1)
 
+    def _grouped_check(self, flat):
+        """--moe-grouped-gemm asked for: raise, naming the condition, where the grouped path cannot
+        run (it never falls back to the per-expert loop). Returns whether the kernels run."""
+        cfg = self.cfg
+        why = None
+        if ps.get_state().tp > 1:
+            why = "tensor parallel size 1"
+        elif cfg.activation != "gelu":
+            why = f"the gelu activation (got {cfg.activation})"
+        elif not cfg.add_bias_linear:
+            why = "linear biases (--disable-bias-linear is set)"
+        elif cfg.fp8:
+            why = "16-bit experts (fp8 is set)"
+        kern = _ext.use_kernels(flat)
+        if why is None and kern:
+            T, h, f, E = flat.shape[0], cfg.hidden_size, cfg.ffn_hidden_size, len(self.experts)
+            R = SF.moe_rows(T, E)
+            C = _ext.ext()
+            probe = self.experts[0]
+            if flat.dtype not in (torch.bfloat16, torch.float16) or probe.fc1.weight.dtype != flat.dtype:
+                why = f"bf16 or fp16 activations and weights (got {flat.dtype} / {probe.fc1.weight.dtype})"
+            elif not (C.gemm_tn_shape_supported(R, f, h) and C.gemm_tn_shape_supported(R, h, f)):
+                why = (f"gemm_tn shapes: hidden {h} and ffn {f} multiples of 256 (rows {R})")
+            elif torch.is_grad_enabled() and any(
+                    getattr(p, "main_grad", None) is None or p.main_grad.dtype != torch.float32
+                    or isinstance(getattr(type(p), "main_grad", None), property)
+                    for ex in self.experts for p in (ex.fc1.weight, ex.fc1.bias, ex.fc2.weight, ex.fc2.bias)):
+                why = "a plain fp32 main_grad on every expert weight and bias (a DDP wrapper with fp32 gradients)"
+        if why is not None:
+            raise RuntimeError(f"--moe-grouped-gemm needs {why}")
+        return kern
+
+    def _forward_grouped(self, x):
+        """--moe-grouped-gemm: device routing + grouped expert GEMMs (``tp.GroupedSwitchExperts``):
+        no host sync and no launch shape that depends on the routing."""
+        s, b, h = x.shape
+        flat = x.reshape(s * b, h)
+        kern = self._grouped_check(flat)
+        logits = F.linear(flat, self.router, self.router_bias)
+        route = SF.moe_route(logits)
+        self.last_counts = route[6]      # tokens per expert of the last call (device, int32)
+        # the router's gradient: autograd through the softmax, at the expert the tables picked
+        top_p = torch.softmax(logits.float(), dim=-1).gather(1, route[1].long().unsqueeze(1)).squeeze(1)
+        ex = self.experts
+        w1, b1 = [e.fc1.weight for e in ex], [e.fc1.bias for e in ex]
+        w2, b2 = [e.fc2.weight for e in ex], [e.fc2.bias for e in ex]
+        tabs = None
+        if kern:
+            key = tuple(p.data_ptr() for p in w1 + b1 + w2 + b2)
+            if self._tabs is None or self._tabs[0] != key:      # built once per layer
+                self._tabs = (key, (SF.moe_pointer_tables(w1, b1), SF.moe_pointer_tables(w2, b2)))
+            tabs = self._tabs[1]
+        out = tp.GroupedSwitchExperts.apply(flat, top_p, route, tabs, len(ex), *w1, *b1, *w2, *b2)
+        return out.view(s, b, h), None
+
     def forward(self, x):
+        if self.cfg.moe_grouped_gemm:
+            return self._forward_grouped(x)
         s, b, h = x.shape
         flat = x.reshape(s * b, h)
         top_p, top_e = self.route(flat)

@@ -935,3 +935,152 @@ def fp8_wgrad(mg, qdy, qx, inv_dy, inv_x, overwrite: bool = False):
                            f"{qx.shape[1]} ({qdy.dtype} x {qx.dtype} -> {mg.dtype}, M must be a multiple of 64, "
                            "N and K of 16, contiguous operands, fp32 contiguous target)")
     return mg
+
+
+# --------------------------------------------------------------------------------------------
+# Switch MLP without host syncs (--moe-grouped-gemm): device routing into an expert-sorted,
+# tile-padded row layout, and expert GEMMs that pick their weight per 256-row tile on the device
+# (csrc/kernels/moe_route.hip, gemm_tn.hip GROUPED, wgrad_gemm.hip wgrad_ranged_kernel).
+
+MOE_TILE = 256
+
+
+def moe_rows(T: int, E: int) -> int:
+    """Rows of the padded layout: every expert's segment is rounded up to whole 256-row tiles."""
+    return (T // MOE_TILE + E) * MOE_TILE
+
+
+def moe_route_ref(logits):
+    """Torch twin of ``moe_route``: the identical tables (it reads the counts on the host)."""
+    T, E = logits.shape
+    dev = logits.device
+    R = moe_rows(T, E)
+    lf = logits.float()
+    top_p = torch.softmax(lf, dim=-1).max(dim=-1).values
+    ar = torch.arange(E, device=dev).expand(T, E)
+    top_e = torch.where(lf == lf.max(dim=-1, keepdim=True).values, ar, E).min(dim=-1).values   # lowest index of a tie
+    counts = torch.bincount(top_e, minlength=E)
+    rows = (counts + MOE_TILE - 1) // MOE_TILE * MOE_TILE
+    start = torch.cumsum(rows, 0) - rows
+    order = torch.argsort(top_e, stable=True)
+    first = torch.cumsum(counts, 0) - counts                       # first sorted position of each expert
+    se = top_e[order]
+    dest = start[se] + (torch.arange(T, device=dev) - first[se])   # row of the i-th sorted token
+    row_of_token = torch.empty(T, dtype=torch.long, device=dev)
+    row_of_token[order] = dest
+    token_of_row = torch.full((R,), -1, dtype=torch.long, device=dev)
+    token_of_row[dest] = order
+    tile_expert = torch.full((R // MOE_TILE,), -1, dtype=torch.int32, device=dev)
+    for e, (s, r) in enumerate(zip(start.tolist(), rows.tolist())):
+        tile_expert[s // MOE_TILE:(s + r) // MOE_TILE] = e
+    seg = torch.stack([start, rows], dim=1).to(torch.int32)
+    return (top_p, top_e.to(torch.int32), row_of_token.to(torch.int32), token_of_row, tile_expert, seg,
+            counts.to(torch.int32))
+
+
+def moe_route(logits):
+    """Top-1 routing of router logits [T, E] (E <= 64) into the expert-sorted, tile-padded layout of
+    ``moe_rows(T, E)`` rows, with no host sync on the kernel path. Returns (top_p fp32 [T],
+    expert_of_token int32 [T], row_of_token int32 [T], token_of_row int64 [R] with -1 on pad rows,
+    tile_expert int32 [R / 256] with -1 on unused tail tiles, seg int32 [E, 2] = (start, rows),
+    counts int32 [E]). Tokens keep their order inside a segment; a tie goes to the lowest index.
+    Not differentiable: the router's gradient flows through the caller's own softmax."""
+    logits = logits.detach()
+    if logits.dim() != 2 or logits.shape[1] > 64:
+        raise ValueError("moe_route: logits must be [tokens, experts] with at most 64 experts")
+    if not _ext.use_kernels(logits):
+        return moe_route_ref(logits)
+    return tuple(_ext.ext().moe_route(logits.contiguous()))
+
+
+def gelu_tanh_grad_ref(z):
+    """d gelu_tanh(z) / dz in fp32."""
+    with torch.enable_grad():      # torch's own derivative: what autograd gives the unfused path
+        zz = z.detach().float().requires_grad_(True)
+        return torch.autograd.grad(F.gelu(zz, approximate="tanh").sum(), zz)[0]
+
+
+def gemm_tn_grouped_ref(a, weights, tile_expert, epi=0, biases=None, aux=None, sums=False):
+    """Torch twin of ``gemm_tn_grouped``, tile by tile (it reads tile_expert on the host). Unused
+    tail tiles are zero here; the kernel leaves padding there that nothing reads."""
+    M = a.shape[0]
+    N = weights[0].shape[0]
+    outs = [a.new_zeros(M, N) for _ in range(2 if epi == 2 else 1)]
+    part = torch.zeros(M // 128, N, dtype=torch.float32, device=a.device) if sums else None
+    for i, e in enumerate(tile_expert.tolist()):
+        if e < 0:
+            continue
+        r = slice(i * MOE_TILE, (i + 1) * MOE_TILE)
+        acc = F.linear(a[r], weights[e])
+        if epi == 0:
+            outs[0][r] = acc
+        elif epi == 1:
+            outs[0][r] = (acc.float() + biases[e].float()).to(a.dtype)
+        elif epi == 2:
+            outs[0][r] = acc
+            outs[1][r] = F.gelu(acc.float() + biases[e].float(), approximate="tanh").to(a.dtype)
+        else:
+            v = acc.float() * gelu_tanh_grad_ref(aux[r].float() + biases[e].float())
+            outs[0][r] = v.to(a.dtype)
+            if sums:
+                part[2 * i] = v[:128].sum(0)
+                part[2 * i + 1] = v[128:].sum(0)
+    return outs + ([part] if sums else [])
+
+
+def moe_pointer_tables(weights, biases=None):
+    """(btab, biastab): device tables of the experts' base pointers for ``gemm_tn_grouped``. The
+    caller keeps the tensors alive and rebuilds the tables when one of them is reallocated."""
+    C = _ext.ext()
+    return C.ptr_table([w.detach() for w in weights]), (C.ptr_table([b.detach() for b in biases])
+                                                       if biases is not None else None)
+
+
+def gemm_tn_grouped(a, weights, tile_expert, epi: int = 0, biases=None, aux=None, sums: bool = False, tables=None):
+    """Per 256-row tile i of a [R, K]: a_i · weights[tile_expert[i]]^T ([N, K] each) with gemm_tn's
+    epilogues (0 none, 1 + bias, 2 (pre-activation, gelu_tanh(pre + bias)), 3 product *
+    gelu_tanh'(aux + bias); ``sums`` with 3: also the fp32 [R / 128, N] column sums per half tile).
+    The expert of a tile is read on the device; ``tables`` = ``moe_pointer_tables(weights, biases)``
+    made once by the caller (built per call when None). Returns a list like ``gemm_tn``. A shape
+    the kernel does not take raises."""
+    if epi >= 1 and biases is None:
+        raise ValueError("gemm_tn_grouped: the epilogue needs the experts' biases")
+    if not _ext.use_kernels(a):
+        return gemm_tn_grouped_ref(a, weights, tile_expert, epi, biases, aux, sums)
+    if tables is None:
+        tables = moe_pointer_tables(weights, biases)
+    return _ext.ext().gemm_tn_grouped(a.contiguous(), tables[0], weights[0].shape[0], tile_expert, epi,
+                                      tables[1] if epi >= 1 else None, aux, sums, 0)
+
+
+def wgrad_ranged_ref(mg, dy, x, seg, expert: int, bias_grad=None, overwrite: bool = False):
+    """Torch twin of the ranged wgrad: mg (+)= dy[s:s + r]^T x[s:s + r] over expert's segment
+    (s, r) = seg[expert] (read on the host); an empty segment leaves mg as it is (zeros with
+    ``overwrite``). Returns whether the segment held rows."""
+    s, r = (int(v) for v in seg[expert].tolist())
+    if r == 0:
+        if overwrite:
+            mg.zero_()
+        return False
+    prod = dy[s:s + r].t().matmul(x[s:s + r]).view_as(mg)
+    if overwrite:
+        mg.copy_(prod)
+    else:
+        mg.add_(prod)
+    if bias_grad is not None:
+        bias_grad.add_(dy[s:s + r].float().sum(0))
+    return True
+
+
+def wgrad_ranged(mg, dy, x, seg, expert: int, bias_grad=None, overwrite: bool = False):
+    """mg [N, K] fp32 (+)= dy[s:s + r]^T x[s:s + r] now, (s, r) = seg[expert] read on the device
+    (wgrad_gemm.hip's ranged kernel; ``bias_grad`` fp32 [N] += the column sums of that dy range).
+    The queued form is ``DeferredWgrad.push(..., mrange=(seg, expert))``."""
+    if not _ext.use_kernels(dy):
+        wgrad_ranged_ref(mg, dy, x, seg, expert, bias_grad, overwrite)
+        return mg
+    bt = bias_grad if bias_grad is not None else torch.empty(0, dtype=torch.float32, device=mg.device)
+    if not _ext.ext().wgrad_grouped([mg], [dy], [x], [bt], [bool(overwrite)], 0, [seg], [int(expert)]):
+        raise RuntimeError(f"wgrad_ranged: the kernel refused dY {tuple(dy.shape)} x X {tuple(x.shape)} -> "
+                           f"{tuple(mg.shape)} (rows a multiple of 256, 16-bit contiguous operands, fp32 target)")
+    return mg

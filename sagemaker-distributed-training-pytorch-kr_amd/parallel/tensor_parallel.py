@@ -332,6 +332,12 @@ class DeferredWgrad:
     the FP8 kernel (csrc/kernels/wgrad_fp8.hip) beside the launch of the round's 16-bit items.
     Everything else (version checks, fresh / overwrite, segment rounds, hold / merge, readiness,
     defer) treats them like 16-bit items; the TP exchange fillers pass over them.
+
+    Ranged items (``push(..., mrange=(seg, e))``, the Switch experts under --moe-grouped-gemm): g2 /
+    t2 are the whole expert-sorted, tile-padded buffers and the GEMM runs over expert e's segment,
+    which the kernel reads from the device table ``seg`` (wgrad_gemm.hip's ranged kernel: a launch
+    of their own inside the same grouped call, never tail-split). They are never merged with a
+    later push; the TP exchange fillers pass over them too.
     """
 
     def __init__(self):
@@ -398,14 +404,17 @@ class DeferredWgrad:
             return int(0.25 * torch.cuda.mem_get_info(dev)[0])
         return 64 * 2 ** 30
 
-    def push(self, weight, mg, g2, t2, bias=None, fresh=False, scales=None):
+    def push(self, weight, mg, g2, t2, bias=None, fresh=False, scales=None, mrange=None):
         """Queue mg += g2^T t2; ``bias`` (a bias Parameter with an fp32 main_grad, or None): its
         gradient, the column sums of g2, comes out of the same grouped launch. ``fresh``: mg holds
         no data yet (a lazily zeroed ZeRO-2 gradient buffer) — the first GEMM into it stores
         instead of adding. ``scales`` = (inv_dy, inv_x), one-element fp32 tensors: g2 / t2 are FP8
         bytes (--fp8-wgrad) and the item goes to the FP8 grouped launch, without a bias (a bias
         gradient is never summed from FP8 bytes). The scales of one weight are the same for every
-        segment of a step, so merged segments keep the first pair."""
+        segment of a step, so merged segments keep the first pair. ``mrange`` = (seg, e): a ranged
+        item, the GEMM over rows [seg[e, 0], + seg[e, 1]) of g2 / t2, read on the device."""
+        if mrange is not None and (scales is not None or fresh):
+            raise ValueError("deferred wgrad: a ranged item takes 16-bit operands and an accumulating target")
         if (scales is not None) != (g2.dtype in _FP8_DTYPES) or (scales is not None and bias is not None):
             raise ValueError("deferred wgrad: FP8 operands come with scales=(inv_dy, inv_x) and no bias, "
                              "16-bit operands without scales")
@@ -416,6 +425,9 @@ class DeferredWgrad:
         seg = (g2, t2, g2._version, t2._version)
         nbytes = g2.numel() * g2.element_size() + t2.numel() * t2.element_size()
         it = self.by_key.get(key)
+        if it is not None and (mrange is not None or it[8] is not None):
+            self.flush()            # ranged items never merge: the earlier gradient is issued first
+            it = None
         if it is not None and (it[3] or self.hold or self.merge_repeats):
             # the same main_grad again inside an accumulation window: merge (the sum over the
             # concatenated token range is the same accumulation; one readiness report)
@@ -427,7 +439,9 @@ class DeferredWgrad:
             # [weight, main_grad, segments, held (created inside a window), has its segment of
             # the synchronising pass, bias parameter or None, main_grad unwritten (store)]
             # FP8 item: (1 / scale of dY, 1 / scale of x), else None]
-            it = [weight, mg, [seg], self.hold, not self.hold, bias, bool(fresh), scales]
+            # ranged item: (seg table, expert), else None]
+            it = [weight, mg, [seg], self.hold and mrange is None, not self.hold or mrange is not None, bias,
+                  bool(fresh), scales, mrange]
             self.items.append(it)
             self.by_key[key] = it
             self.tiles += -(-g2.shape[1] // 256) * -(-t2.shape[1] // 256)
@@ -469,18 +483,18 @@ class DeferredWgrad:
         self.held_bytes = sum(sg[0].numel() * sg[0].element_size() + sg[1].numel() * sg[1].element_size()
                               for it in keep for sg in it[2])
         work = []
-        for weight, mg, segs, _held, complete, bias, fresh, scales in items:
+        for weight, mg, segs, _held, complete, bias, fresh, scales, mrange in items:
             for g2, t2, vg, vt in segs:
                 if g2._version != vg or t2._version != vt:
                     raise RuntimeError("deferred wgrad: a queued dY / X tensor was modified in place before the "
                                        "flush; disable with SMDT_DEFER_WGRAD=0 and report the op that did it")
             if len(segs) == 1:
-                work.append((weight, mg, [(segs[0][0], segs[0][1])], complete, bias, fresh, scales))
+                work.append((weight, mg, [(segs[0][0], segs[0][1])], complete, bias, fresh, scales, mrange))
             elif self.concat_segments and _held:
                 work.append((weight, mg, [(_cat_rows([sg[0] for sg in segs]), _cat_rows([sg[1] for sg in segs]))],
-                             complete, bias, fresh, scales))
+                             complete, bias, fresh, scales, mrange))
             else:
-                work.append((weight, mg, [(sg[0], sg[1]) for sg in segs], complete, bias, fresh, scales))
+                work.append((weight, mg, [(sg[0], sg[1]) for sg in segs], complete, bias, fresh, scales, mrange))
         self.stats["flushes"] += 1
         self.stats["items"] += len(work)
         self.stats["max_segments"] = max(self.stats["max_segments"], max(len(w[2]) for w in work))
@@ -488,23 +502,36 @@ class DeferredWgrad:
         # segments of one main_grad never run in the same launch (no write race, no atomics)
         for i in range(max(len(w[2]) for w in work)):
             # round 0 of an unwritten main_grad stores (overwrite), later rounds add
-            rnd = [(mg, sg[i], b, fr and i == 0, sc) for _, mg, sg, _, b, fr, sc in work if len(sg) > i]
+            rnd = [(mg, sg[i], b, fr and i == 0, sc, mr) for _, mg, sg, _, b, fr, sc, mr in work if len(sg) > i]
             self.stats["stores"] += sum(1 for r in rnd if r[3])
             # one launch for the round's 16-bit items and one for its FP8 items (wgrad_fp8.hip)
-            cuda = [(mg, g2, t2, b, ow) for mg, (g2, t2), b, ow, sc in rnd if g2.is_cuda and sc is None]
+            cuda = [(mg, g2, t2, b, ow, mr) for mg, (g2, t2), b, ow, sc, mr in rnd if g2.is_cuda and sc is None]
             done = False
             if cuda:
-                bts = [b.main_grad if b is not None else _NO_BIAS.get(g2.device) for _, g2, _, b, _ in cuda]
-                done = _ext.ext().wgrad_grouped([c[0] for c in cuda], [c[1] for c in cuda], [c[2] for c in cuda], bts,
-                                                [c[4] for c in cuda])
+                bts = [b.main_grad if b is not None else _NO_BIAS.get(g2.device) for _, g2, _, b, _, _ in cuda]
+                if any(c[5] is not None for c in cuda):      # ranged items: their own launch inside the call
+                    none = torch.empty(0, dtype=torch.int32, device=cuda[0][1].device)
+                    done = _ext.ext().wgrad_grouped(
+                        [c[0] for c in cuda], [c[1] for c in cuda], [c[2] for c in cuda], bts, [c[4] for c in cuda], 0,
+                        [c[5][0] if c[5] is not None else none for c in cuda],
+                        [int(c[5][1]) if c[5] is not None else 0 for c in cuda])
+                    if not done:
+                        raise RuntimeError("deferred wgrad: the grouped launch refused a queued ranged item")
+                else:
+                    done = _ext.ext().wgrad_grouped([c[0] for c in cuda], [c[1] for c in cuda], [c[2] for c in cuda],
+                                                    bts, [c[4] for c in cuda])
             for fmt in _FP8_DTYPES:      # one MFMA opcode per launch: E5M2 and E4M3 dY apart
-                f8 = [(mg, g2, t2, sc, ow) for mg, (g2, t2), _, ow, sc in rnd
+                f8 = [(mg, g2, t2, sc, ow) for mg, (g2, t2), _, ow, sc, _ in rnd
                       if g2.is_cuda and sc is not None and g2.dtype == fmt]
                 if f8 and not _ext.ext().wgrad_fp8_grouped([c[0] for c in f8], [c[1] for c in f8], [c[2] for c in f8],
                                                            [c[3][0] for c in f8], [c[3][1] for c in f8],
                                                            [c[4] for c in f8]):
                     raise RuntimeError("deferred wgrad: the FP8 grouped launch refused a queued item")
-            for mg, (g2, t2), b, ow, sc in rnd:
+            for mg, (g2, t2), b, ow, sc, mr in rnd:
+                if mr is not None:
+                    if not (g2.is_cuda and done):      # the twin (CPU, or kernels disabled)
+                        SF.wgrad_ranged_ref(mg, g2, t2, mr[0], mr[1], b.main_grad if b is not None else None, ow)
+                    continue
                 if sc is not None:
                     if not g2.is_cuda:       # CPU (tests: allow_cpu): the twin
                         SF.fp8_wgrad_ref(mg, g2, t2, sc[0], sc[1], ow)
@@ -517,7 +544,7 @@ class DeferredWgrad:
                         mg.add_(prod)
                     if b is not None:
                         b.main_grad.add_(g2.float().sum(0))
-        for weight, _, _, complete, b, _, _ in work:
+        for weight, _, _, complete, b, _, _, _ in work:
             if not complete:
                 continue
             for p in (weight, b):
@@ -533,12 +560,12 @@ class DeferredWgrad:
         in-flight TP exchange leaves; its tail split into pieces that fill them), and report its
         readiness. Returns False when there was nothing to issue."""
         # FP8 items (TP = 1 only, so never beside a TP exchange) are passed over: flush() issues them
-        pick = next((it for it in self.items if it[4] and not it[3] and it[7] is None), None)
+        pick = next((it for it in self.items if it[4] and not it[3] and it[7] is None and it[8] is None), None)
         if pick is None:
             return False
         self.items = [it for it in self.items if it is not pick]
         self.by_key.pop(pick[1].data_ptr(), None)
-        weight, mg, segs, _held, _complete, bias, fresh, _ = pick
+        weight, mg, segs, _held, _complete, bias, fresh, _, _ = pick
         self.tiles -= -(-segs[0][0].shape[1] // 256) * -(-segs[0][1].shape[1] // 256)
         self.held_bytes -= sum(sg[0].numel() * sg[0].element_size() + sg[1].numel() * sg[1].element_size()
                                for sg in segs)
@@ -587,8 +614,8 @@ class DeferredWgrad:
         and ``fire_ready`` reports the items' readiness afterwards. Returns the items issued."""
         picks, spent = [], 0.0
         for it in self.items:
-            if not (it[4] and not it[3] and len(it[2]) == 1 and it[1].is_cuda) or it[7] is not None:
-                continue                    # FP8 items are passed over (see fill_one)
+            if not (it[4] and not it[3] and len(it[2]) == 1 and it[1].is_cuda) or it[7] is not None or it[8] is not None:
+                continue                    # FP8 and ranged items are passed over (see fill_one)
             if picks and spent + _item_us(it, cus) > budget_us:
                 break
             picks.append(it)
@@ -904,6 +931,7 @@ _WT_CACHE: dict = {}
 def params_changed():
     """Invalidate every cached W^T and FP8 q(W) (call before any out-of-autograd parameter write)."""
     _WT_CACHE.clear()
+    _PARAMS_EPOCH[0] += 1           # the Switch experts' W^T buffers (moe_weight_t_tables) refill
     for s in list(_FP8_STATES):
         s._wq.clear()
 
@@ -911,6 +939,7 @@ def params_changed():
 def drop_cached_weight_t(params):
     """Forget the W^T of these parameters (ZeRO-3 frees a gathered bucket: its transposes must go
     with it, or the cache would end up holding a full bf16 copy of the model on every rank)."""
+    _PARAMS_EPOCH[0] += 1
     for p in params:
         _WT_CACHE.pop(id(p), None)
         for s in list(_FP8_STATES):
@@ -1432,6 +1461,127 @@ def fused_gelu_mlp_ok(x, mlp) -> bool:
     parallelism and with its bias left to the caller."""
     return (_tp_size() == 1 and linear_bias_gelu_ok(x, mlp.fc1) and mlp.fc2.skip_bias_add
             and not mlp.fc2.sequence_parallel and mlp.fc2.weight.dtype == x.dtype)
+
+
+class GroupedSwitchExperts(torch.autograd.Function):
+    """The experts of a Switch MLP at TP = 1 on the expert-sorted, tile-padded rows that
+    ``SF.moe_route`` laid out (--moe-grouped-gemm): no host sync, no launch shape that depends on
+    the per-expert counts, so the layer can be captured in a HIP graph.
+
+    Forward: gather the tokens into the padded buffer (pad rows zero), grouped fc1 + bias + GeLU
+    (keeps the pre-activation, as ``FusedGeLUMLP``), grouped fc2 + bias, gather back by
+    ``row_of_token``, times ``top_p``. Backward: d(top_p) = rowwise dot of dOut with the unscaled
+    expert output; the scaled dOut gathered into the padded layout, fc2 dgrad with the GeLU
+    backward in its epilogue on the per-expert W2^T, fc1 dgrad on the per-expert W1^T, gather back.
+    The 2 E weight gradients (and the bias gradients, from their bias tiles) are ranged items of
+    ``DeferredWgrad`` when the parameters have an fp32 ``main_grad`` — the kernel path requires
+    one; the torch twin (CPU, or SMDT_DISABLE_KERNELS=1) hands them to autograd otherwise, None for
+    an expert without tokens.
+
+    ``apply(x [T, h], top_p [T], route, tabs, E, *w1, *b1, *w2, *b2)``: ``route`` the tuple
+    ``SF.moe_route`` returned, ``tabs`` = (fc1 tables, fc2 tables) for the forward or None."""
+
+    @staticmethod
+    def forward(ctx, x, top_p, route, tabs, E, *params):
+        w1, b1, w2, b2 = (list(params[i * E:(i + 1) * E]) for i in range(4))
+        _, _, row_of_token, token_of_row, tile_expert, seg, _ = route
+        kern = _ext.use_kernels(x)
+        if kern:
+            xs = _ext.ext().gather_rows(x.contiguous(), token_of_row)
+        else:
+            xs = x.index_select(0, token_of_row.clamp_min(0)) * (token_of_row >= 0).unsqueeze(-1).to(x.dtype)
+        pre, act = SF.gemm_tn_grouped(xs, w1, tile_expert, 2, b1, tables=tabs[0] if tabs else None)
+        y = SF.gemm_tn_grouped(act, w2, tile_expert, 1, b2, tables=tabs[1] if tabs else None)[0]
+        u = y.index_select(0, row_of_token)                  # the unscaled expert output per token
+        ctx.save_for_backward(xs, pre, act, u, top_p, row_of_token, token_of_row, tile_expert, seg)
+        ctx.params = (w1, b1, w2, b2)
+        ctx.kern = kern
+        return u * top_p.unsqueeze(-1).to(x.dtype)
+
+    @staticmethod
+    def backward(ctx, dout):
+        xs, pre, act, u, top_p, row_of_token, token_of_row, tile_expert, seg = ctx.saved_tensors
+        w1, b1, w2, b2 = ctx.params
+        E = len(w1)
+        dprob = (dout * u).sum(-1).to(top_p.dtype)
+        du = (dout * top_p.unsqueeze(-1).to(dout.dtype)).contiguous()
+        if ctx.kern:
+            dys = _ext.ext().gather_rows(du, token_of_row)
+            w2t, w1t = moe_weight_t_tables(w2, b1), moe_weight_t_tables(w1, None)
+        else:
+            dys = du.index_select(0, token_of_row.clamp_min(0)) * (token_of_row >= 0).unsqueeze(-1).to(du.dtype)
+            w2t = w1t = None
+        b1d = [b.detach() for b in b1]
+        dz = SF.gemm_tn_grouped(dys, w2t[0] if w2t else [w.detach().t().contiguous() for w in w2], tile_expert, 3, b1d,
+                                aux=pre, tables=w2t[1] if w2t else None)[0]
+        dxs = SF.gemm_tn_grouped(dz, w1t[0] if w1t else [w.detach().t().contiguous() for w in w1], tile_expert, 0,
+                                 tables=w1t[1] if w1t else None)[0]
+        dx = dxs.index_select(0, row_of_token)
+        grads = []
+        for ws, bs, g2, t2 in ((w1, b1, dz, xs), (w2, b2, dys, act)):
+            gw, gb = [], []
+            for e in range(E):
+                dw, db = _wgrad_ranged(ws[e], bs[e], g2, t2, seg, e, ctx.kern)
+                gw.append(dw)
+                gb.append(db)
+            grads.append((gw, gb))
+        (gw1, gb1), (gw2, gb2) = grads
+        return (dx, dprob, None, None, None, *gw1, *gb1, *gw2, *gb2)
+
+
+def _wgrad_ranged(weight, bias_p, g2, t2, seg, e, kern):
+    """(dW, db) of expert e for autograd, each None when it went into the fp32 main_grad: queued as
+    a ranged item (``DeferredWgrad``) or, on the twin without a main_grad, computed from the host
+    copy of the segment (None for an expert without tokens)."""
+    mg = getattr(weight, "main_grad", None)
+    bmg = getattr(bias_p, "main_grad", None)
+    if mg is not None and bmg is not None and mg.dtype == torch.float32 and bmg.dtype == torch.float32:
+        q = DEFERRED_WGRAD
+        if q.eligible(mg, g2, t2):
+            q.push(weight, mg, g2, t2, bias=bias_p, mrange=(seg, e))
+            return None, None
+        if kern:
+            SF.wgrad_ranged(mg, g2, t2, seg, e, bmg)
+        else:
+            SF.wgrad_ranged_ref(mg, g2, t2, seg, e, bmg)
+        for p in (weight, bias_p):
+            cb = getattr(p, "_smdt_grad_ready", None)
+            if cb is not None:
+                cb(p)
+        return None, None
+    if kern:
+        raise RuntimeError("--moe-grouped-gemm: the experts' weights and biases need an fp32 main_grad")
+    s, r = (int(v) for v in seg[e].tolist())
+    if r == 0:
+        return None, None
+    return g2[s:s + r].t().matmul(t2[s:s + r]), g2[s:s + r].sum(0)
+
+
+# Per-expert W^T for the grouped dgrads: one persistent [E, in, out] buffer per weight list with
+# the pointer tables over it, both made once (the table's H2D copy would not be capturable, and a
+# graph replay must find the W^T where the capture left them). The contents are re-transposed
+# when the parameters changed: ``params_changed`` / ``drop_cached_weight_t`` advance the epoch.
+_MOE_WT: dict = {}
+_PARAMS_EPOCH = [0]
+
+
+def moe_weight_t_tables(weights, biases):
+    """([W_e^T], (table of the W_e^T, table of ``biases`` or None)) for ``gemm_tn_grouped``."""
+    key = (tuple((w.data_ptr(), tuple(w.shape), w.dtype) for w in weights),
+           tuple(b.data_ptr() for b in biases) if biases is not None else None)
+    hit = _MOE_WT.get(id(weights[0]))
+    if hit is None or hit["key"] != key:
+        buf = weights[0].new_empty((len(weights), weights[0].shape[1], weights[0].shape[0]))
+        wts = list(buf.unbind(0))
+        hit = {"key": key, "wts": wts, "tabs": SF.moe_pointer_tables(wts, biases), "stamp": None}
+        _MOE_WT[id(weights[0])] = hit
+    stamp = (_PARAMS_EPOCH[0], tuple(w._version for w in weights))
+    if hit["stamp"] != stamp:
+        with torch.no_grad():
+            for wt, w in zip(hit["wts"], weights):
+                wt.copy_(w.detach().t())
+        hit["stamp"] = stamp
+    return hit["wts"], hit["tabs"]
 
 
 class SPFusedGeLUMLP(torch.autograd.Function):

@@ -178,6 +178,9 @@ _GROUPS = {
         # ours: the weight-gradient GEMM of the FP8 linears on their FP8 operands (opt-in; the
         # reference's --no-fp8-wgrad below keeps dest fp8_wgrad)
         ("--fp8-wgrad", dict(action="store_true", dest="use_fp8_wgrad")),
+        # ours (Megatron-core's name): the Switch MLP of --num-experts with device routing and
+        # grouped expert GEMMs, no host sync (models/transformer.SwitchMLP, opt-in)
+        ("--moe-grouped-gemm", dict(action="store_true")),
     ],
     "distributed": [
         ("--tensor-model-parallel-size", dict(type=int, default=1)),
@@ -492,6 +495,23 @@ def validate_args(args, defaults=None):
     assert args.seq_length is not None and args.max_position_embeddings >= args.seq_length
     if args.ffn_hidden_size is None:
         args.ffn_hidden_size = 4 * args.hidden_size if not args.swiglu else int(8 * args.hidden_size / 3)
+    if getattr(args, "moe_grouped_gemm", False):
+        # the grouped Switch path (tp.GroupedSwitchExperts): what it cannot run is refused here
+        if not args.num_experts:
+            raise ValueError("--moe-grouped-gemm needs --num-experts")
+        if requested_tp > 1:
+            raise ValueError("--moe-grouped-gemm with --tensor-model-parallel-size > 1 is not supported")
+        if args.swiglu or args.squared_relu or not args.add_bias_linear:
+            raise ValueError("--moe-grouped-gemm needs the GeLU activation with linear biases (no --swiglu, "
+                             "--squared-relu or --disable-bias-linear)")
+        if args.hidden_size % 256 or args.ffn_hidden_size % 256:
+            raise ValueError("--moe-grouped-gemm needs --hidden-size and --ffn-hidden-size to be multiples of 256 "
+                             f"(got {args.hidden_size} and {args.ffn_hidden_size})")
+        if args.fp8_e4m3 or args.fp8_hybrid:
+            raise ValueError("--moe-grouped-gemm with --fp8-e4m3 / --fp8-hybrid is not supported")
+        if os.environ.get("SMDT_LAZY_GRAD_ZERO") == "1":
+            raise ValueError("--moe-grouped-gemm with SMDT_LAZY_GRAD_ZERO=1 is not supported: the ranged weight "
+                             "gradients accumulate into zeroed fp32 buffers")
     if args.kv_channels is None:
         assert args.hidden_size % args.num_attention_heads == 0
         args.kv_channels = args.hidden_size // args.num_attention_heads
@@ -575,6 +595,7 @@ def core_transformer_config_from_args(args) -> TransformerConfig:
         init_method_std=args.init_method_std, params_dtype=args.params_dtype, seed=args.seed,
         init_method="xavier_uniform" if args.init_method_xavier_uniform else "normal",
         layernorm_zero_centered_gamma=args.apply_layernorm_1p, num_experts=args.num_experts,
+        moe_grouped_gemm=bool(getattr(args, "moe_grouped_gemm", False)),
         apply_residual_connection_post_layernorm=args.apply_residual_connection_post_layernorm,
         perform_initialization=args.perform_initialization,
         use_cpu_initialization=bool(args.use_cpu_initialization),

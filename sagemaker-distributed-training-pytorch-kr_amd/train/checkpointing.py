@@ -240,7 +240,7 @@ CHECKPOINT_ARGS = ("num_layers", "hidden_size", "ffn_hidden_size", "seq_length",
                    "rotary_percent", "add_bias_linear", "swiglu", "untie_embeddings_and_output_weights",
                    "normalization", "layernorm_epsilon", "tokenizer_type", "vocab_size", "padded_vocab_size",
                    "make_vocab_size_divisible_by", "tensor_model_parallel_size",
-                   "pipeline_model_parallel_size")
+                   "pipeline_model_parallel_size", "moe_grouped_gemm")
 
 
 def load_args_from_checkpoint(args, load_dir: Optional[str] = None) -> bool:
