@@ -295,8 +295,11 @@ class _ScaledSoftmax(torch.autograd.Function):
 def scaled_masked_softmax(x, mask=None, scale: float = 1.0, causal: bool = False):
     """softmax(scale * x) over the last dim of [b, np, sq, sk].
 
-    ``causal`` masks key j > query i (Megatron's upper-triangular mask); otherwise ``mask``
-    ([b, 1, sq, sk] bool, True = masked) is applied if given.
+    ``causal`` masks key j > query i (Megatron's upper-triangular mask) for any sq, sk: the
+    triangle is aligned to the top-left corner, on the kernel path and the PyTorch path alike (for
+    sq != sk this is NOT the bottom-right alignment of a decoding step). Otherwise ``mask``
+    ([b, 1, sq, sk] or [1, 1, sq, sk] bool, True = masked) is applied if given; a fully masked
+    row gives zeros.
     """
     mode = 1 if causal else (2 if mask is not None else 0)
     if _ext.use_kernels(x) and x.shape[-1] <= 4096 and x.shape[-1] % 8 == 0:
@@ -307,7 +310,7 @@ def scaled_masked_softmax(x, mask=None, scale: float = 1.0, causal: bool = False
     xf = x.float() * scale
     if mode == 1:
         sq, sk = x.shape[-2], x.shape[-1]
-        cm = torch.ones(sq, sk, dtype=torch.bool, device=x.device).triu(1 + sk - sq)
+        cm = torch.ones(sq, sk, dtype=torch.bool, device=x.device).triu(1)
         xf = xf.masked_fill(cm, float("-inf"))
     elif mode == 2:
         xf = xf.masked_fill(mask, float("-inf"))

@@ -9,6 +9,7 @@ is zero beyond row 64.
 import pytest
 import torch
 
+import _numerics as N
 from _numerics import (CE_TOL, SOFTMAX_TOL, ce_case, ce_kernel_emulation, ce_ref, lmce_case,
                        lmce_kernel_emulation, lmce_ref, row_rel_err, softmax_case, softmax_grad_floor,
                        softmax_ref)
@@ -86,3 +87,170 @@ def test_vocab_parallel_lm_head_ce_math_cpu(V, vocab):
     assert row_rel_err(dw, rdw) <= CE_TOL / 3, row_rel_err(dw, rdw)
     _, bdh, bdw = lmce_ref(h, w, lg, tgt, dl, vocab, soft=1.1)
     assert row_rel_err(bdh, rdh) > 2 * CE_TOL and row_rel_err(bdw, rdw) > 2 * CE_TOL
+
+
+# ------------------------------------------------------------------ fused norm (layernorm.hip)
+
+def _ln_inputs(rows, H, dtype, rms, form, seed=21):
+    """The case, the 16-bit s the kernel would store, and the keyword arguments shared by
+    ``ln_ref`` and ``ln_kernel_emulation``. form: plain | fused (bias, residual, ds_in, x2, dy2) |
+    drop (bias, residual, ds_in and a p = 0.1 keep mask)."""
+    c = N.ln_case(rows, H, dtype, torch.float32 if dtype == torch.float16 else None,
+                  fused=form != "plain", summands=form == "fused", seed=seed)
+    keep, ks = None, 1.0
+    if form == "drop":
+        keep = torch.rand(rows, H, generator=torch.Generator().manual_seed(3)) >= 0.1
+        ks = 1 / 0.9
+    s = N.ln_s_emulation(c["x"], c.get("x2"), c.get("bias"), c.get("res"), keep, ks)
+    return c, s, dict(keep=keep, keep_scale=ks, ds_in=c.get("ds_in"), dy2=c.get("dy2"))
+
+
+def _ln_errors(out, ref):
+    e = {k: N.row_rel_err(out[k], ref[k]) for k in ("y", "ds", "dx") if k in out}
+    e.update({k: N.col_rel_err(out[k], ref[k], ref[sc])
+              for k, sc in (("dgamma", "sg"), ("dbeta", "sb"), ("dbias", "sbi")) if k in out})
+    return e
+
+
+@pytest.mark.parametrize("rows,H", [(4101, 512), (4101, 1536), (1029, 5120), (2300, 64), (3, 8)])
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32])
+def test_ln_emulation_within_a_quarter_of_the_tolerances(rows, H, dtype):
+    """The measurement the LN_* tolerances are sized from (4x the largest value seen here, see the
+    comment beside them in _numerics.py): the kernel's rounding points against the float64
+    reference, under every criterion the GPU tests use."""
+    for rms in (False, True):
+        for form in ("plain", "fused", "drop"):
+            c, s, kw = _ln_inputs(rows, H, dtype, rms, form)
+            ref = N.ln_ref(s, c["gamma"], c["beta"], c["dy"], 1e-5, rms, **kw)
+            emu = N.ln_kernel_emulation(s, c["gamma"], c["beta"], c["dy"], 1e-5, rms, **kw)
+            e = _ln_errors(emu, ref)
+            e["mean"] = ((emu["mean"].double() - ref["mean"]).abs() / s.double().abs().mean(-1)).max().item()
+            e["rstd"] = ((emu["rstd"].double() - ref["rstd"]).abs() / ref["rstd"]).max().item()
+            print(f"ln emulation {dtype} {rows}x{H} rms={rms} {form}: " + " ".join(f"{k}={v:.3g}" for k, v in e.items()))
+            for k in ("y", "ds", "dx"):
+                assert e[k] <= N.LN_ELEM_TOL[dtype] / 4 * 1.01, (rms, form, k, e[k])
+            for k in ("dgamma", "dbeta", "dbias"):
+                assert e[k] <= N.LN_COL_TOL / 4 * 1.01, (rms, form, k, e[k])
+            assert e["mean"] <= N.LN_STAT_TOL / 4 * 1.01 and e["rstd"] <= N.LN_STAT_TOL / 4 * 1.01, (rms, form, e)
+
+
+# mutation -> (rows, H, the outputs whose criterion must reject it). m2 / (H + 8) differs from
+# m2 / H by 8 / (H + 8): at H = 512 that is 1.5 % of one term of ds, below ten bf16 tolerances by
+# arithmetic, so it is shown at H = 8 (the sweep's smallest row), where the term is halved.
+_LN_MUT = {"no_m1": (4101, 512, ("ds", "dx")), "m2_h_plus_8": (2300, 8, ("ds", "dx")),
+           "dgamma_first_pass": (4101, 512, ("dgamma",)), "dbeta_no_last_row": (4101, 512, ("dbeta",)),
+           "stale_rstd": (4101, 512, ("ds", "dx")), "dx_unmasked": (4101, 512, ("dx", "dbias"))}
+
+
+@pytest.mark.parametrize("mutation", N.LN_MUTATIONS)
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+def test_ln_criteria_reject_mutations(mutation, dtype):
+    """Each mutation of ``ln_ref`` (one term of the backward wrong) is at least 10 tolerances away
+    from the true reference under the criterion of every output it touches, while the emulation of
+    the kernel passes the same criterion on the same inputs."""
+    rows, H, outs = _LN_MUT[mutation]
+    rstep = N.ln_geometry(H, rows)["bwd_rstep"]
+    for rms in (False, True):
+        if rms and mutation == "no_m1":
+            continue                        # RMSNorm has no m1 term
+        c, s, kw = _ln_inputs(rows, H, dtype, rms, "drop")
+        ref = N.ln_ref(s, c["gamma"], c["beta"], c["dy"], 1e-5, rms, **kw)
+        emu = _ln_errors(N.ln_kernel_emulation(s, c["gamma"], c["beta"], c["dy"], 1e-5, rms, **kw), ref)
+        bad = _ln_errors(N.ln_ref(s, c["gamma"], c["beta"], c["dy"], 1e-5, rms, mutate=mutation, rstep=rstep, **kw), ref)
+        print(f"ln mutation {mutation} {dtype} rms={rms}: " + " ".join(f"{k}={bad[k]:.3g}" for k in outs))
+        for k in outs:
+            tol = N.LN_ELEM_TOL[dtype] if k in ("y", "ds", "dx") else N.LN_COL_TOL
+            assert emu[k] <= tol, (k, emu[k])
+            assert bad[k] >= 10 * tol, (rms, k, bad[k], tol)
+
+
+def test_ln_accumulate_criterion_rejects_overwrite():
+    """The accumulate form (``dgamma_acc`` = an fp32 main_grad with O(10) content): prefill + the
+    emulation's sum passes the column criterion against prefill + reference; a kernel that
+    overwrote the buffer is >= 10 tolerances away."""
+    c, s, kw = _ln_inputs(4101, 512, torch.bfloat16, False, "fused")
+    ref = N.ln_ref(s, c["gamma"], c["beta"], c["dy"], 1e-5, False, **kw)
+    emu = N.ln_kernel_emulation(s, c["gamma"], c["beta"], c["dy"], 1e-5, False, **kw)
+    pre = 10 * torch.randn(512, generator=torch.Generator().manual_seed(4))
+    for k, sc in (("dgamma", "sg"), ("dbeta", "sb"), ("dbias", "sbi")):
+        want = pre.double() + ref[k]
+        assert N.col_rel_err(pre + emu[k], want, ref[sc]) <= N.LN_COL_TOL
+        e = N.col_rel_err(emu[k], want, ref[sc])
+        print(f"ln accumulate overwritten {k}: {e:.3g}")
+        assert e >= 10 * N.LN_COL_TOL
+
+
+def test_ln_s_check_is_one_rounding():
+    """``ulp_distance``: equal tensors 0, neighbours 1, across zero 2 (+-tiny), and a s rounded
+    twice (fp32 -> fp16-precision -> bf16) or scaled by 1 + 2^-6 is farther than the 1 ulp the GPU
+    test allows."""
+    a = torch.tensor([1.0, -1.0, 3.0], dtype=torch.bfloat16)
+    assert N.ulp_distance(a, a.clone()) == 0
+    assert N.ulp_distance(a, torch.tensor([1.0078125, -1.0, 3.0], dtype=torch.bfloat16)) == 1
+    c = N.ln_case(64, 512, fused=True)
+    s = N.ln_s_emulation(c["x"], None, c["bias"], c["res"])
+    assert N.ulp_distance(s, (s.float() * (1 + 2.0 ** -6)).bfloat16()) > 1
+    assert N.ulp_distance(s, N.ln_s_emulation(c["x"], None, None, c["res"])) > 1     # bias forgotten
+
+
+# ---------------------------------------------------------- softmax in fp16 / fp32 and the edges
+
+_SM_CASES = [(8, 8), (136, 40), (520, 64), (4096, 64), (136, 7), (1536, 8)]
+
+
+@pytest.mark.parametrize("sk,sq", _SM_CASES)
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32])
+def test_softmax_dtype_tolerances(sk, sq, dtype):
+    """The measurement SOFTMAX_TOLS is sized from, on the very inputs test_norm_softmax_gpu.py
+    gives the kernel (b = 1, np = 3): the emulation of softmax.hip's rounding points in each dtype
+    against the float64 reference stays within a quarter of the fp16 / fp32 tolerances in all three
+    mask modes, and within 0.6 of bf16's SOFTMAX_TOL (fixed at 0.03 earlier; the bf16 emulation
+    reaches 0.016 on a causal row with few live keys, where the row is judged against its floor);
+    an all-zero output, dx x 1.1 and an unmasked forward are rejected."""
+    ty, tdx = N.SOFTMAX_TOLS[dtype]
+    for mode in (0, 1, 2):
+        if sk == 1536 and mode == 1:
+            continue            # not a GPU case: causal C = 4 is the square sk = 2048 test
+        x, dy = N.softmax_case(sk, mode == 1, b=1, np_=3, sq=sq, dtype=dtype)
+        mask = None
+        if mode == 2:
+            mask = torch.rand(1, 1, sq, sk, generator=torch.Generator().manual_seed(1)) < 0.3
+        y, dx = N.softmax_ref(x, dy, 0.125, mode == 1, mask, dtype=torch.float64)
+        ye, dxe = N.softmax_kernel_emulation(x, dy, 0.125, mode == 1, mask)
+        fl = N.softmax_grad_floor(y, dy, 0.125, dtype)
+        ey, edx = N.row_rel_err(ye, y), N.row_rel_err(dxe, dx, row_floor=fl)
+        print(f"softmax emulation {dtype} sk={sk} sq={sq} mode={mode}: y={ey:.3g} dx={edx:.3g}")
+        frac = 0.6 if dtype == torch.bfloat16 else 0.2525
+        assert ey <= ty * frac and edx <= tdx * frac, (mode, ey, edx)
+        assert N.row_rel_err(torch.zeros_like(y), y) > 2 * ty
+        assert N.row_rel_err(torch.zeros_like(dx), dx, row_floor=fl) > 2 * tdx
+        assert N.row_rel_err(1.1 * dx, dx, row_floor=fl) > 2 * tdx
+        if mode:
+            assert N.row_rel_err(torch.softmax(x.double() * 0.125, -1), y) > 2 * ty
+
+
+def test_softmax_ref_fully_masked_row_is_zero():
+    x, dy = N.softmax_case(136, False, b=1, np_=2, sq=5)
+    mask = torch.zeros(1, 1, 5, 136, dtype=torch.bool)
+    mask[0, 0, 3] = True
+    y, dx = N.softmax_ref(x, dy, 0.125, False, mask, dtype=torch.float64)
+    assert torch.isfinite(y).all() and torch.isfinite(dx).all()
+    assert (y[:, :, 3] == 0).all() and (dx[:, :, 3] == 0).all() and (y[:, :, 2].sum(-1) - 1).abs().max() < 1e-12
+    ye, dxe = N.softmax_kernel_emulation(x, dy, 0.125, False, mask)
+    assert (ye[:, :, 3] == 0).all() and (dxe[:, :, 3] == 0).all()
+
+
+def test_causal_softmax_rectangular_is_top_left_aligned():
+    """``scaled_masked_softmax(causal=True)`` with sq != sk masks key j > query i (what the kernel
+    and the docstring say), not j > i + sk - sq: the PyTorch path at sq = 40, sk = 136 equals the
+    reference's ``triu(1)`` mask and differs from the bottom-right form by a whole probability."""
+    from smdt_amd.ops import functional as SF
+    x, dy = N.softmax_case(136, True, b=1, np_=3, sq=40)
+    y = SF.scaled_masked_softmax(x, None, 0.125, causal=True)
+    yr, _ = N.softmax_ref(x, dy, 0.125, True, dtype=torch.float64)
+    assert N.row_rel_err(y, yr) <= N.SOFTMAX_TOL
+    assert (y[..., 0, 0] == 1).all() and (y[..., 0, 1:] == 0).all()          # query 0 sees key 0 only
+    i, j = torch.arange(40)[:, None], torch.arange(136)[None, :]
+    assert (y[..., j > i] == 0).all() and (y[..., 39, :40] > 0).any()
+    br = torch.softmax((x.double() * 0.125).masked_fill(j > i + 96, float("-inf")), -1)
+    assert N.row_rel_err(br, yr) > 0.5
