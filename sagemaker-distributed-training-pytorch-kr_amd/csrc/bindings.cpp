@@ -409,6 +409,70 @@ std::vector<Tensor> fp8_quantize(Tensor x, Tensor scale, Tensor amax, int64_t fm
   return {q};
 }
 
+// ------------------------------------------------------------------ MX (block-scaled) FP8
+// x [R, C] bf16 / fp16 -> the row form (q [R, C], s [R, C / 32]) and / or the column form
+// (qt [C, R], st [C, R / 32]: the quantisation of x^T) in float8_e4m3fn (fmt 0) or float8_e5m2
+// (fmt 1) with uint8 E8M0 scales; returns the requested forms in that order.
+std::vector<Tensor> mx_quantize(Tensor x, int64_t fmt, bool rows, bool cols) {
+  need_contig(x, "x");
+  TORCH_CHECK(x.dim() == 2, "mx_quantize: x must be 2-D, got ", x.dim(), "-D");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf, "mx_quantize: bf16 / fp16 only");
+  TORCH_CHECK(fmt == 0 || fmt == 1, "mx_quantize: fmt must be 0 (e4m3) or 1 (e5m2)");
+  TORCH_CHECK(rows || cols, "mx_quantize: nothing to produce");
+  const int64_t R = x.size(0), C = x.size(1);
+  TORCH_CHECK(R >= 1 && C >= 1, "mx_quantize: empty input [", R, ", ", C, "]");
+  TORCH_CHECK(!rows || C % 32 == 0, "mx_quantize: the row form needs columns in multiples of 32, got [", R, ", ", C, "]");
+  TORCH_CHECK(!cols || (R % 32 == 0 && C % 16 == 0),
+              "mx_quantize: the column form needs rows in multiples of 32 and columns of 16, got [", R, ", ", C, "]");
+  const auto qopt = x.options().dtype(fmt == 0 ? at::kFloat8_e4m3fn : at::kFloat8_e5m2);
+  const auto sopt = x.options().dtype(at::kByte);
+  Tensor q, s, qt, st;
+  if (rows) { q = torch::empty({R, C}, qopt); s = torch::empty({R, C / 32}, sopt); }
+  if (cols) { qt = torch::empty({C, R}, qopt); st = torch::empty({C, R / 32}, sopt); }
+  check(smdt_mx_quantize(x.data_ptr(), rows ? q.data_ptr() : nullptr, rows ? s.data_ptr() : nullptr,
+                         cols ? qt.data_ptr() : nullptr, cols ? st.data_ptr() : nullptr, R, C, dcode(x), (int)fmt,
+                         cur_stream()),
+        "mx_quantize");
+  std::vector<Tensor> out;
+  if (rows) { out.push_back(q); out.push_back(s); }
+  if (cols) { out.push_back(qt); out.push_back(st); }
+  return out;
+}
+
+bool gemm_mx_supported(int64_t M, int64_t N, int64_t K) { return smdt_gemm_mx_supported(M, N, K) != 0; }
+
+// out [M, N] = a [M, K] . b [N, K]^T on MX operands (+ bias [N]); see kernels/gemm_mx.hip.
+Tensor gemm_mx(Tensor a, Tensor sa, Tensor b, Tensor sb, OptT bias, int64_t out_dtype, int64_t max_blocks) {
+  TORCH_CHECK(a.dim() == 2 && b.dim() == 2 && sa.dim() == 2 && sb.dim() == 2, "gemm_mx: 2-D operands and scales");
+  const int64_t M = a.size(0), K = a.size(1), N = b.size(0);
+  TORCH_CHECK(a.is_cuda() && b.is_cuda() && sa.is_cuda() && sb.is_cuda(), "gemm_mx: GPU tensors only");
+  TORCH_CHECK(a.is_contiguous() && b.is_contiguous() && sa.is_contiguous() && sb.is_contiguous(),
+              "gemm_mx: operands and scales must be contiguous (M x N x K = ", M, " x ", N, " x ", K, ")");
+  TORCH_CHECK(b.size(1) == K && smdt_gemm_mx_supported(M, N, K) != 0, "gemm_mx: M x N x K = ", M, " x ", N, " x ",
+              b.size(1) == K ? K : -1, " refused: M, N and K must be multiples of 128 and the operands' K must agree");
+  TORCH_CHECK(a.scalar_type() == at::kFloat8_e4m3fn || a.scalar_type() == at::kFloat8_e5m2,
+              "gemm_mx: a must be float8_e4m3fn or float8_e5m2");
+  TORCH_CHECK(b.scalar_type() == at::kFloat8_e4m3fn, "gemm_mx: b must be float8_e4m3fn");
+  TORCH_CHECK(sa.scalar_type() == at::kByte && sb.scalar_type() == at::kByte && sa.size(0) == M &&
+                  sa.size(1) == K / 32 && sb.size(0) == N && sb.size(1) == K / 32,
+              "gemm_mx: scales must be uint8 [rows, K / 32]");
+  for (const Tensor* t : {&a, &b, &sa, &sb}) {
+    TORCH_CHECK(t->device() == a.device(), "gemm_mx: operands on different devices");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, "gemm_mx: operands must be 16-byte aligned");
+  }
+  TORCH_CHECK(out_dtype == 1 || out_dtype == 2, "gemm_mx: out_dtype must be 1 (bf16) or 2 (fp16)");
+  auto out = torch::empty({M, N}, a.options().dtype(out_dtype == 1 ? at::kBFloat16 : at::kHalf));
+  if (bias) {
+    need_contig(*bias, "bias");
+    TORCH_CHECK(bias->numel() == N && bias->scalar_type() == out.scalar_type() && bias->device() == a.device(),
+                "gemm_mx: bias must be [N] of the output dtype");
+  }
+  check(smdt_gemm_mx((int)out_dtype, a.scalar_type() == at::kFloat8_e5m2 ? 1 : 0, a.data_ptr(), sa.data_ptr(),
+                     b.data_ptr(), sb.data_ptr(), out.data_ptr(), optr(bias), M, N, K, (int)max_blocks, cur_stream()),
+        "gemm_mx");
+  return out;
+}
+
 // In place on scale [T], hist [T, H], amax [T]; fmt_max [T] (448 or 57344 per tensor).
 void fp8_update_scales(Tensor scale, Tensor hist, Tensor amax, Tensor fmt_max, int64_t margin, bool use_max) {
   need_contig(scale, "scale");
@@ -1208,6 +1272,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("transpose2d", &transpose2d);
   m.def("fp8_quantize", &fp8_quantize);
   m.def("fp8_update_scales", &fp8_update_scales);
+  m.def("mx_quantize", &mx_quantize, arg("x"), arg("fmt"), arg("rows") = true, arg("cols") = false);
+  m.def("gemm_mx", &gemm_mx, arg("a"), arg("sa"), arg("b"), arg("sb"), arg("bias") = pybind11::none(),
+        arg("out_dtype") = 1, arg("max_blocks") = 0);
+  m.def("gemm_mx_supported", &gemm_mx_supported);
   m.def("paced_copy", &paced_copy);
   m.def("gather_rows", &gather_rows);
   m.def("aug_depthwise", &aug_depthwise);

@@ -82,6 +82,18 @@ hipError_t smdt_fp8_quantize(const void* x, void* q, void* qt, const float* scal
 // scale = (fmt_max / reduce(hist)) / 2^margin (kept when the reduced amax is 0 or not finite).
 hipError_t smdt_fp8_update_scales(float* scale, float* hist, float* amax, const float* fmt_max, int64_t T,
                                   int64_t H, int margin, int use_max, hipStream_t st);
+// mx_quant.hip: OCP MX quantisation of x [R, C] (bf16 / fp16) into one-byte elements (bf8 = 0: E4M3,
+// 1: E5M2) with one E8M0 scale byte per 32 elements. Row form q [R, C], s [R, C / 32] (C % 32 ==
+// 0) and / or column form qt [C, R], st [C, R / 32] with the blocks along R (R % 32 == 0, C % 16
+// == 0); a null q or qt leaves that form out, both given read x once.
+hipError_t smdt_mx_quantize(const void* x, void* q, void* s, void* qt, void* st, int64_t R, int64_t C, int dtype,
+                            int bf8, hipStream_t st_);
+// gemm_mx.hip: c [M, N] (dtype bf16 / fp16) = a [M, K] . b [N, K]^T on MX operands (a E5M2 when
+// a_bf8, else E4M3; b E4M3; sa [M, K / 32], sb [N, K / 32] E8M0) (+ bias [N] of c's dtype).
+// M, N, K multiples of 128. max_blocks > 0 caps the persistent grid.
+int smdt_gemm_mx_supported(int64_t M, int64_t N, int64_t K);
+hipError_t smdt_gemm_mx(int dtype, int a_bf8, const void* a, const void* sa, const void* b, const void* sb, void* c,
+                        const void* bias, int64_t M, int64_t N, int64_t K, int max_blocks, hipStream_t st);
 // link_standin.hip: paced copy standing in for a TP-pair exchange in single-GPU rank emulation
 hipError_t smdt_paced_copy(const void* src, void* dst, int64_t nbytes, int blocks, int64_t ns, hipStream_t st);
 // dst[r] = map[r] >= 0 ? src[map[r]] : 0 (rows of row_bytes, a multiple of 16)

@@ -88,8 +88,17 @@ class TransformerConfig:
     fp8_interval: int = 1
     fp8_amax_history_len: int = 1
     fp8_amax_compute_algo: str = "most_recent"   # or "max"
+    # --fp8-recipe: "delayed" (per-tensor delayed scaling, above) | "mxfp8" (OCP MX block scaling
+    # on the scaled MFMA, tp.MXFP8Linear: no state, no table in the state dict)
+    fp8_recipe: str = "delayed"
 
     def __post_init__(self):
+        if self.fp8_recipe not in ("delayed", "mxfp8"):
+            raise ValueError(f"fp8_recipe must be 'delayed' or 'mxfp8', got {self.fp8_recipe!r}")
+        if self.fp8_recipe == "mxfp8" and not self.fp8:
+            raise ValueError("fp8_recipe 'mxfp8' needs fp8 linears (fp8 = 'e4m3' or 'hybrid')")
+        if self.fp8_recipe == "mxfp8" and self.fp8_wgrad:
+            raise ValueError("fp8_recipe 'mxfp8' keeps the weight gradient in 16 bits: fp8_wgrad is not supported")
         if self.fp8 not in (None, "e4m3", "hybrid"):
             raise ValueError(f"fp8 must be None, 'e4m3' or 'hybrid', got {self.fp8!r}")
         if self.fp8_wgrad and not self.fp8:
@@ -819,10 +828,26 @@ class ParallelTransformer(nn.Module):
             # QKV, projection, fc1 and fc2 of every layer; registered only with FP8 on, so the state
             # dict of a 16-bit model keeps its keys
             lins = [m for l in self.layers for m in (l.attention.qkv, l.attention.proj, l.mlp.fc1, l.mlp.fc2)]
+            if cfg.fp8_recipe == "mxfp8":      # stateless: no module, no buffer, nothing in the state dict
+                tp.attach_mxfp8(lins, tp.MXFP8Recipe(cfg.fp8))
+                return
             self.fp8_state = tp.FP8State(len(lins), cfg.fp8, cfg.fp8_margin, cfg.fp8_interval,
                                          cfg.fp8_amax_history_len, cfg.fp8_amax_compute_algo, device,
                                          fp8_wgrad=cfg.fp8_wgrad)
             tp.attach_fp8(lins, self.fp8_state)
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
+                              error_msgs):
+        if self.cfg.fp8 and self.cfg.fp8_recipe == "mxfp8":
+            # a delayed-scaling checkpoint: its table has no meaning for block scaling
+            table = [k for k in state_dict if k.startswith(prefix + "fp8_state.")]
+            for k in table:
+                del state_dict[k]
+            if table and (not torch.distributed.is_initialized() or torch.distributed.get_rank() == 0):
+                print(f"FP8: --fp8-recipe mxfp8 keeps no scaling state: dropped the checkpoint's delayed-scaling "
+                      f"table ({prefix}fp8_state.*)", flush=True)
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
+                                      error_msgs)
 
     def _run(self, i, x, xb, res, doc_start=None):
         layer = self.layers[i]

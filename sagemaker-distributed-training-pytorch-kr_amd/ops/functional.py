@@ -941,6 +941,123 @@ def fp8_wgrad(mg, qdy, qx, inv_dy, inv_x, overwrite: bool = False):
 
 
 # --------------------------------------------------------------------------------------------
+# MXFP8 (--fp8-recipe mxfp8): OCP MX block scaling, one E8M0 scale byte (bias 127) per 32 elements
+# along the contraction dimension (csrc/kernels/mx_quant.hip, gemm_mx.hip). No amax table, no
+# delayed scale: a block's scale comes from the block itself.
+
+MX_BLOCK = 32
+MX_EMAX = {"e4m3": 8, "e5m2": 15}    # exponent of the format's largest power of two
+
+
+def _mx_check(x, fmt, columnwise, name):
+    if fmt not in FP8_MAX:
+        raise ValueError(f"{name}: fmt must be 'e4m3' or 'e5m2', got {fmt!r}")
+    if x.dim() != 2 or x.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"{name}: need a 2-D bf16 / fp16 tensor, got {tuple(x.shape)} {x.dtype}")
+    R, C = x.shape
+    if columnwise:
+        if R < 32 or R % 32 or C < 16 or C % 16:
+            raise ValueError(f"{name}: the column form needs [R multiple of 32, C multiple of 16], got {tuple(x.shape)}")
+    elif R < 1 or C < 32 or C % 32:
+        raise ValueError(f"{name}: the row form needs [M >= 1, K multiple of 32], got {tuple(x.shape)}")
+
+
+def mx_quantize_ref(x, fmt: str, columnwise: bool = False):
+    """Torch twin of ``mx_quantize`` and its definition. Per block of 32 along the last dimension
+    (of x^T with ``columnwise``): a = max |v| over the finite values, e = clamp(floor(log2 a) -
+    emax, -127, 127) (0 when a == 0), s = e + 127, q = fp8(clamp(v * 2^-e, +-max)), round to
+    nearest even; NaN stays NaN, +-inf saturates."""
+    xf = x.float()
+    if columnwise:
+        xf = xf.t()
+    M, K = xf.shape
+    b = xf.reshape(M, K // MX_BLOCK, MX_BLOCK)
+    a = torch.where(torch.isfinite(b), b.abs(), torch.zeros_like(b)).amax(dim=-1)
+    ex = (a.contiguous().view(torch.int32) >> 23) & 0xFF          # floor(log2 a) + 127 (0 for an fp32 subnormal)
+    e = (ex - 127 - MX_EMAX[fmt]).clamp(-127, 127)
+    e = torch.where(a == 0, torch.zeros_like(e), e)
+    mult = ((127 - e) << 23).to(torch.int32).view(torch.float32)   # 2^-e, exact
+    mx = FP8_MAX[fmt]
+    q = (b * mult.unsqueeze(-1)).clamp(-mx, mx).to(FP8_DTYPE[fmt]).reshape(M, K)   # clamp keeps NaN
+    return q.contiguous(), (e + 127).to(torch.uint8)
+
+
+def mx_quantize(x, fmt: str, columnwise: bool = False):
+    """MX quantisation of x [M, K] bf16 / fp16 (K % 32 == 0): (q [M, K] in ``fmt`` ("e4m3" |
+    "e5m2"), s [M, K / 32] uint8 E8M0). With ``columnwise`` x is [R, C] (R % 32 == 0, C % 16 == 0)
+    and the result is the quantisation of x^T: (qT [C, R], sT [C, R / 32]), blocks along R."""
+    _mx_check(x, fmt, columnwise, "mx_quantize")
+    if not _ext.use_kernels(x):
+        return mx_quantize_ref(x, fmt, columnwise)
+    out = _ext.ext().mx_quantize(x.contiguous(), 0 if fmt == "e4m3" else 1, not columnwise, bool(columnwise))
+    return out[0], out[1]
+
+
+def mx_quantize_weight_ref(w, fmt: str = "e4m3"):
+    return mx_quantize_ref(w, fmt) + mx_quantize_ref(w, fmt, True)
+
+
+def mx_quantize_weight(w, fmt: str = "e4m3"):
+    """Both forms of a weight w [N, K] (N, K multiples of 32) from one read of it: (q [N, K],
+    s [N, K / 32], qT [K, N], sT [K, N / 32]), the operands of the forward and the dgrad GEMM."""
+    _mx_check(w, fmt, False, "mx_quantize_weight")
+    _mx_check(w, fmt, True, "mx_quantize_weight")
+    if not _ext.use_kernels(w):
+        return mx_quantize_weight_ref(w, fmt)
+    return tuple(_ext.ext().mx_quantize(w.contiguous(), 0 if fmt == "e4m3" else 1, True, True))
+
+
+def mx_dequantize_ref(q, s):
+    M, K = q.shape
+    scale = torch.ldexp(torch.ones((), dtype=torch.float32, device=q.device), s.to(torch.int32) - 127)
+    return (q.float().reshape(M, K // MX_BLOCK, MX_BLOCK) * scale.unsqueeze(-1)).reshape(M, K)
+
+
+def mx_dequantize(q, s):
+    """fp32 [M, K] = q * 2^(s - 127) per block of 32 (plain torch on every device: tests and
+    references only, nothing on the training path calls it)."""
+    return mx_dequantize_ref(q, s)
+
+
+def gemm_mx_ref(a, sa, b, sb, bias=None, out_dtype=torch.bfloat16):
+    """Torch twin of ``gemm_mx``: the fp32 matmul of the dequantised operands."""
+    acc = mx_dequantize_ref(a, sa).matmul(mx_dequantize_ref(b, sb).t())
+    if bias is not None:
+        acc = acc + bias.float()
+    return acc.to(out_dtype)
+
+
+def gemm_mx_supported(M: int, N: int, K: int) -> bool:
+    """Whether the block-scaled GEMM takes [M, K] x [N, K]: every extent a multiple of 128."""
+    return (M > 0 and N > 0 and K > 0 and M % 128 == 0 and N % 128 == 0 and K % 128 == 0
+            and M * K < 2 ** 31 and N * K < 2 ** 31 and M * N < 2 ** 31)
+
+
+def gemm_mx(a, sa, b, sb, bias=None, out_dtype=torch.bfloat16, max_blocks: int = 0):
+    """out [M, N] = sum_k a[m, k] 2^(sa[m, k / 32] - 127) * b[n, k] 2^(sb[n, k / 32] - 127) (+ bias)
+    on gfx950's block-scaled MFMA (csrc/kernels/gemm_mx.hip): a [M, K] E4M3 or E5M2, b [N, K] E4M3,
+    uint8 E8M0 scales, fp32 accumulation, bf16 / fp16 output. M, N and K must be multiples of 128
+    and the operands contiguous: anything else raises with the shape; there is no fallback.
+    ``max_blocks`` > 0 caps the persistent grid (tests)."""
+    M, K = a.shape
+    N = b.shape[0]
+    shape = f"M x N x K = {M} x {N} x {K}"
+    if b.shape[1] != K or not gemm_mx_supported(M, N, K):
+        raise ValueError(f"gemm_mx: {shape} refused (b is {tuple(b.shape)}): M, N and K must be multiples of 128")
+    if tuple(sa.shape) != (M, K // 32) or tuple(sb.shape) != (N, K // 32) or sa.dtype != torch.uint8 or sb.dtype != torch.uint8:
+        raise ValueError(f"gemm_mx: {shape}: scales must be uint8 [rows, K / 32], got {tuple(sa.shape)} and {tuple(sb.shape)}")
+    if not (a.is_contiguous() and b.is_contiguous() and sa.is_contiguous() and sb.is_contiguous()):
+        raise ValueError(f"gemm_mx: {shape}: operands and scales must be contiguous")
+    if a.dtype not in (torch.float8_e4m3fn, torch.float8_e5m2) or b.dtype != torch.float8_e4m3fn:
+        raise ValueError(f"gemm_mx: {shape}: a must be E4M3 or E5M2 and b E4M3, got {a.dtype} and {b.dtype}")
+    if out_dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"gemm_mx: bf16 / fp16 output only, got {out_dtype}")
+    if not _ext.use_kernels(a):
+        return gemm_mx_ref(a, sa, b, sb, bias, out_dtype)
+    return _ext.ext().gemm_mx(a, sa, b, sb, bias, 1 if out_dtype == torch.bfloat16 else 2, int(max_blocks))
+
+
+# --------------------------------------------------------------------------------------------
 # Switch MLP without host syncs (--moe-grouped-gemm): device routing into an expert-sorted,
 # tile-padded row layout, and expert GEMMs that pick their weight per 256-row tile on the device
 # (csrc/kernels/moe_route.hip, gemm_tn.hip GROUPED, wgrad_gemm.hip wgrad_ranged_kernel).

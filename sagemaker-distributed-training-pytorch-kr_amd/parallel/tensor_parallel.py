@@ -934,6 +934,7 @@ def params_changed():
     _PARAMS_EPOCH[0] += 1           # the Switch experts' W^T buffers (moe_weight_t_tables) refill
     for s in list(_FP8_STATES):
         s._wq.clear()
+    _MX_WQ.clear()
 
 
 def drop_cached_weight_t(params):
@@ -944,6 +945,7 @@ def drop_cached_weight_t(params):
         _WT_CACHE.pop(id(p), None)
         for s in list(_FP8_STATES):
             s._wq.pop(id(p), None)      # q(W) and q(W)^T go with the gathered weight too
+        _MX_WQ.pop(id(p), None)
 
 
 def mm_rows(g, w):
@@ -1372,6 +1374,90 @@ def attach_fp8(linears, state: FP8State):
     """Give each linear (Column / RowParallelLinear) its three rows of ``state``'s table."""
     for i, lin in enumerate(linears):
         object.__setattr__(lin, "_fp8", (state, _FP8_SLOTS * i))    # a reference, not a submodule
+
+
+# --------------------------------------------------------------------------------------------
+# MXFP8 linears (--fp8-recipe mxfp8): the same two GEMMs on OCP MX operands, one E8M0 scale per 32
+# elements along the contraction dimension, dequantised by the matrix core (gemm_mx.hip):
+#   y  = q_row(x) · q_row(W)^T + b          x, W in E4M3, blocks along `in`
+#   dX = q_row(dY) · q_col(W)^T             dY in E5M2 (hybrid) or E4M3, blocks along `out`
+# A block's scale comes from the block itself, so there is no table, no amax all-reduce, nothing
+# after the optimizer step and nothing in the state dict; no call reads the host, so a step
+# captures with no caveat. The weight gradient is the 16-bit one (``_wgrad_and_bias``), x is saved
+# in 16 bits. Both forms of q(W) are made by one launch per optimizer step and dropped by
+# ``params_changed()`` like the cached W^T. TP = 1 only; every extent a multiple of 128.
+
+_MX_WQ: dict = {}
+
+
+class MXFP8Recipe:
+    """What ``attach_mxfp8`` hangs on a linear: the gradient format alone ("hybrid": dY in E5M2)."""
+
+    def __init__(self, fmt: str):
+        if fmt not in ("e4m3", "hybrid"):
+            raise ValueError(f"MXFP8Recipe: fmt must be 'e4m3' or 'hybrid', got {fmt!r}")
+        if _tp_size() > 1:
+            raise NotImplementedError("MXFP8 linears (--fp8-recipe mxfp8) with --tensor-model-parallel-size > 1")
+        self.fmt = fmt
+        self.grad_fmt = "e5m2" if fmt == "hybrid" else "e4m3"
+
+
+def mx_weight_q(weight):
+    """(q [out, in], s [out, in / 32], qT [in, out], sT [in, out / 32]) of W in E4M3, made once per
+    optimizer step (keyed like ``FP8State.weight_q``)."""
+    key = (weight.data_ptr(), weight._version, tuple(weight.shape), weight.dtype, _PARAMS_EPOCH[0])
+    hit = _MX_WQ.get(id(weight))
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    with torch.no_grad():
+        forms = SF.mx_quantize_weight(weight.detach())
+    _MX_WQ[id(weight)] = (key, forms)
+    return forms
+
+
+def _mx_rows(t, what, n_other):
+    t2 = t.reshape(-1, t.shape[-1])
+    if not t2.is_contiguous():
+        t2 = t2.contiguous()
+    if not SF.gemm_mx_supported(t2.shape[0], n_other, t2.shape[1]):
+        raise ValueError(f"MXFP8 linear: {what} has {t2.shape[0]} rows x {t2.shape[1]} columns against {n_other} "
+                         "on the other side; the block-scaled GEMM needs multiples of 128 in every dimension")
+    return t2
+
+
+class MXFP8Linear(torch.autograd.Function):
+    """y = x W^T (+ b) at TP = 1 with MXFP8 forward and dgrad GEMMs (see the section comment).
+    ``grad_fmt``: "e5m2" | "e4m3" for dY. ``bias`` always gets its gradient; ``add_bias`` False
+    leaves the addition to the caller (skip_bias_add)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, add_bias, grad_fmt):
+        ctx.grad_fmt = grad_fmt
+        ctx.has_bias = bias is not None
+        ctx.bias_p = bias
+        ctx.x_shape = x.shape
+        x2 = _mx_rows(x, "the input", weight.shape[0])
+        qx, sx = SF.mx_quantize(x2, "e4m3")
+        ctx.save_for_backward(x, weight)
+        qw, sw, _, _ = mx_weight_q(weight)
+        y = SF.gemm_mx(qx, sx, qw, sw, bias if (add_bias and bias is not None) else None, weight.dtype)
+        return y.view(tuple(x.shape[:-1]) + (weight.shape[0],))
+
+    @staticmethod
+    def backward(ctx, g):
+        x, weight = ctx.saved_tensors
+        g2 = _mx_rows(g, "the output gradient", weight.shape[1])
+        qg, sg = SF.mx_quantize(g2, ctx.grad_fmt)
+        _, _, qwt, swt = mx_weight_q(weight)
+        gi = SF.gemm_mx(qg, sg, qwt, swt, None, weight.dtype).view(ctx.x_shape)
+        dw, db = _wgrad_and_bias(weight, ctx.bias_p if ctx.has_bias else None, g2, x.reshape(-1, x.shape[-1]))
+        return gi, dw, db, None, None
+
+
+def attach_mxfp8(linears, recipe: MXFP8Recipe):
+    """Make each linear (Column / RowParallelLinear) an MXFP8 linear."""
+    for lin in linears:
+        object.__setattr__(lin, "_fp8", (recipe, 0))
 
 
 # fc1 + bias + GeLU(tanh) as ONE GEMM launch (gemm_tn.hip EPI_BIAS_GELU): the epilogue writes the
@@ -1911,6 +1997,8 @@ def linear_with_grad_accumulation_and_async_allreduce(x, weight, bias, sequence_
     if not bias_grad and (fp8 is not None or sequence_parallel):
         raise RuntimeError("bias_grad=False (the bias gradient from the consumer's kernel) is for the plain "
                            "16-bit linear at TP = 1")
+    if fp8 is not None and isinstance(fp8[0], MXFP8Recipe):     # from attach_mxfp8; TP = 1
+        return MXFP8Linear.apply(x, weight, bias, add_bias, fp8[0].grad_fmt)
     if fp8 is not None:                 # (FP8State, first table row) from attach_fp8; TP = 1
         return FP8Linear.apply(x, weight, bias, add_bias, fp8[0], fp8[1])
     if sequence_parallel and _TP_OVERLAP and _tp_size() > 1:

@@ -14,7 +14,9 @@ Front-end parity with /root/reference/3_training_megatron-lm/megatron/arguments.
 ``--fp8-amax-history-len``, ``--fp8-amax-compute-algo``) switch the four linears of every
 transformer layer to FP8 with delayed scaling (``TransformerConfig.fp8``); the weight gradient
 stays 16-bit unless ``--fp8-wgrad`` (ours, opt-in) puts it on the FP8 operands too
-(``TransformerConfig.fp8_wgrad``); the reference's ``--no-fp8-wgrad`` asks for what is the default here. Flags that only matter on NVIDIA stacks
+(``TransformerConfig.fp8_wgrad``); ``--fp8-recipe mxfp8`` (ours, Megatron-core's name, opt-in) runs
+those linears on OCP MX block scaling instead (``TransformerConfig.fp8_recipe``, no scaling state);
+the reference's ``--no-fp8-wgrad`` asks for what is the default here. Flags that only matter on NVIDIA stacks
 (``--transformer-impl``) are accepted and ignored; table-driven groups keep the list easy to
 audit against the reference.
 """
@@ -254,6 +256,8 @@ _GROUPS = {
     "transformer-engine": [
         ("--fp8-e4m3", dict(action="store_true")),
         ("--fp8-hybrid", dict(action="store_true")),
+        # block scaling instead of delayed scaling for those linears (Megatron-core's flag name)
+        ("--fp8-recipe", dict(default="delayed", choices=["delayed", "mxfp8"])),
         ("--no-fp8-wgrad", dict(action="store_false", dest="fp8_wgrad")),
         ("--fp8-margin", dict(type=int, default=0)),
         ("--fp8-interval", dict(type=int, default=1)),
@@ -459,6 +463,28 @@ def validate_args(args, defaults=None):
     # FP8 linears with delayed scaling (parallel/tensor_parallel.py FP8Linear)
     args.fp8 = None
     use_fp8_wgrad = bool(getattr(args, "use_fp8_wgrad", False))
+    if getattr(args, "fp8_recipe", "delayed") == "mxfp8":
+        # MXFP8 linears (tp.MXFP8Linear): what the block-scaled path cannot run, and the delayed-scaling
+        # knobs that would be silently inert under it, are refused here
+        why = None
+        if not (args.fp8_e4m3 or args.fp8_hybrid):
+            why = "needs the gradient format: add --fp8-hybrid (dY in E5M2) or --fp8-e4m3"
+        elif requested_tp > 1:
+            why = "with --tensor-model-parallel-size > 1 is not supported"
+        elif args.num_experts:
+            why = "with --num-experts is not supported (the Switch MLP stays 16-bit)"
+        elif use_fp8_wgrad:
+            why = "with --fp8-wgrad is not supported: the weight gradient stays 16-bit (MX needs token-direction blocks)"
+        else:
+            inert = [f for f, v, d in (("--fp8-margin", args.fp8_margin, 0), ("--fp8-interval", args.fp8_interval, 1),
+                                       ("--fp8-amax-history-len", args.fp8_amax_history_len, 1),
+                                       ("--fp8-amax-compute-algo", args.fp8_amax_compute_algo, "most_recent"))
+                     if v != d]
+            if inert:
+                why = "has no delayed scaling: " + " ".join(inert) + " would have no effect, drop " + \
+                      ("it" if len(inert) == 1 else "them")
+        if why:
+            raise ValueError(f"--fp8-recipe mxfp8 {why}")
     if use_fp8_wgrad and not args.fp8_wgrad:
         raise ValueError("--fp8-wgrad and --no-fp8-wgrad contradict each other: drop one")
     if use_fp8_wgrad and not (args.fp8_e4m3 or args.fp8_hybrid):
@@ -558,6 +584,11 @@ def validate_args(args, defaults=None):
         for name, v in dims:
             if v % 16:
                 raise ValueError(f"{flag} needs {name} to be a multiple of 16, got {v}")
+        if getattr(args, "fp8_recipe", "delayed") == "mxfp8":
+            for name, v in dims:
+                if v % 128:
+                    raise ValueError(f"--fp8-recipe mxfp8 needs {name} to be a multiple of 128 (the block-scaled "
+                                     f"GEMM's tile), got {v}")
         if use_fp8_wgrad and tokens % 64:
             raise ValueError("--fp8-wgrad needs --seq-length x --micro-batch-size (tokens per micro-batch) to be a "
                              f"multiple of 64 (the FP8 weight-gradient kernel's stage), got {tokens}")
@@ -611,7 +642,8 @@ def core_transformer_config_from_args(args) -> TransformerConfig:
         fp8_margin=getattr(args, "fp8_margin", 0),
         fp8_interval=getattr(args, "fp8_interval", 1),
         fp8_amax_history_len=getattr(args, "fp8_amax_history_len", 1),
-        fp8_amax_compute_algo=getattr(args, "fp8_amax_compute_algo", "most_recent"))
+        fp8_amax_compute_algo=getattr(args, "fp8_amax_compute_algo", "most_recent"),
+        fp8_recipe=getattr(args, "fp8_recipe", "delayed"))
 
 
 # ------------------------------------------------------------------------ micro-batch calculator (U2)
