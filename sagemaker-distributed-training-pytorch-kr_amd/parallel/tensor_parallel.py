@@ -311,6 +311,81 @@ def _cat_rows(ts):
     return torch.cat(ts)
 
 
+def _fire(params):
+    """Report to DDP that the gradients of ``params`` (entries may be None) are in their main_grad."""
+    for p in params:
+        cb = getattr(p, "_smdt_grad_ready", None) if p is not None else None
+        if cb is not None:
+            cb(p)
+
+
+def _wgrad_torch(mg, g2, t2, overwrite=False, bias_mg=None):
+    """One wgrad problem in torch (CPU, or no kernel took it): mg (+)= g2^T t2 and, with a bias
+    target, bias_mg += the column sums of g2."""
+    prod = g2.t().matmul(t2).view_as(mg)
+    (mg.copy_ if overwrite else mg.add_)(prod)
+    if bias_mg is not None:
+        bias_mg.add_(g2.float().sum(0))
+
+
+class _WgradItem:
+    """One queued weight gradient of ``DeferredWgrad``: main_grad (+)= g2^T t2 over its segments."""
+
+    __slots__ = ("weight", "main_grad", "bias", "segments", "held", "complete", "fresh", "scales", "mrange", "nbytes")
+
+    def __init__(self, weight, main_grad, bias, held, complete, fresh, scales, mrange):
+        self.weight = weight
+        self.main_grad = main_grad
+        self.bias = bias            # bias Parameter whose gradient comes out of the same launch, or None
+        self.segments = []          # one (g2, t2, g2._version, t2._version) per push, in push order
+        self.nbytes = 0             # dY / X bytes the segments keep alive
+        self.held = held            # created inside an accumulation window
+        self.complete = complete    # has its segment of the synchronising pass
+        self.fresh = fresh          # main_grad unwritten: the first GEMM into it stores
+        self.scales = scales        # FP8 item: (1 / scale of dY, 1 / scale of x), else None
+        self.mrange = mrange        # ranged item: (seg table, expert), else None
+
+    @property
+    def tiles(self):
+        """256 x 256 output tiles of the weight (what ``flush_tiles`` counts)."""
+        g2, t2 = self.segments[0][:2]
+        return -(-g2.shape[1] // 256) * -(-t2.shape[1] // 256)
+
+    def add(self, seg) -> int:
+        """Append a segment; returns its bytes."""
+        n = _nbytes(seg[0]) + _nbytes(seg[1])
+        self.segments.append(seg)
+        self.nbytes += n
+        return n
+
+    @property
+    def kind(self):
+        return "ranged" if self.mrange is not None else "fp8" if self.scales is not None else "16bit"
+
+    @property
+    def fillable(self):
+        """Whether an exchange-wait filler may issue the item: complete, not held for a later pass,
+        and 16-bit (FP8 and ranged items exist at TP = 1 only, so never beside a TP exchange)."""
+        return self.complete and not self.held and self.scales is None and self.mrange is None
+
+    @property
+    def one_cuda_segment(self):
+        """What the grouped filler (``fill_many``) asks on top of ``fillable``."""
+        return len(self.segments) == 1 and self.main_grad.is_cuda
+
+    def est_us(self, cus):
+        """Estimated GEMM time on ``cus`` CUs (0: the whole chip) at _FILL_PFLOPS, for the filler budget."""
+        g2, t2 = self.segments[0][:2]
+        fl = 2.0 * g2.shape[0] * g2.shape[1] * t2.shape[1] * len(self.segments)
+        return fl / (_FILL_PFLOPS * 1e9 * max(cus or 256, 1) / 256.0)
+
+    def check_versions(self):
+        for g2, t2, vg, vt in self.segments:
+            if g2._version != vg or t2._version != vt:
+                raise RuntimeError("deferred wgrad: a queued dY / X tensor was modified in place before the "
+                                   "flush; disable with SMDT_DEFER_WGRAD=0 and report the op that did it")
+
+
 class DeferredWgrad:
     """Deferred, grouped weight-gradient GEMMs.
 
@@ -370,10 +445,11 @@ class DeferredWgrad:
         self.merge_repeats = False
         self.ready_after_join = []      # filler-stream items waiting for their readiness report
         self.stats = {"flushes": 0, "items": 0, "max_segments": 0, "stores": 0}
-        self.items = []
-        self.by_key = {}
-        self.tiles = 0
-        self.held_bytes = 0
+        # membership: written by _add and _take only
+        self.items = []                 # _WgradItem, oldest first
+        self.by_key = {}                # main_grad.data_ptr() -> item
+        self.tiles = 0                  # sum of the items' tiles
+        self.held_bytes = 0             # sum of the items' nbytes
 
     @property
     def targets(self):
@@ -404,6 +480,24 @@ class DeferredWgrad:
             return int(0.25 * torch.cuda.mem_get_info(dev)[0])
         return 64 * 2 ** 30
 
+    def _add(self, it, seg):
+        """The one way in: a new item with its first segment, or one more segment of a queued item."""
+        self.held_bytes += it.add(seg)
+        if len(it.segments) == 1:
+            self.items.append(it)
+            self.by_key[it.main_grad.data_ptr()] = it
+            self.tiles += it.tiles
+
+    def _take(self, picks):
+        """The one way out: remove ``picks`` (queued items) from the queue and return them."""
+        ids ={id(it) for it in picks}
+        self.items = [it for it in self.items if id(it) not in ids]
+        for it in picks:
+            del self.by_key[it.main_grad.data_ptr()]
+            self.tiles -= it.tiles
+            self.held_bytes -= it.nbytes
+        return picks
+
     def push(self, weight, mg, g2, t2, bias=None, fresh=False, scales=None, mrange=None):
         """Queue mg += g2^T t2; ``bias`` (a bias Parameter with an fp32 main_grad, or None): its
         gradient, the column sums of g2, comes out of the same grouped launch. ``fresh``: mg holds
@@ -420,40 +514,28 @@ class DeferredWgrad:
                              "16-bit operands without scales")
         if self.hold_bytes_cap is None:
             self.hold_bytes_cap = self._hold_cap(g2.device)
-        key = mg.data_ptr()
         g2, t2 = g2.contiguous(), t2.contiguous()
-        seg = (g2, t2, g2._version, t2._version)
-        nbytes = g2.numel() * g2.element_size() + t2.numel() * t2.element_size()
-        it = self.by_key.get(key)
-        if it is not None and (mrange is not None or it[8] is not None):
+        it = self.by_key.get(mg.data_ptr())
+        if it is not None and (mrange is not None or it.mrange is not None):
             self.flush()            # ranged items never merge: the earlier gradient is issued first
             it = None
-        if it is not None and (it[3] or self.hold or self.merge_repeats):
+        if it is not None and (it.held or self.hold or self.merge_repeats):
             # the same main_grad again inside an accumulation window: merge (the sum over the
             # concatenated token range is the same accumulation; one readiness report)
-            it[2].append(seg)
-            it[4] = it[4] or not self.hold
+            it.complete = it.complete or not self.hold
         else:
             if it is not None:          # same main_grad twice outside a window: keep order
                 self.flush()
-            # [weight, main_grad, segments, held (created inside a window), has its segment of
-            # the synchronising pass, bias parameter or None, main_grad unwritten (store)]
-            # FP8 item: (1 / scale of dY, 1 / scale of x), else None]
-            # ranged item: (seg table, expert), else None]
-            it = [weight, mg, [seg], self.hold and mrange is None, not self.hold or mrange is not None, bias,
-                  bool(fresh), scales, mrange]
-            self.items.append(it)
-            self.by_key[key] = it
-            self.tiles += -(-g2.shape[1] // 256) * -(-t2.shape[1] // 256)
-        self.held_bytes += nbytes
+            it = _WgradItem(weight, mg, bias, held=self.hold and mrange is None, fresh=bool(fresh), scales=scales,
+                            mrange=mrange, complete=not self.hold or mrange is not None)
+        self._add(it, (g2, t2, g2._version, t2._version))
         if self.held_bytes > self.hold_bytes_cap:
             self.flush()
         elif not self.hold and not self.defer:
             # size trigger on what a flush would issue now (the complete items): held items still
             # waiting for this pass's gradient neither count nor flush
-            ready = [x for x in self.items if x[4]]
-            tiles = sum(-(-x[2][0][0].shape[1] // 256) * -(-x[2][0][1].shape[1] // 256) for x in ready)
-            if tiles >= self.flush_tiles or len(ready) >= 32:
+            ready = [x for x in self.items if x.complete]
+            if len(ready) >= 32 or sum(x.tiles for x in ready) >= self.flush_tiles:
                 self.flush(complete_only=True)
 
     def flush_opportunistic(self):
@@ -461,151 +543,117 @@ class DeferredWgrad:
         if not self.defer:
             self.flush()
 
-    @torch.no_grad()
     def flush(self, complete_only: bool = False):
         """Issue the queued GEMMs (one grouped launch) and report readiness. ``complete_only`` (the
         size-triggered flush of a synchronising pass): items of a held window whose weight has
         not yet received this pass's gradient stay queued to merge with it. A held item flushed
         without that gradient (a forced flush) accumulates but reports no readiness: the pass's
         own item for the weight does."""
-        if not self.items:
-            return
-        if complete_only:
-            items = [it for it in self.items if it[4]]
-            keep = [it for it in self.items if not it[4]]
-        else:
-            items, keep = self.items, []
-        if not items:
-            return
-        self.items = keep
-        self.by_key = {it[1].data_ptr(): it for it in keep}
-        self.tiles = sum(-(-it[2][0][0].shape[1] // 256) * -(-it[2][0][1].shape[1] // 256) for it in keep)
-        self.held_bytes = sum(sg[0].numel() * sg[0].element_size() + sg[1].numel() * sg[1].element_size()
-                              for it in keep for sg in it[2])
-        work = []
-        for weight, mg, segs, _held, complete, bias, fresh, scales, mrange in items:
-            for g2, t2, vg, vt in segs:
-                if g2._version != vg or t2._version != vt:
-                    raise RuntimeError("deferred wgrad: a queued dY / X tensor was modified in place before the "
-                                       "flush; disable with SMDT_DEFER_WGRAD=0 and report the op that did it")
-            if len(segs) == 1:
-                work.append((weight, mg, [(segs[0][0], segs[0][1])], complete, bias, fresh, scales, mrange))
-            elif self.concat_segments and _held:
-                work.append((weight, mg, [(_cat_rows([sg[0] for sg in segs]), _cat_rows([sg[1] for sg in segs]))],
-                             complete, bias, fresh, scales, mrange))
-            else:
-                work.append((weight, mg, [(sg[0], sg[1]) for sg in segs], complete, bias, fresh, scales, mrange))
-        self.stats["flushes"] += 1
-        self.stats["items"] += len(work)
-        self.stats["max_segments"] = max(self.stats["max_segments"], max(len(w[2]) for w in work))
-        # round i issues the i-th segment of every item: one grouped launch per round, so two
-        # segments of one main_grad never run in the same launch (no write race, no atomics)
-        for i in range(max(len(w[2]) for w in work)):
-            # round 0 of an unwritten main_grad stores (overwrite), later rounds add
-            rnd = [(mg, sg[i], b, fr and i == 0, sc, mr) for _, mg, sg, _, b, fr, sc, mr in work if len(sg) > i]
-            self.stats["stores"] += sum(1 for r in rnd if r[3])
-            # one launch for the round's 16-bit items and one for its FP8 items (wgrad_fp8.hip)
-            cuda = [(mg, g2, t2, b, ow, mr) for mg, (g2, t2), b, ow, sc, mr in rnd if g2.is_cuda and sc is None]
-            done = False
-            if cuda:
-                bts = [b.main_grad if b is not None else _NO_BIAS.get(g2.device) for _, g2, _, b, _, _ in cuda]
-                if any(c[5] is not None for c in cuda):      # ranged items: their own launch inside the call
-                    none = torch.empty(0, dtype=torch.int32, device=cuda[0][1].device)
-                    done = _ext.ext().wgrad_grouped(
-                        [c[0] for c in cuda], [c[1] for c in cuda], [c[2] for c in cuda], bts, [c[4] for c in cuda], 0,
-                        [c[5][0] if c[5] is not None else none for c in cuda],
-                        [int(c[5][1]) if c[5] is not None else 0 for c in cuda])
-                    if not done:
-                        raise RuntimeError("deferred wgrad: the grouped launch refused a queued ranged item")
-                else:
-                    done = _ext.ext().wgrad_grouped([c[0] for c in cuda], [c[1] for c in cuda], [c[2] for c in cuda],
-                                                    bts, [c[4] for c in cuda])
-            for fmt in _FP8_DTYPES:      # one MFMA opcode per launch: E5M2 and E4M3 dY apart
-                f8 = [(mg, g2, t2, sc, ow) for mg, (g2, t2), _, ow, sc, _ in rnd
-                      if g2.is_cuda and sc is not None and g2.dtype == fmt]
-                if f8 and not _ext.ext().wgrad_fp8_grouped([c[0] for c in f8], [c[1] for c in f8], [c[2] for c in f8],
-                                                           [c[3][0] for c in f8], [c[3][1] for c in f8],
-                                                           [c[4] for c in f8]):
-                    raise RuntimeError("deferred wgrad: the FP8 grouped launch refused a queued item")
-            for mg, (g2, t2), b, ow, sc, mr in rnd:
-                if mr is not None:
-                    if not (g2.is_cuda and done):      # the twin (CPU, or kernels disabled)
-                        SF.wgrad_ranged_ref(mg, g2, t2, mr[0], mr[1], b.main_grad if b is not None else None, ow)
-                    continue
-                if sc is not None:
-                    if not g2.is_cuda:       # CPU (tests: allow_cpu): the twin
-                        SF.fp8_wgrad_ref(mg, g2, t2, sc[0], sc[1], ow)
-                    continue
-                if not (g2.is_cuda and done):
-                    prod = g2.t().matmul(t2).view_as(mg)
-                    if ow:
-                        mg.copy_(prod)
-                    else:
-                        mg.add_(prod)
-                    if b is not None:
-                        b.main_grad.add_(g2.float().sum(0))
-        for weight, _, _, complete, b, _, _, _ in work:
-            if not complete:
-                continue
-            for p in (weight, b):
-                cb = getattr(p, "_smdt_grad_ready", None) if p is not None else None
-                if cb is not None:
-                    cb(p)
+        self._flush([it for it in self.items if it.complete] if complete_only else self.items)
 
+    def flush_unheld(self):
+        """Issue every queued item that is not held for a later synchronising pass."""
+        self._flush([it for it in self.items if not it.held])
 
     @torch.no_grad()
+    def _flush(self, items):
+        if not items:
+            return
+        for it in self._take(items):        # a failed version check has dropped what was taken
+            it.check_versions()
+            if len(it.segments) > 1 and self.concat_segments and it.held:
+                g2, t2 = _cat_rows([sg[0] for sg in it.segments]), _cat_rows([sg[1] for sg in it.segments])
+                it.segments = [(g2, t2, g2._version, t2._version)]
+        rounds = max(len(it.segments) for it in items)
+        self.stats["flushes"] += 1
+        self.stats["items"] += len(items)
+        self.stats["max_segments"] = max(self.stats["max_segments"], rounds)
+        # round i issues the i-th segment of every item: one grouped launch per round, so two
+        # segments of one main_grad never run in the same launch (no write race, no atomics);
+        # round 0 of an unwritten main_grad stores (overwrite), later rounds add
+        for i in range(rounds):
+            rnd = [(it, i, it.fresh and i == 0) for it in items if len(it.segments) > i]
+            self.stats["stores"] += sum(1 for r in rnd if r[2])
+            self._issue(rnd)
+        _fire(p for it in items if it.complete for p in (it.weight, it.bias))
+
+    @torch.no_grad()
+    def _issue(self, rnd, cus: int = 0, filler=None):
+        """Issue one round: ``rnd`` lists (item, segment index, overwrite), each item once, and the
+        launches are sized for ``cus`` CUs (0: the whole chip). ``filler``: None for a flush, where
+        torch takes over 16-bit problems that the grouped kernel declines; "grouped" / "blaslt" for
+        an exchange-wait filler (16-bit items only), where a declined launch is an error."""
+        ops = [(it, it.segments[i][0], it.segments[i][1], ow) for it, i, ow in rnd]
+        cuda = [op for op in ops if op[1].is_cuda]
+        # one launch for the round's 16-bit items, ranged ones included, and one for its FP8 items
+        c16 = [op for op in cuda if op[0].kind != "fp8"]
+        done = False
+        if c16 and filler == "blaslt":
+            # hipBLASLt beta = 1 into main_grad (its own non-persistent tiling shares the CUs
+            # with the transfer without a tail split) + the bias column sums
+            C = _ext.ext()
+            for it, g2, t2, ow in c16:
+                if ow:
+                    it.main_grad.zero_()
+                if not C.wgrad_accumulate(it.main_grad, g2, t2):
+                    raise RuntimeError("deferred wgrad filler: hipBLASLt wgrad refused")
+                if it.bias is not None:
+                    C.bias_grad(g2, it.bias.main_grad, True)
+            done = True
+        elif c16:
+            its, g2s, t2s, ows = map(list, zip(*c16))
+            dev = g2s[0].device
+            args = [[it.main_grad for it in its], g2s, t2s,
+                    [it.bias.main_grad if it.bias is not None else _NO_BIAS.get(dev) for it in its], ows, int(cus)]
+            ranged = any(it.mrange is not None for it in its)
+            if ranged:      # ranged items: their own launch inside the call
+                none = torch.empty(0, dtype=torch.int32, device=dev)
+                args += [[it.mrange[0] if it.mrange is not None else none for it in its],
+                         [int(it.mrange[1]) if it.mrange is not None else 0 for it in its]]
+            done = _ext.ext().wgrad_grouped(*args)
+            if not done and ranged:
+                raise RuntimeError("deferred wgrad: the grouped launch refused a queued ranged item")
+            if not done and filler:
+                raise RuntimeError("deferred wgrad filler: grouped launch refused")
+        for fmt in _FP8_DTYPES:      # one MFMA opcode per launch: E5M2 and E4M3 dY apart
+            f8 = [op for op in cuda if op[0].kind == "fp8" and op[1].dtype == fmt]
+            if f8:
+                its, g2s, t2s, ows = map(list, zip(*f8))
+                if not _ext.ext().wgrad_fp8_grouped([it.main_grad for it in its], g2s, t2s, [it.scales[0] for it in its],
+                                                    [it.scales[1] for it in its], ows):
+                    raise RuntimeError("deferred wgrad: the FP8 grouped launch refused a queued item")
+        for it, g2, t2, ow in ops:
+            if g2.is_cuda and (done or it.kind == "fp8"):
+                continue
+            # CPU (tests: allow_cpu), or kernels disabled: the twins and torch
+            bias_mg = it.bias.main_grad if it.bias is not None else None
+            if it.kind == "ranged":
+                SF.wgrad_ranged_ref(it.main_grad, g2, t2, it.mrange[0], it.mrange[1], bias_mg, ow)
+            elif it.kind == "fp8":
+                SF.fp8_wgrad_ref(it.main_grad, g2, t2, it.scales[0], it.scales[1], ow)
+            else:
+                _wgrad_torch(it.main_grad, g2, t2, ow, bias_mg)
+
+    def next_fillable(self):
+        """The oldest item an exchange-wait filler may issue, or None."""
+        return next((it for it in self.items if it.fillable), None)
+
     def fill_one(self, cus: int = 0) -> bool:
         """Exchange-wait filler (``fill``): issue the oldest queued, complete and not held item —
         ONE weight's gradient GEMM — as its own grouped launch sized for ``cus`` CUs (the ones an
         in-flight TP exchange leaves; its tail split into pieces that fill them), and report its
         readiness. Returns False when there was nothing to issue."""
-        # FP8 items (TP = 1 only, so never beside a TP exchange) are passed over: flush() issues them
-        pick = next((it for it in self.items if it[4] and not it[3] and it[7] is None and it[8] is None), None)
+        pick = self.next_fillable()
         if pick is None:
             return False
-        self.items = [it for it in self.items if it is not pick]
-        self.by_key.pop(pick[1].data_ptr(), None)
-        weight, mg, segs, _held, _complete, bias, fresh, _, _ = pick
-        self.tiles -= -(-segs[0][0].shape[1] // 256) * -(-segs[0][1].shape[1] // 256)
-        self.held_bytes -= sum(sg[0].numel() * sg[0].element_size() + sg[1].numel() * sg[1].element_size()
-                               for sg in segs)
-        for g2, t2, vg, vt in segs:
-            if g2._version != vg or t2._version != vt:
-                raise RuntimeError("deferred wgrad: a queued dY / X tensor was modified in place before the "
-                                   "flush; disable with SMDT_DEFER_WGRAD=0 and report the op that did it")
-        bt = bias.main_grad if bias is not None else _NO_BIAS.get(mg.device)
-        for i, (g2, t2, _, _) in enumerate(segs):      # segments in order: round 0 may store
-            ow = bool(fresh) and i == 0
-            if g2.is_cuda and _FILL_IMPL == "blaslt":
-                # hipBLASLt beta = 1 into main_grad (its own non-persistent tiling shares the CUs
-                # with the transfer without a tail split) + the bias column sums
-                C = _ext.ext()
-                if ow:
-                    mg.zero_()
-                if not C.wgrad_accumulate(mg, g2, t2):
-                    raise RuntimeError("deferred wgrad filler: hipBLASLt wgrad refused")
-                if bias is not None:
-                    C.bias_grad(g2, bias.main_grad, True)
-                continue
-            if g2.is_cuda:
-                if not _ext.ext().wgrad_grouped([mg], [g2], [t2], [bt], [ow], int(cus)):
-                    raise RuntimeError("deferred wgrad filler: grouped launch refused")
-                continue
-            prod = g2.t().matmul(t2).view_as(mg)       # CPU (tests: allow_cpu)
-            if ow:
-                mg.copy_(prod)
-            else:
-                mg.add_(prod)
-            if bias is not None:
-                bias.main_grad.add_(g2.float().sum(0))
+        self._take([pick])
+        pick.check_versions()
+        for i in range(len(pick.segments)):      # segments in order: round 0 may store
+            self._issue([(pick, i, pick.fresh and i == 0)], cus, "blaslt" if _FILL_IMPL == "blaslt" else "grouped")
         self.stats["fills"] = self.stats.get("fills", 0) + 1
-        for p in (weight, bias):
-            cb = getattr(p, "_smdt_grad_ready", None) if p is not None else None
-            if cb is not None:
-                cb(p)
+        _fire((pick.weight, pick.bias))
         return True
 
-    @torch.no_grad()
     def fill_many(self, budget_us: float, cus: int = 0, stream=None) -> int:
         """Exchange-wait filler, grouped form: the oldest queued, complete, not held, single-segment
         CUDA items up to ~``budget_us`` of estimated GEMM time (at least one) as ONE grouped launch
@@ -614,40 +662,27 @@ class DeferredWgrad:
         and ``fire_ready`` reports the items' readiness afterwards. Returns the items issued."""
         picks, spent = [], 0.0
         for it in self.items:
-            if not (it[4] and not it[3] and len(it[2]) == 1 and it[1].is_cuda) or it[7] is not None or it[8] is not None:
-                continue                    # FP8 and ranged items are passed over (see fill_one)
-            if picks and spent + _item_us(it, cus) > budget_us:
+            if not (it.fillable and it.one_cuda_segment):
+                continue
+            us = it.est_us(cus)
+            if picks and spent + us > budget_us:
                 break
             picks.append(it)
-            spent += _item_us(it, cus)
+            spent += us
             if spent >= budget_us:
                 break
         if not picks:
             return 0
-        ids = {id(it) for it in picks}
-        self.items = [it for it in self.items if id(it) not in ids]
-        for it in picks:
-            self.by_key.pop(it[1].data_ptr(), None)
-            g2, t2, vg, vt = it[2][0]
-            if g2._version != vg or t2._version != vt:
-                raise RuntimeError("deferred wgrad: a queued dY / X tensor was modified in place before the "
-                                   "flush; disable with SMDT_DEFER_WGRAD=0 and report the op that did it")
-            self.tiles -= -(-g2.shape[1] // 256) * -(-t2.shape[1] // 256)
-            self.held_bytes -= g2.numel() * g2.element_size() + t2.numel() * t2.element_size()
-        mgs = [it[1] for it in picks]
-        g2s = [it[2][0][0] for it in picks]
-        t2s = [it[2][0][1] for it in picks]
-        bts = [it[5].main_grad if it[5] is not None else _NO_BIAS.get(it[1].device) for it in picks]
-        ows = [bool(it[6]) for it in picks]
-        if stream is not None:
-            for t in g2s + t2s:
-                t.record_stream(stream)      # the queue drops them before the filler stream ran
-        if not _ext.ext().wgrad_grouped(mgs, g2s, t2s, bts, ows, int(cus)):
-            raise RuntimeError("deferred wgrad filler: grouped launch refused")
+        for it in self._take(picks):
+            it.check_versions()
+            if stream is not None:      # the queue drops them before the filler stream ran
+                it.segments[0][0].record_stream(stream)
+                it.segments[0][1].record_stream(stream)
+        self._issue([(it, 0, it.fresh) for it in picks], cus, "grouped")
         self.stats["fills"] = self.stats.get("fills", 0) + len(picks)
-        ready = [p for it in picks for p in (it[0], it[5]) if p is not None]
+        ready = [p for it in picks for p in (it.weight, it.bias) if p is not None]
         if stream is None:
-            self._fire(ready)
+            _fire(ready)
         else:
             self.ready_after_join.extend(ready)
         return len(picks)
@@ -655,30 +690,7 @@ class DeferredWgrad:
     def fire_ready(self):
         """Readiness of the items issued on the filler stream (after the caller joined it)."""
         ready, self.ready_after_join = self.ready_after_join, []
-        self._fire(ready)
-
-    @staticmethod
-    def _fire(params):
-        for p in params:
-            cb = getattr(p, "_smdt_grad_ready", None)
-            if cb is not None:
-                cb(p)
-
-    def flush_unheld(self):
-        """Issue every queued item that is not held for a later synchronising pass."""
-        if not any(not it[3] for it in self.items):
-            return
-        held = [it for it in self.items if it[3]]
-        if not held:
-            self.flush()
-            return
-        self.items = [it for it in self.items if not it[3]]
-        self.flush()
-        self.items = held + self.items
-        self.by_key = {it[1].data_ptr(): it for it in self.items}
-        self.tiles = sum(-(-it[2][0][0].shape[1] // 256) * -(-it[2][0][1].shape[1] // 256) for it in self.items)
-        self.held_bytes = sum(sg[0].numel() * sg[0].element_size() + sg[1].numel() * sg[1].element_size()
-                              for it in self.items for sg in it[2])
+        _fire(ready)
 
 
 DEFERRED_WGRAD = DeferredWgrad()
@@ -696,12 +708,6 @@ _FILL_US = float(os.environ.get("SMDT_W_FILL_US", "250" if _FILL_STREAM_ON else 
 _FILL_PFLOPS = 1.0
 _FILL_IMPL = os.environ.get("SMDT_W_FILL_IMPL", "grouped")     # "grouped" (MFMA, split tail) / "blaslt"
 _FILL = {"on": False}
-
-
-def _item_us(it, cus):
-    g2, t2 = it[2][0][0], it[2][0][1]
-    fl = 2.0 * g2.shape[0] * g2.shape[1] * t2.shape[1] * len(it[2])
-    return fl / (_FILL_PFLOPS * 1e9 * max(cus or 256, 1) / 256.0)
 
 
 # SMDT_W_FILL_STREAM (default 1, above): the fillers go to a stream of their own (joined at the end
@@ -722,10 +728,10 @@ def fill_exchange_wait():
     if not (_FILL["on"] and DEFERRED_WGRAD.items):
         return
     cus = gemm_tn_blocks()
-    it0 = next((x for x in DEFERRED_WGRAD.items if x[4] and not x[3] and x[7] is None), None)
-    if it0 is not None and it0[1].is_cuda and len(it0[2]) == 1:
+    it0 = DEFERRED_WGRAD.next_fillable()
+    if it0 is not None and it0.one_cuda_segment:
         if _FILL_STREAM_ON:
-            dev = it0[1].device
+            dev = it0.main_grad.device
             fs = _fill_stream(dev)
             fs.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(fs):
@@ -735,10 +741,10 @@ def fill_exchange_wait():
         return
     spent = 0.0
     while spent < _FILL_US:
-        it = next((x for x in DEFERRED_WGRAD.items if x[4] and not x[3] and x[7] is None), None)
+        it = DEFERRED_WGRAD.next_fillable()
         if it is None:
             return
-        spent += _item_us(it, cus)
+        spent += it.est_us(cus)
         DEFERRED_WGRAD.fill_one(cus)
 
 
@@ -833,7 +839,18 @@ def accumulate_wgrad(mg, g2, t2):
         if not done:
             done = C.wgrad_accumulate(mg, g2, t2)
     if not done:
-        mg.add_(g2.t().matmul(t2).view_as(mg))
+        _wgrad_torch(mg, g2, t2)
+
+
+def _wgrad_target(weight):
+    """(mg, claim) for a weight's gradient GEMM: ``mg`` its fp32 main_grad or None, ``claim()``
+    whether the first GEMM into mg stores — call it only when the item is pushed. Of a lazily
+    zeroed ZeRO-2 buffer (distributed.py) mg is the raw slice, which ``claim`` may find still
+    unwritten; a GEMM that runs now goes to ``weight.main_grad`` instead, which zeroes it."""
+    raw = getattr(weight, "_smdt_mg_raw", None)
+    if raw is not None:
+        return raw(), weight._smdt_mg_claim
+    return getattr(weight, "main_grad", None), bool      # bool() is False: nothing to claim
 
 
 def _wgrad(weight, g2, t2):
@@ -842,19 +859,14 @@ def _wgrad(weight, g2, t2):
     (``DeferredWgrad``), or ONE GEMM now (the MFMA kernel or hipBLASLt with beta = 1) instead of a
     bf16 GEMM + a separate fp32 add pass. Returns the gradient to hand back to autograd (None
     when it goes to ``main_grad``)."""
-    raw = getattr(weight, "_smdt_mg_raw", None)     # lazily zeroed ZeRO-2 buffer (distributed.py)
-    mg = raw() if raw is not None else getattr(weight, "main_grad", None)
+    mg, claim = _wgrad_target(weight)
     if mg is None:
         return g2.t().matmul(t2)
     if DEFERRED_WGRAD.eligible(mg, g2, t2):
-        DEFERRED_WGRAD.push(weight, mg, g2, t2, fresh=raw is not None and weight._smdt_mg_claim())
+        DEFERRED_WGRAD.push(weight, mg, g2, t2, fresh=claim())
         return None
-    if raw is not None:
-        mg = weight.main_grad                          # zeroes the slice if it is still unwritten
-    accumulate_wgrad(mg, g2, t2)
-    cb = getattr(weight, "_smdt_grad_ready", None)
-    if cb is not None:
-        cb(weight)
+    accumulate_wgrad(weight.main_grad, g2, t2)
+    _fire((weight,))
     return None
 
 
@@ -897,12 +909,10 @@ def _wgrad_and_bias(weight, bias_p, g2, t2):
     """(dW, db) for autograd: dW = g2^T t2 and db = sum_rows g2, each None when it went straight
     into the parameter's fp32 main_grad (queued, or by a kernel now)."""
     if bias_p is not None and _WGRAD_BIAS and g2.is_cuda:
-        raw = getattr(weight, "_smdt_mg_raw", None)
-        mg = raw() if raw is not None else getattr(weight, "main_grad", None)
+        mg, claim = _wgrad_target(weight)
         tgt = SF.grad_accumulate_target(bias_p)
         if mg is not None and tgt is not None and tgt.numel() == g2.shape[-1] and DEFERRED_WGRAD.eligible(mg, g2, t2):
-            DEFERRED_WGRAD.push(weight, mg, g2, t2, bias=bias_p,
-                                fresh=raw is not None and weight._smdt_mg_claim())
+            DEFERRED_WGRAD.push(weight, mg, g2, t2, bias=bias_p, fresh=claim())
             return None, None
     dw = _wgrad(weight, g2, t2)
     return dw, (_bias_grad(bias_p, g2) if bias_p is not None else None)
@@ -1352,21 +1362,15 @@ class FP8Linear(torch.autograd.Function):
 def _fp8_wgrad(weight, qg, qx, inv_dy, inv_x):
     """dW = dequant(q(dY)^T q(x)) as ``_wgrad`` does it for 16-bit operands: queued for the FP8
     grouped launch, or one launch into ``main_grad`` now, or (no main_grad) returned to autograd."""
-    raw = getattr(weight, "_smdt_mg_raw", None)     # lazily zeroed ZeRO-2 buffer (distributed.py)
-    mg = raw() if raw is not None else getattr(weight, "main_grad", None)
+    mg, claim = _wgrad_target(weight)
     if mg is None:
         dw = torch.empty(qg.shape[1], qx.shape[1], dtype=torch.float32, device=qg.device)
         return SF.fp8_wgrad(dw, qg, qx, inv_dy, inv_x, overwrite=True).to(weight.dtype)
     if DEFERRED_WGRAD.eligible(mg, qg, qx):
-        DEFERRED_WGRAD.push(weight, mg, qg, qx, fresh=raw is not None and weight._smdt_mg_claim(),
-                            scales=(inv_dy, inv_x))
+        DEFERRED_WGRAD.push(weight, mg, qg, qx, fresh=claim(), scales=(inv_dy, inv_x))
         return None
-    if raw is not None:
-        mg = weight.main_grad                          # zeroes the slice if it is still unwritten
-    SF.fp8_wgrad(mg.view(qg.shape[1], qx.shape[1]), qg, qx, inv_dy, inv_x)
-    cb = getattr(weight, "_smdt_grad_ready", None)
-    if cb is not None:
-        cb(weight)
+    SF.fp8_wgrad(weight.main_grad.view(qg.shape[1], qx.shape[1]), qg, qx, inv_dy, inv_x)
+    _fire((weight,))
     return None
 
 
@@ -1619,21 +1623,18 @@ def _wgrad_ranged(weight, bias_p, g2, t2, seg, e, kern):
     """(dW, db) of expert e for autograd, each None when it went into the fp32 main_grad: queued as
     a ranged item (``DeferredWgrad``) or, on the twin without a main_grad, computed from the host
     copy of the segment (None for an expert without tokens)."""
+    # not _wgrad_target: a ranged item only accumulates, so a lazily zeroed buffer is zeroed here
     mg = getattr(weight, "main_grad", None)
     bmg = getattr(bias_p, "main_grad", None)
     if mg is not None and bmg is not None and mg.dtype == torch.float32 and bmg.dtype == torch.float32:
-        q = DEFERRED_WGRAD
-        if q.eligible(mg, g2, t2):
-            q.push(weight, mg, g2, t2, bias=bias_p, mrange=(seg, e))
+        if DEFERRED_WGRAD.eligible(mg, g2, t2):
+            DEFERRED_WGRAD.push(weight, mg, g2, t2, bias=bias_p, mrange=(seg, e))
             return None, None
         if kern:
             SF.wgrad_ranged(mg, g2, t2, seg, e, bmg)
         else:
             SF.wgrad_ranged_ref(mg, g2, t2, seg, e, bmg)
-        for p in (weight, bias_p):
-            cb = getattr(p, "_smdt_grad_ready", None)
-            if cb is not None:
-                cb(p)
+        _fire((weight, bias_p))
         return None, None
     if kern:
         raise RuntimeError("--moe-grouped-gemm: the experts' weights and biases need an fp32 main_grad")
@@ -2922,9 +2923,7 @@ class _EmbeddingLookup(torch.autograd.Function):
         mg = getattr(w, "main_grad", None)
         if mg is not None and mg.dtype == torch.float32:
             mg.index_add_(0, flat, g2)
-            cb = getattr(w, "_smdt_grad_ready", None)
-            if cb is not None:
-                cb(w)
+            _fire((w,))
             return None, None
         dw = torch.zeros(w.shape, dtype=torch.float32, device=g.device)
         dw.index_add_(0, flat, g2)
@@ -2950,9 +2949,7 @@ class _AddPositionSlice(torch.autograd.Function):
         mg = getattr(w, "main_grad", None)
         if mg is not None and mg.dtype == torch.float32:
             mg[start:start + s].add_(gs)
-            cb = getattr(w, "_smdt_grad_ready", None)
-            if cb is not None:
-                cb(w)
+            _fire((w,))
             return g, None, None
         dw = torch.zeros(w.shape, dtype=torch.float32, device=g.device)
         dw[start:start + s] = gs

@@ -197,7 +197,7 @@ def test_deferred_queue_merges_fp8_segments(queue, concat):
     queue.push(w, mg, a[0], a[1], scales=a[2])
     queue.hold = False
     queue.push(w, mg, b[0], b[1], scales=b[2])
-    assert len(queue.items) == 1 and len(queue.items[0][2]) == 2
+    assert len(queue.items) == 1 and len(queue.items[0].segments) == 2
     queue.flush()
     assert queue.stats["max_segments"] == (1 if concat else 2)
     torch.testing.assert_close(mg, a[3] + b[3], atol=1e-5, rtol=1e-5)

@@ -225,6 +225,75 @@ def test_deferred_wgrad_queue_semantics(monkeypatch):
     assert ready[-1] is b and not q.items
 
 
+def test_deferred_wgrad_counters_follow_membership():
+    """DeferredWgrad's tiles / held_bytes / by_key stay the sums over its items through every way in
+    and out: push, a merge inside a window, the size-triggered flush of the complete items,
+    fill_one, fill_many, flush_unheld beside held items and a flush that raises."""
+    from smdt_amd.parallel import tensor_parallel as tp
+    q = tp.DeferredWgrad()
+    q.allow_cpu = True
+    q.flush_tiles = 3
+    torch.manual_seed(2)
+    ready, want = [], {}
+
+    def mk(o, i):
+        w = torch.nn.Parameter(torch.randn(o, i))
+        w.main_grad = torch.zeros(o, i)
+        w._smdt_grad_ready = lambda p: ready.append(p)
+        want[w] = torch.zeros(o, i)
+        return w
+
+    def push(w, tokens):
+        g, x = torch.randn(tokens, w.shape[0]), torch.randn(tokens, w.shape[1])
+        want[w] += g.t() @ x
+        q.push(w, w.main_grad, g, x)
+        return g
+
+    def check(*queued):
+        assert [id(it.weight) for it in q.items] == [id(w) for w in queued]
+        assert q.tiles == sum(it.tiles for it in q.items)
+        assert q.held_bytes == sum(t.numel() * t.element_size() for it in q.items for sg in it.segments for t in sg[:2])
+        assert set(q.by_key) == {it.main_grad.data_ptr() for it in q.items} == q.targets
+
+    a, b, c, h = mk(16, 8), mk(1024, 64), mk(8, 8), mk(1024, 64)      # 1, 4, 1 and 4 tiles
+    push(a, 64)
+    check(a)
+    q.hold = True                   # a window: h is created held, a (queued before it) takes a segment
+    push(h, 32)
+    push(h, 64)
+    push(a, 32)
+    check(a, h)
+    assert [len(it.segments) for it in q.items] == [2, 2] and q.tiles == 5
+    q.hold = False                  # a + b are 5 complete tiles >= 3: they flush, h waits for its pass
+    push(b, 128)
+    check(h)
+    assert ready == [a, b]
+    q.defer = True                  # no size trigger: the fillers' turn
+    for w in (a, b, c):
+        push(w, 64)
+    check(h, a, b, c)
+    assert q.fill_one() and ready == [a, b, a] and q.stats["fills"] == 1
+    check(h, b, c)
+    assert q.fill_many(1e9) == 0    # the grouped filler takes CUDA items only
+    check(h, b, c)
+    q.flush_unheld()
+    check(h)
+    assert ready == [a, b, a, b, c]
+    g = push(a, 64)
+    g.mul_(2)
+    with pytest.raises(RuntimeError, match="modified in place"):
+        q.flush(complete_only=True)
+    check(h)                        # the failed flush dropped what it took, nothing else
+    want.pop(a)
+    push(h, 96)                     # h's own pass; defer keeps it queued
+    check(h)
+    q.flush()
+    check()
+    assert ready == [a, b, a, b, c, h] and q.tiles == 0 and q.held_bytes == 0
+    for w, ref in want.items():
+        torch.testing.assert_close(w.main_grad, ref, atol=2e-4, rtol=1e-4)   # fp32 summation order
+
+
 def test_deferred_wgrad_accumulation_window_merges(monkeypatch):
     """DeferredWgrad.hold (the ZeRO engine's gradient-accumulation window): nothing flushes during
     the window, every weight's micro-batch GEMMs merge into ONE product over the concatenated
@@ -248,7 +317,7 @@ def test_deferred_wgrad_accumulation_window_merges(monkeypatch):
     q.hold = True
     for g, x in zip(gs[:3], xs[:3]):
         tp._wgrad(w, g, x)
-    assert not ready and len(q.items) == 1 and len(q.items[0][2]) == 3
+    assert not ready and len(q.items) == 1 and len(q.items[0].segments) == 3
     q.hold = False                   # the boundary micro-batch
     tp._wgrad(w, gs[3], xs[3])       # merges, then the size threshold flushes the window at once
     assert ready == [w] and not q.items and calls == [4, 4]

@@ -221,7 +221,7 @@ def test_merged_accumulation_window_wgrad_matches_per_microbatch():
         segs = []
 
         def flush(self, _orig=orig_flush, _segs=segs):
-            _segs.extend(len(it[2]) for it in self.items)
+            _segs.extend(len(it.segments) for it in self.items)
             return _orig(self)
         type(q).flush = flush
         try:
