@@ -61,6 +61,9 @@ def main():
                         "(the step's ~1.5-3.7 k kernel launches leave the device idle 5-42 ms per step "
                         "in eager mode, profiles/r4_vision/); the augmented batch is copied into the "
                         "graph's static input")
+    p.add_argument("--fused-window-attn", type=int, default=0, choices=[0, 1],
+                   help="Swin models: 1 = the fused window-attention kernel (csrc/kernels/window_attn.hip) "
+                        "instead of the batched-GEMM op chain")
     p.add_argument("--optim", default="smdt", choices=["smdt", "torch"],
                    help="smdt: the hand-written fused Adam (optim.hip, device-side step count: "
                         "capturable) over the DDP's flat buffers; torch: torch.optim.Adam(fused)")
@@ -103,7 +106,7 @@ def main():
     dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
     torch.manual_seed(0)
     torch.backends.cudnn.benchmark = True
-    model = zoo.create(a.model)
+    model = zoo.create(a.model, **({"fused_window_attention": True} if a.fused_window_attn else {}))
     zoo.reset_classifier(model, a.num_classes)
     mf = torch.channels_last if (a.channels_last and dev.type == "cuda") else torch.contiguous_format
     bucket = int(a.bucket_mb * 2 ** 20 / 4) if a.bucket_mb > 0 else "auto"
@@ -223,6 +226,7 @@ def main():
                        "optimizer": "smdt fused Adam (optim.hip)" if a.optim == "smdt" and a.ddp == "smdt" else "torch Adam (fused)",
                        "augment": "prefetched (side stream)" if a.prefetch else "in line",
                        "hip_graph": graph_note,
+                       "fused_window_attn": a.fused_window_attn,
                        "backend": dist.get_backend() if dist.is_initialized() else None,
                        "ddp_bucket": {"elements": model.bucket_size, "count": len(model.buckets),
                                       "MB": round(model.bucket_size * 4 / 2 ** 20, 2)} if a.ddp == "smdt" else None},

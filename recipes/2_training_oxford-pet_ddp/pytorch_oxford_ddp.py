@@ -75,6 +75,9 @@ def args_fn(argv=None):
     parser.add_argument("--graph", type=str2bool, default=False,
                         help="capture the training step (forward, backward with the DDP bucket reductions, the "
                              "hand-written fused Adam) in a HIP graph and replay it (smdt_amd/train/graphs.py)")
+    parser.add_argument("--fused-window-attn", type=str2bool, default=False,
+                        help="Swin models: run the attention core between the qkv and proj linears as one "
+                             "fused HIP kernel (csrc/kernels/window_attn.hip); same parameters and checkpoints")
     return parser.parse_args(argv)
 
 
@@ -122,7 +125,14 @@ def _get_test_data_loader(args):
 def train(args):
     best_acc1 = -1
     model_history = util.init_modelhistory({})
-    model = util.torch_model(args.model_name, num_classes=args.num_classes, pretrained=args.pretrained)
+    model_kwargs = {}
+    if args.fused_window_attn:
+        if args.model_name.startswith("swin"):
+            model_kwargs["fused_window_attention"] = True
+        else:
+            print("=> --fused-window-attn ignored: '{}' is not a Swin model".format(args.model_name))
+    model = util.torch_model(args.model_name, num_classes=args.num_classes, pretrained=args.pretrained,
+                             **model_kwargs)
     dev = args.device
     mf = torch.channels_last if (args.channels_last and dev.type == "cuda") else torch.contiguous_format
     model = model.to(dev, memory_format=mf)

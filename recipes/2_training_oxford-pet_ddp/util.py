@@ -26,11 +26,11 @@ logger.setLevel(logging.DEBUG)
 logger.addHandler(logging.StreamHandler(sys.stdout))
 
 
-def torch_model(model_name, num_classes=0, pretrained=True):
+def torch_model(model_name, num_classes=0, pretrained=True, **model_kwargs):
     from smdt_amd.models import zoo
     if model_name == "inception_v3":
         raise RuntimeError("Currently, inception_v3 is not supported by this example.")
-    model = zoo.create(model_name)
+    model = zoo.create(model_name, **model_kwargs)
     if pretrained:
         d = os.environ.get("SMDT_PRETRAINED_DIR", "")
         path = os.path.join(d, f"{model_name}.pth") if d else ""

@@ -932,6 +932,66 @@ const int* fa_doc_ptr(const OptT& d, const Tensor& q, const char* n) {
   return d->data_ptr<int>();
 }
 
+// ------------------------------------------------------------------ Swin window attention
+// qkv [B, ph, pw, 3 heads d] on the padded, unrolled grid; table fp32 [(2 ws - 1)^2, heads].
+// Everything the kernel does not take is refused here, before any launch.
+struct WaDims { int B, ph, pw, heads, ws, shift; int64_t C, nW, N, E; };
+static WaDims wa_check(const Tensor& qkv, const Tensor& table, int64_t window, int64_t shift, int64_t heads) {
+  need_contig(qkv, "qkv");
+  need_contig(table, "table");
+  TORCH_CHECK(qkv.dim() == 4, "window_attn: qkv must be [B, ph, pw, 3 C]");
+  TORCH_CHECK(qkv.scalar_type() == at::kBFloat16 || qkv.scalar_type() == at::kHalf,
+              "window_attn: qkv must be bf16 or fp16, got ", qkv.scalar_type());
+  TORCH_CHECK(heads > 0 && qkv.size(3) % (3 * heads) == 0, "window_attn: last dim is not (3, heads, d)");
+  const int64_t d = qkv.size(3) / (3 * heads);
+  TORCH_CHECK(window > 0 && window < 1024 && qkv.numel() > 0 && qkv.size(1) < (1 << 20) && qkv.size(2) < (1 << 20),
+              "window_attn: bad shape");
+  TORCH_CHECK(smdt_window_attn_supported(dcode(qkv), (int)d, (int)window, (int)qkv.size(1), (int)qkv.size(2),
+                                         (int)shift),
+              "window_attn: unsupported (needs d == 32, window <= 8, ph and pw multiples of the window, "
+              "0 <= shift < window): d ", d, ", window ", window, ", grid ", qkv.size(1), " x ", qkv.size(2),
+              ", shift ", shift);
+  WaDims w{(int)qkv.size(0), (int)qkv.size(1), (int)qkv.size(2), (int)heads, (int)window, (int)shift,
+           heads * d, (qkv.size(1) / window) * (qkv.size(2) / window), window * window,
+           (2 * window - 1) * (2 * window - 1)};
+  TORCH_CHECK(table.scalar_type() == at::kFloat && table.dim() == 2 && table.size(0) == w.E &&
+                  table.size(1) == heads && table.device() == qkv.device(),
+              "window_attn: table must be fp32 [(2 window - 1)^2, heads] on qkv's device");
+  return w;
+}
+
+std::vector<Tensor> window_attn_fwd(Tensor qkv, Tensor table, int64_t window, int64_t shift, int64_t heads) {
+  const WaDims w = wa_check(qkv, table, window, shift, heads);
+  auto out = torch::empty({w.B, w.ph, w.pw, w.C}, qkv.options());
+  auto lse = torch::empty({w.B, w.nW, w.heads, w.N}, qkv.options().dtype(at::kFloat));
+  check(smdt_window_attn_fwd(dcode(qkv), qkv.data_ptr(), table.data_ptr<float>(), out.data_ptr(),
+                             lse.data_ptr<float>(), w.B, w.ph, w.pw, w.heads, w.ws, w.shift, cur_stream()),
+        "window_attn_fwd");
+  return {out, lse};
+}
+
+// -> dqkv (qkv's shape and dtype), dtable (fp32, table's shape)
+std::vector<Tensor> window_attn_bwd(Tensor qkv, Tensor table, Tensor lse, Tensor dout, int64_t window,
+                                    int64_t shift, int64_t heads) {
+  const WaDims w = wa_check(qkv, table, window, shift, heads);
+  need_contig(lse, "lse");
+  need_contig(dout, "dout");
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.numel() == (int64_t)w.B * w.nW * w.heads * w.N &&
+                  lse.device() == qkv.device(), "window_attn_bwd: lse must be fp32 [B, nW, heads, N]");
+  TORCH_CHECK(dout.scalar_type() == qkv.scalar_type() && dout.dim() == 4 && dout.size(0) == w.B &&
+                  dout.size(1) == w.ph && dout.size(2) == w.pw && dout.size(3) == w.C &&
+                  dout.device() == qkv.device(), "window_attn_bwd: dout must be [B, ph, pw, C] of qkv's dtype");
+  auto dqkv = torch::empty_like(qkv);
+  auto f32 = qkv.options().dtype(at::kFloat);
+  auto partials = torch::empty({(int64_t)w.B * w.nW, w.E * w.heads}, f32);
+  auto dtable = torch::empty({w.E, (int64_t)w.heads}, f32);
+  check(smdt_window_attn_bwd(dcode(qkv), qkv.data_ptr(), table.data_ptr<float>(), lse.data_ptr<float>(),
+                             dout.data_ptr(), dqkv.data_ptr(), partials.data_ptr<float>(),
+                             dtable.data_ptr<float>(), w.B, w.ph, w.pw, w.heads, w.ws, w.shift, cur_stream()),
+        "window_attn_bwd");
+  return {dqkv, dtable};
+}
+
 // `out` (optional) is a preallocated [B, S, H, D] view with any strides (e.g. the [s, b, h]
 // activation layout used by the transformer trunk). `doc_start` (optional, causal only) selects the
 // per-document kernels.
@@ -1300,6 +1360,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("wgrad_fp8_grouped", &wgrad_fp8_grouped, arg("main_grads"), arg("dys"), arg("xs"), arg("inv_dys"),
         arg("inv_xs"), arg("overwrite") = std::vector<bool>{}, arg("cus") = 0);
   m.def("wgrad_fp8_supported", &wgrad_fp8_supported);
+  m.def("window_attn_fwd", &window_attn_fwd, arg("qkv"), arg("table"), arg("window"), arg("shift"), arg("heads"));
+  m.def("window_attn_bwd", &window_attn_bwd, arg("qkv"), arg("table"), arg("lse"), arg("dout"), arg("window"),
+        arg("shift"), arg("heads"));
   m.def("ce_stats", &ce_stats);
   m.def("set_rng_step", &set_rng_step);
   m.def("adam_capturable", &adam_capturable);

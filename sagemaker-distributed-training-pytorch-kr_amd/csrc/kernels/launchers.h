@@ -150,6 +150,20 @@ hipError_t smdt_flash_bwd_sums(int dtype, const void* q, const void* k, const vo
                                float scale, int causal, float dropout_p, uint64_t seed, uint64_t offset,
                                const int* doc_start, const int* doc_end, float* colpart, hipStream_t st);
 
+// window_attn.hip: Swin shifted-window attention on the qkv linear's output over the padded,
+// unrolled grid, qkv [B, ph, pw, 3 heads d] read as (3, heads, d); roll, window partition and head
+// split are address arithmetic. table: fp32 [(2 ws - 1)^2, heads]. out [B, ph, pw, heads d] at the
+// unrolled positions, lse fp32 [B, nW, heads, ws^2]. Supported: bf16 / fp16, d == 32, ws <= 8,
+// ph and pw multiples of ws, 0 <= shift < ws; anything else returns hipErrorInvalidValue unlaunched.
+int smdt_window_attn_supported(int dtype, int d, int ws, int ph, int pw, int shift);
+hipError_t smdt_window_attn_fwd(int dtype, const void* qkv, const float* table, void* out, float* lse, int B,
+                                int ph, int pw, int heads, int ws, int shift, hipStream_t st);
+// partials: fp32 scratch [B nW, (2 ws - 1)^2 heads] (one row per window, summed by smdt_col_sum
+// into dtable, fp32 [(2 ws - 1)^2, heads]); dqkv as qkv, every element written.
+hipError_t smdt_window_attn_bwd(int dtype, const void* qkv, const float* table, const float* lse,
+                                const void* dout, void* dqkv, float* partials, float* dtable, int B, int ph,
+                                int pw, int heads, int ws, int shift, hipStream_t st);
+
 // gemm_tn.hip: C[M, N] = A[M, K] . B[N, K]^T (16-bit in / out, fp32 accumulate) with an epilogue:
 // epi 0 none, 1 + bias[n], 2 C = pre-activation and C2 = gelu_tanh(C + bias[n]) (bias_gelu fusion),
 // 3 C = product * gelu_tanh'(aux + bias[n]) (fc2 dgrad + GeLU backward; aux = pre-activation [M, N]).

@@ -6,7 +6,9 @@ image, so the architecture is implemented here with torchvision's parameter name
 MI355X layout choices: activations stay channels-last [B, H, W, C] end to end (the natural Swin
 layout; no NCHW<->NHWC permutes between blocks), LayerNorms run on the fused HIP LN kernel, window
 attention (49 tokens) is a batched bf16 GEMM pair on hipBLASLt with the additive relative-position
-bias + shift mask folded into one precomputed [nW, heads, 49, 49] bias per stage.
+bias + shift mask folded into one precomputed [nW, heads, 49, 49] bias per stage. With
+``fused_window_attention=True`` (opt-in) the attention core between the qkv and proj linears is one
+fused HIP kernel instead (csrc/kernels/window_attn.hip); parameters and state dicts are the same.
 """
 from __future__ import annotations
 
@@ -56,8 +58,13 @@ def _rel_index(ws: int) -> torch.Tensor:
 
 
 class ShiftedWindowAttention(nn.Module):
-    def __init__(self, dim: int, window: int, shift: int, num_heads: int, attention_dropout=0.0, dropout=0.0):
+    def __init__(self, dim: int, window: int, shift: int, num_heads: int, attention_dropout=0.0, dropout=0.0,
+                 fused: bool = False):
         super().__init__()
+        if fused and attention_dropout > 0:
+            raise ValueError("fused window attention has no attention dropout: use fused=False or "
+                             "attention_dropout=0")
+        self.fused = fused
         self.window, self.shift, self.num_heads = window, shift, num_heads
         self.attention_dropout, self.dropout = attention_dropout, dropout
         self.qkv = nn.Linear(dim, dim * 3)
@@ -97,6 +104,12 @@ class ShiftedWindowAttention(nn.Module):
         x = F.pad(x, (0, 0, 0, pr, 0, pb))
         ph, pw = H + pb, W + pr
         shift = 0 if (ws >= ph and ws >= pw) else self.shift
+        if self.fused:
+            # the qkv linear is per token, so it runs on the unrolled grid; roll, window partition and
+            # head split are the kernel's address arithmetic (ops.functional.window_attention)
+            x = SF.window_attention(self.qkv(x), self.relative_position_bias_table, ws, shift, self.num_heads)
+            x = F.dropout(self.proj(x), p=self.dropout, training=self.training)
+            return x[:, :H, :W, :].contiguous()
         if shift > 0:
             x = torch.roll(x, shifts=(-shift, -shift), dims=(1, 2))
         nW = (ph // ws) * (pw // ws)
@@ -125,10 +138,11 @@ class MLP(nn.Sequential):
 
 class SwinTransformerBlock(nn.Module):
     def __init__(self, dim, num_heads, window, shift, mlp_ratio=4.0, dropout=0.0, attention_dropout=0.0,
-                 stochastic_depth_prob=0.0):
+                 stochastic_depth_prob=0.0, fused_window_attention=False):
         super().__init__()
         self.norm1 = LayerNorm(dim, eps=1e-5)
-        self.attn = ShiftedWindowAttention(dim, window, shift, num_heads, attention_dropout, dropout)
+        self.attn = ShiftedWindowAttention(dim, window, shift, num_heads, attention_dropout, dropout,
+                                           fused=fused_window_attention)
         self.sd = stochastic_depth_prob
         self.norm2 = LayerNorm(dim, eps=1e-5)
         self.mlp = MLP(dim, int(dim * mlp_ratio), dropout)
@@ -163,7 +177,7 @@ class Permute(nn.Module):
 class SwinTransformer(nn.Module):
     def __init__(self, embed_dim=96, depths=(2, 2, 6, 2), num_heads=(3, 6, 12, 24), window_size=7,
                  patch_size=4, mlp_ratio=4.0, dropout=0.0, attention_dropout=0.0, stochastic_depth_prob=0.1,
-                 num_classes=1000):
+                 num_classes=1000, fused_window_attention=False):
         super().__init__()
         layers: List[nn.Module] = [nn.Sequential(
             nn.Conv2d(3, embed_dim, kernel_size=patch_size, stride=patch_size), Permute([0, 2, 3, 1]),
@@ -176,7 +190,8 @@ class SwinTransformer(nn.Module):
             for j in range(depth):
                 sd = stochastic_depth_prob * bid / max(total - 1, 1)
                 stage.append(SwinTransformerBlock(dim, num_heads[i], window_size, 0 if j % 2 == 0 else window_size // 2,
-                                                  mlp_ratio, dropout, attention_dropout, sd))
+                                                  mlp_ratio, dropout, attention_dropout, sd,
+                                                  fused_window_attention))
                 bid += 1
             layers.append(nn.Sequential(*stage))
             if i < len(depths) - 1:

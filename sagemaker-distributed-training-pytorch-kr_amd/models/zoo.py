@@ -12,11 +12,15 @@ def available():
     return _resnet.available() + _swin.available() + ["mnist_cnn"]
 
 
-def create(name: str, num_classes: int = 1000) -> nn.Module:
+def create(name: str, num_classes: int = 1000, **model_kwargs) -> nn.Module:
+    """``model_kwargs`` go to the model's constructor (e.g. ``fused_window_attention=True`` for the
+    Swin models); a model that takes none refuses them."""
+    if name in _swin.available():
+        return _swin.swin(name, num_classes=num_classes, **model_kwargs)
+    if model_kwargs:
+        raise TypeError(f"model '{name}' takes no keyword arguments, got {sorted(model_kwargs)}")
     if name in _resnet.available():
         return _resnet.resnet(name, num_classes=num_classes)
-    if name in _swin.available():
-        return _swin.swin(name, num_classes=num_classes)
     if name == "mnist_cnn":
         return MnistNet()
     raise ValueError(f"unknown model '{name}'; available: {available()}")

@@ -677,6 +677,96 @@ def flash_attention_qkv(qkv, nh: int, nkv: int, hd: int, seq_first: bool = True,
 
 
 # --------------------------------------------------------------------------------------------
+# Swin shifted-window attention on the qkv linear's output over the padded, unrolled grid.
+#
+# Window (wy, wx) token (iy, ix) is rolled coordinate (y, x) = (wy ws + iy, wx ws + ix); it is read
+# from and written to source coordinate ((y + shift) mod ph, (x + shift) mod pw). The shift mask's
+# region of a rolled coordinate is 0 for y < ph - ws, 1 for y < ph - shift, else 2 (same in x), id
+# 3 ry + rx: the image ShiftedWindowAttention._bias paints. window_attn.hip computes the same
+# mapping as address arithmetic; window_attention_ref is its statement in torch ops.
+
+
+def window_attention_map(ph: int, pw: int, window: int, shift: int, device=None):
+    """(src, region), both int64 [nW, N]: the flat index into the [ph * pw] token grid of every
+    window token, and its shift-mask region id."""
+    ws = window
+    ar = lambda n, *shape: torch.arange(n, device=device).view(*shape)  # noqa: E731
+    y = (ar(ph // ws, -1, 1, 1, 1) * ws + ar(ws, 1, 1, -1, 1)).expand(ph // ws, pw // ws, ws, ws)
+    x = (ar(pw // ws, 1, -1, 1, 1) * ws + ar(ws, 1, 1, 1, -1)).expand(ph // ws, pw // ws, ws, ws)
+    src = ((y + shift) % ph) * pw + (x + shift) % pw
+    ry = (y >= ph - ws).long() + (y >= ph - shift).long()
+    rx = (x >= pw - ws).long() + (x >= pw - shift).long()
+    return src.reshape(-1, ws * ws), (3 * ry + rx).reshape(-1, ws * ws)
+
+
+def window_attention_ref(qkv, table, window: int, shift: int, num_heads: int):
+    """Torch twin of the fused kernel: qkv [B, ph, pw, 3 C] read as (3, heads, d), table
+    [(2 ws - 1)^2, heads] -> [B, ph, pw, C] at the unrolled positions. Gather by computed source
+    coordinates, scores and softmax in fp32 (float64 for float64 operands)."""
+    B, ph, pw, C3 = qkv.shape
+    ws, N, C = window, window * window, C3 // 3
+    d = C // num_heads
+    if ph % ws or pw % ws or C3 != 3 * num_heads * d or not 0 <= shift < ws:
+        raise ValueError(f"window_attention: grid {ph} x {pw}, window {ws}, shift {shift}, last dim {C3}, "
+                         f"heads {num_heads} do not fit")
+    ct = torch.float64 if qkv.dtype == torch.float64 else torch.float32
+    src, region = window_attention_map(ph, pw, ws, shift, qkv.device)
+    nW = src.shape[0]
+    x = qkv.reshape(B, ph * pw, 3, num_heads, d)[:, src.flatten()].view(B, nW, N, 3, num_heads, d)
+    q, k, v = (t.permute(0, 1, 3, 2, 4).to(ct) for t in x.unbind(3))                # [B, nW, h, N, d]
+    t = torch.arange(N, device=qkv.device)
+    c = (t // ws) * (2 * ws - 1) + t % ws
+    idx = c[:, None] - c[None, :] + 2 * ws * (ws - 1)
+    s = q.matmul(k.transpose(-2, -1)) * d ** -0.5 + table.to(ct)[idx].permute(2, 0, 1)
+    if shift > 0:
+        s = s + (region[:, :, None] != region[:, None, :]).to(ct).mul(-100.0)[None, :, None]
+    o = torch.softmax(s, dim=-1).matmul(v).permute(0, 1, 3, 2, 4).reshape(B, nW * N, C).to(qkv.dtype)
+    return o[:, torch.argsort(src.flatten())].view(B, ph, pw, C)
+
+
+def window_attention_supported(qkv, window: int, shift: int, num_heads: int) -> bool:
+    """The shapes window_attn.hip takes (smdt_window_attn_supported in launchers.h)."""
+    if qkv.dim() != 4 or qkv.dtype not in (torch.bfloat16, torch.float16) or num_heads <= 0:
+        return False
+    B, ph, pw, C3 = qkv.shape
+    if not (C3 == 96 * num_heads and 1 <= window <= 8 and ph >= window and pw >= window and ph % window == 0
+            and pw % window == 0 and 0 <= shift < window and qkv.numel() > 0):
+        return False
+    # the binding's and the launcher's size limits: grid sides below 2^20, at most 2^30 (window, head) waves
+    return ph < 2 ** 20 and pw < 2 ** 20 and B * (ph // window) * (pw // window) * num_heads <= 2 ** 30
+
+
+class _WindowAttn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, table, window, shift, heads):
+        tf = table.detach().float().contiguous()
+        qkv = qkv.contiguous()
+        out, lse = _ext.ext().window_attn_fwd(qkv, tf, window, shift, heads)
+        ctx.save_for_backward(qkv, tf, lse)
+        ctx.args = (window, shift, heads, table.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, tf, lse = ctx.saved_tensors
+        window, shift, heads, tdtype = ctx.args
+        dqkv, dtable = _ext.ext().window_attn_bwd(qkv, tf, lse, dout.contiguous(), window, shift, heads)
+        return dqkv, dtable.to(tdtype), None, None, None
+
+
+def window_attention(qkv, table, window: int, shift: int, num_heads: int):
+    """Shifted-window attention core of a Swin block (no dropout): see window_attention_ref for the
+    semantics. bf16 / fp16 GPU operands of a supported shape run the fused HIP kernels (under
+    autocast an fp32 qkv is cast to the autocast dtype first); the CPU, SMDT_DISABLE_KERNELS=1 and
+    every other dtype or shape run the torch twin."""
+    if qkv.is_cuda and qkv.dtype == torch.float32 and torch.is_autocast_enabled():
+        qkv = qkv.to(torch.get_autocast_gpu_dtype())
+    if window_attention_supported(qkv, window, shift, num_heads) and _ext.use_kernels(qkv):
+        return _WindowAttn.apply(qkv, table, window, shift, num_heads)
+    return window_attention_ref(qkv, table, window, shift, num_heads)
+
+
+# --------------------------------------------------------------------------------------------
 # Rotary embedding
 
 
