@@ -1,6 +1,6 @@
 """Flash-attention microbenchmark: smdt_amd HIP kernels vs torch SDPA on the same random data.
 
-python benchmarks/bench_attention.py [--b 16 --h 16 --s 1024 --d 64 --causal 1]
+python benchmarks/bench_attention.py [--b 16 --h 16 --s 1024 --d 64 --causal 1 --dtype bf16|fp16]
 Reports fwd / bwd times and TFLOP/s (causal FLOPs counted as half of the dense 4*B*H*S^2*D).
 
 --doc-len N: per-document attention (``doc_start``) with a document boundary every N tokens
@@ -87,6 +87,7 @@ def main():
     p.add_argument("--causal", type=int, default=1)
     p.add_argument("--sdpa", type=int, default=1)
     p.add_argument("--dropout", type=float, default=0.0)
+    p.add_argument("--dtype", choices=["bf16", "fp16"], default="bf16")
     p.add_argument("--ext", default=None, help="alternate _C.so for A/B runs")
     p.add_argument("--doc-len", type=int, default=0,
                    help="per-document attention with a boundary every N tokens, next to plain causal")
@@ -95,14 +96,15 @@ def main():
     B, H, S, D = a.b, a.h, a.s, a.d
     Hkv = a.hkv or H
     torch.manual_seed(0)
-    q = torch.randn(B, S, H, D, device="cuda", dtype=torch.bfloat16, requires_grad=True)
-    k = torch.randn(B, S, Hkv, D, device="cuda", dtype=torch.bfloat16, requires_grad=True)
-    v = torch.randn(B, S, Hkv, D, device="cuda", dtype=torch.bfloat16, requires_grad=True)
-    do = torch.randn(B, S, H, D, device="cuda", dtype=torch.bfloat16)
+    dt = torch.float16 if a.dtype == "fp16" else torch.bfloat16
+    q = torch.randn(B, S, H, D, device="cuda", dtype=dt, requires_grad=True)
+    k = torch.randn(B, S, Hkv, D, device="cuda", dtype=dt, requires_grad=True)
+    v = torch.randn(B, S, Hkv, D, device="cuda", dtype=dt, requires_grad=True)
+    do = torch.randn(B, S, H, D, device="cuda", dtype=dt)
     flops = 4 * B * H * S * S * D * (0.5 if a.causal else 1.0)
     if a.doc_len > 0:
         return doc_compare(a, q, k, v, do)
-    res = {"shape": [B, S, H, Hkv, D], "causal": bool(a.causal), "dropout": a.dropout}
+    res = {"shape": [B, S, H, Hkv, D], "dtype": a.dtype, "causal": bool(a.causal), "dropout": a.dropout}
 
     def ours_f():
         return SF.flash_attention(q, k, v, 1 / math.sqrt(D), bool(a.causal), dropout_p=a.dropout)

@@ -470,19 +470,33 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fwd_kernel(const E* __re
       };
       scores();
       // Lazy reference max without a per-tile row max: p = exp2(S - m) is taken straight away and
-      // m only moves when the row's tile sum leaves [2^-64, 2^64] (p that large or small is still
-      // exact in fp32 / bf16, l and O have range to spare) — too large (or not finite), or, before
-      // anything was accumulated, so small that the row could underflow. Wave-uniform branch
-      // (ballot); rare: it recomputes the tile's scores (the K tile is still in LDS), takes the
-      // exact row max, rescales and redoes the exponentials. Saves the ~21 max instructions per
-      // tile of a per-tile max (the loop is VALU-issue-bound).
+      // m only moves when the row's tile sum leaves the window [kSumLo, kSumHi] — too large (or not
+      // finite), or, before anything was accumulated, too small. Wave-uniform branch (ballot);
+      // rare: it recomputes the tile's scores (the K tile is still in LDS), takes the exact row
+      // max, rescales and redoes the exponentials. Saves the ~21 max instructions per tile of a
+      // per-tile max (the loop is VALU-issue-bound).
+      // The window is a function of E, because p goes to the P.V MFMA as E:
+      //   * bf16 has fp32's exponent range: [2^-64, 2^64]; p that large or small is still exact,
+      //     l and O have range to spare.
+      //   * fp16 holds 2^-24 .. 65504 and only 2^-14 and up at full precision: [2^0, 2^15]. Every p
+      //     is at most its tile sum, so p <= 2^15 is finite in fp16. The first tile a row
+      //     accumulates has a sum >= 1 over 64 keys, so the row's largest p is >= 2^-6 from then on
+      //     (later tiles only add to it): a p within 2^-8 of the row's largest is a normal fp16,
+      //     and a p flushed to zero is below 2^-18 of it (2^-24 with a true row max; either is far
+      //     below the 2^-11 rounding of the largest). A window that only kept p non-zero, e.g.
+      //     2^-14, leaves the whole row in fp16's subnormals (tests/_numerics.py, profile
+      //     fp16_subnormal: 10 to 20 times the allowed error in the tile-by-tile twin).
+      //     randn-like scores (|S| of a few units) stay inside [2^0, 2^15]: only a causal row
+      //     with one or two visible keys asks for the rescue, on its first tile.
+      constexpr bool kHalf = std::is_same_v<E, f16>;
+      constexpr float kSumLo = kHalf ? 0x1p0f : 0x1p-64f, kSumHi = kHalf ? 0x1p15f : 0x1p64f;
       float rsum = expsum();
       // DOC: a row whose document starts past this tile has every score at -inf here (rsum = 0
       // with l = 0): it must neither ask for the rescue nor move m (tmax = -inf would make
       // alpha = exp2(+inf) and 0 * inf = NaN). Such a row keeps d = 0 below; every other visited
       // tile holds at least the row's own key or its document's first key, as in the plain kernel.
       const bool dead = DOC && kb + kTile <= ds_q;
-      const bool bad = !dead && (!(rsum <= 0x1p64f) || (l == 0.f && rsum < 0x1p-64f));
+      const bool bad = !dead && (!(rsum <= kSumHi) || (l == 0.f && rsum < kSumLo));
       if (__builtin_amdgcn_ballot_w64(bad) != 0) {
         scores();
         float tmax = st[0][0];
@@ -492,7 +506,10 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fwd_kernel(const E* __re
           for (int i = 0; i < 16; ++i) tmax = fmaxf(tmax, st[tt][i]);
         tmax = xhalf_max(tmax);
         const float d = bad ? tmax : 0.f;
-        const float alpha = fexp2(-d);
+        // Nothing accumulated yet (l == 0, o == 0): nothing to rescale. A downward move past
+        // 2^-128 would otherwise make alpha = exp2(-d) = inf and l, o = 0 * inf = NaN. (With l > 0
+        // a bad row only ever moves up: d > 0, alpha < 1.)
+        const float alpha = l > 0.f ? fexp2(-d) : 1.f;
         l *= alpha;
 #pragma unroll
         for (int dt = 0; dt < G::DT; ++dt) o[dt] *= alpha;

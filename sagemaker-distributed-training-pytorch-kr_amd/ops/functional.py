@@ -529,7 +529,8 @@ def flash_dropout_keep_mask(B: int, H: int, S: int, p: float, seed: int, offset:
 
 
 def attention_ref(q, k, v, scale, causal, dropout_p: float = 0.0, keep=None, doc_start=None):
-    """Reference attention on [B, S, H, D] (GQA by head repetition), fp32 math. ``keep``
+    """Reference attention on [B, S, H, D] (GQA by head repetition), fp32 math (float64 for float64
+    inputs). ``keep``
     ([B, H, S, S] bool) is the dropout keep-mask (``flash_dropout_keep_mask``). ``doc_start``
     (int32 [B, S], causal only) also masks keys before the query's document: block-diagonal causal."""
     if q.is_cuda and os.environ.get("SMDT_ASSERT_FLASH") == "1":
@@ -539,7 +540,8 @@ def attention_ref(q, k, v, scale, causal, dropout_p: float = 0.0, keep=None, doc
     if Hkv != H:
         k = k.repeat_interleave(H // Hkv, dim=2)
         v = v.repeat_interleave(H // Hkv, dim=2)
-    qf, kf, vf = (t.float().transpose(1, 2) for t in (q, k, v))
+    wd = torch.float64 if q.dtype == torch.float64 else torch.float32   # float64 in, float64 math (tests)
+    qf, kf, vf = (t.to(wd).transpose(1, 2) for t in (q, k, v))
     s = torch.matmul(qf, kf.transpose(-1, -2)) * scale
     if causal:
         cm = torch.ones(S, S, dtype=torch.bool, device=q.device).triu(1)

@@ -395,3 +395,339 @@ def vp_lmce_two_shards(h, w, tgt, dl, vocab=0, ranks=2, local_pass=None):
         dh += (e.float() @ w[r * vl:(r + 1) * vl].float()) * rr
         dws.append(e.float().t() @ (x.float() * rr).to(h.dtype).float())
     return loss.view(tgt.shape), dh.view(h.shape), torch.cat(dws), torch.cat(lgs, -1)
+
+
+# --------------------------------------------------------------------------- flash attention
+#
+# Scores that move the forward kernel's lazy reference max. flash_attn.hip's forward takes
+# p = exp2(S - m) with m = 0 and moves m (the "rescue") only when a row's 64-key tile sum leaves a
+# window; randn inputs (scores ~ N(0, 1)) never get there. ``flash_score_case`` puts a chosen level
+# on every (query, key tile) through one reserved channel of the head dim, ``flash_lazy_max_twin``
+# follows the forward tile by tile in torch (fp32, the kernel's rounding points and move rule, with
+# mutations), and ``flash_kernel_emulation`` is float64 attention with only the three kernels'
+# 16-bit rounding points: the yardstick the GPU tests judge the kernels against.
+
+FLASH_SCALE = 0.125          # passed explicitly for D = 64 and D = 128: the offsets stay exact
+FLASH_TILE = 64              # kTile: keys per tile of the forward sweep
+_LOG2E_F32 = 1.4426950408889634
+# Move-rule windows (log2 of the tile sum) of fwd_kernel per type; FLASH_WINDOW_PARENT is the one
+# every type shared before the fp16 fix (kept for the CPU record of the defect).
+FLASH_WINDOW_PARENT = (-64, 64)
+FLASH_WINDOWS = {torch.bfloat16: (-64, 64), torch.float16: (0, 15)}
+
+# name -> (natural-log level per key tile for a query with qa = 16 (cycled past 4 tiles), qa values
+# of even / odd queries). A query with qa = 0 sees plain scores, so the lanes of a wave disagree.
+FLASH_PROFILES = {
+    "plain": ((0, 0, 0, 0), (0, 16)),                  # control
+    "up_late": ((0, 50, 100, 50), (0, 16)),            # upward rescue after l > 0, twice; causal diagonal too
+    "low_start": ((-60, -60, -30, -30), (0, 16)),      # downward rescue with l == 0
+    "very_low": ((-100, -100, -100, -100), (0, 16)),   # tmax < -128 (log2): alpha = exp2(-tmax) = inf
+    "very_low_first": ((-100, 0, 0, 0), (0, 16)),      # ... and real mass afterwards
+    "fp16_high": ((20, 20, 20, 20), (0, 16)),          # inside the bf16 window, above fp16's maximum
+    "fp16_low": ((-25, -25, -25, -25), (0, 16)),       # inside the bf16 window, below fp16's minimum
+    # p = exp2(S) ~ 2^-20 is finite and non-zero in fp16 but a subnormal with 4 bits: a lower window
+    # bound that only keeps p away from zero is not enough (this profile sets fp16's lower bound)
+    "fp16_subnormal": ((-14, -14, -14, -14), (0, 16)),
+    # odd queries rise as in up_late while even queries fall: at the tile where the odd lanes ask
+    # for the rescue the even lanes hold l > 0 and tmax < -128 (moving them would overflow l)
+    "opposed": ((0, 50, 100, 50), (-16, 16)),
+}
+
+
+def flash_score_case(profile, B=2, S=256, H=2, Hkv=2, D=64, dtype=torch.bfloat16, device="cpu", seed=31):
+    """q, k, v, do ([B, S, heads, D], ``dtype``) whose scores (with scale FLASH_SCALE) carry the
+    profile's level per 64-key tile: channel 0 holds qa[q] (a power of two, or 0) in q and
+    kb[k] = level / (FLASH_SCALE * 16) (a multiple of 1/2) in k, both exact in bf16 and fp16, so the
+    added score FLASH_SCALE * qa * kb is exact; the other channels are randn scaled to an O(1)
+    score contribution, so the keys of a plateau differ and no row is degenerate."""
+    levels, qa_vals = FLASH_PROFILES[profile]
+    g = torch.Generator().manual_seed(seed)
+    q = torch.randn(B, S, H, D, generator=g) * (8.0 / D ** 0.5)
+    k = torch.randn(B, S, Hkv, D, generator=g)
+    v = torch.randn(B, S, Hkv, D, generator=g)
+    do = torch.randn(B, S, H, D, generator=g)
+    ar = torch.arange(S)
+    qa = torch.where(ar % 2 == 1, float(qa_vals[1]), float(qa_vals[0]))
+    lv = torch.tensor([levels[(t // FLASH_TILE) % len(levels)] for t in range(S)], dtype=torch.float32)
+    kb = lv / (FLASH_SCALE * 16.0)
+    q[..., 0] = qa[None, :, None]
+    k[..., 0] = kb[None, :, None]
+    out = tuple(t.to(dtype).to(device) for t in (q, k, v, do))
+    assert torch.equal(out[1][..., 0].float().cpu(), kb[None, :, None].expand(B, S, Hkv)), "kb not exact"
+    return out
+
+
+def _bhsd(t, H, wd):
+    """[B, S, heads, D] -> [B, H, S, D] in ``wd`` (kv heads repeated for GQA)."""
+    t = t.detach().to(wd).transpose(1, 2)
+    return t if t.shape[1] == H else t.repeat_interleave(H // t.shape[1], dim=1)
+
+
+def _flash_masked(B, S, causal, doc_start, device):
+    """bool [B, 1, S, S], True = masked (key after the query / before the query's document)."""
+    ar = torch.arange(S, device=device)
+    m = torch.zeros(B, 1, S, S, dtype=torch.bool, device=device)
+    if causal:
+        m = m | (ar[None, :] > ar[:, None])
+    if doc_start is not None:
+        m = m | (ar[None, None, :] < doc_start.to(device)[:, :, None].long()).unsqueeze(1)
+    return m
+
+
+def flash_ref(q, k, v, do, scale, causal, dropout_p=0.0, keep=None, doc_start=None):
+    """float64 attention on the given 16-bit inputs: o and the three gradients from
+    ``attention_ref`` on ``.double()`` copies, lse = logsumexp of the masked scores. [B, S, heads, D];
+    lse [B, H, S]."""
+    from smdt_amd.ops import functional as SF
+    qd, kd, vd = (t.detach().double().requires_grad_() for t in (q, k, v))
+    o = SF.attention_ref(qd, kd, vd, scale, causal, dropout_p, keep, doc_start)
+    assert o.dtype == torch.float64
+    o.backward(do.detach().double())
+    B, S, H, _ = q.shape
+    s = torch.matmul(_bhsd(q, H, torch.float64), _bhsd(k, H, torch.float64).transpose(-1, -2)) * scale
+    s = s.masked_fill(_flash_masked(B, S, causal, doc_start, q.device), float("-inf"))
+    return {"o": o.detach(), "lse": torch.logsumexp(s, -1), "dq": qd.grad, "dk": kd.grad, "dv": vd.grad}
+
+
+def _drop_consts(dropout_p):
+    """(1 / (1 - p_realised), 1 - p_realised, fp32 log2 of the first) as the launcher makes them."""
+    if not dropout_p:
+        return 1.0, 1.0, 0.0
+    from smdt_amd.ops import functional as SF
+    thr, inv = SF.flash_dropout_thr(dropout_p)
+    import math
+    return float(torch.tensor(inv, dtype=torch.float32)), float(torch.tensor((128.0 - thr) / 128.0, dtype=torch.float32)), \
+        float(torch.tensor(math.log2(inv), dtype=torch.float32))
+
+
+def flash_kernel_emulation(q, k, v, do, scale, causal, dropout_p=0.0, keep=None, doc_start=None, m_ref=None):
+    """float64 attention, forward and backward, with only the rounding points of flash_attn.hip in
+    the inputs' 16-bit type T (a true row max, no window; ``m_ref``, [B, H, S] in the log2 domain,
+    replaces the row max as the point P is rounded at, see ``flash_emulation_at_kernel_max``):
+      * forward and dQ kernel: Q' = T(q * scale * log2 e) (fp32 product), scores Q' K^T in the log2
+        domain; the dK / dV kernel prescales K instead: scores Q K'^T with K' = T(k * scale * log2 e);
+      * forward: P = exp2(S - max) rounded to T before P V (l sums the unrounded, undropped p),
+        O = T(P V / l / (1 - p)), lse = fp32 (max + log2 l) ln 2;
+      * backward: P' = exp2(S - lse log2 e + log2 inv) from the forward's lse (fp32 row constant),
+        delta' = keep * sum(dO O) from the stored 16-bit O; P' (dV) and dS = P' (dP - delta') (dQ,
+        dK) rounded to T; dQ = T(scale dS K), dK = T(scale dS^T Q), dV = T(P'^T dO), the kv heads'
+        groups summed before the rounding.
+    Returns o, lse, dq, dk, dv like ``flash_ref``."""
+    T, f64 = q.dtype, torch.float64
+    B, S, H, D = q.shape
+    Hkv = k.shape[2]
+    c2 = torch.tensor(scale, dtype=torch.float32) * torch.tensor(_LOG2E_F32, dtype=torch.float32)
+    inv, keepf, log2inv = _drop_consts(dropout_p)
+    Q, K, V, DO = (_bhsd(t, H, f64) for t in (q, k, v, do))
+    Qp = _bhsd((q.float() * c2).to(T), H, f64)
+    Kp = _bhsd((k.float() * c2).to(T), H, f64)
+    masked = _flash_masked(B, S, causal, doc_start, q.device)
+    kp = torch.ones((), dtype=f64, device=q.device) if keep is None else keep.to(f64)
+    sq = torch.matmul(Qp, K.transpose(-1, -2)).masked_fill(masked, float("-inf"))
+    sk = torch.matmul(Q, Kp.transpose(-1, -2)).masked_fill(masked, float("-inf"))
+    m = sq.amax(-1, keepdim=True) if m_ref is None else m_ref.to(f64)[..., None]
+    p = torch.exp2(sq - m)
+    l = p.sum(-1, keepdim=True)
+    O = (torch.matmul(p.to(T).to(f64) * kp, V) * (inv / l)).to(T)
+    lse = ((m + torch.log2(l)) * 0.6931471805599453).float()[..., 0]
+    nlse2 = (log2inv - lse * torch.tensor(_LOG2E_F32, dtype=torch.float32)).to(f64)[..., None]
+    delta = keepf * (O.to(f64) * DO).sum(-1, keepdim=True)
+    dP = torch.matmul(DO, V.transpose(-1, -2)) * (kp if keep is not None else 1.0)
+    Pq, Pk = torch.exp2(sq + nlse2), torch.exp2(sk + nlse2)
+    dSq = (Pq * (dP - delta)).to(T).to(f64)
+    dSk = (Pk * (dP - delta)).to(T).to(f64)
+    dq = (torch.matmul(dSq, K) * scale).to(T)
+    dk = torch.matmul(dSk.transpose(-1, -2), Q).view(B, Hkv, H // Hkv, S, D).sum(2)
+    dv = torch.matmul((Pk.to(T).to(f64) * kp).transpose(-1, -2), DO).view(B, Hkv, H // Hkv, S, D).sum(2)
+    return {"o": O.transpose(1, 2), "lse": lse, "dq": dq.transpose(1, 2), "dk": (dk * scale).to(T).transpose(1, 2),
+            "dv": dv.to(T).transpose(1, 2)}
+
+
+def flash_emulation_at_kernel_max(q, k, v, do, scale, causal, dropout_p=0.0, keep=None, doc_start=None):
+    """``flash_kernel_emulation`` with P rounded where the kernel rounds it: at the lazy reference
+    max the forward ends with (``flash_lazy_max_twin``'s m, 0 for a row that never asked for the
+    rescue), not at the row max. With a true max the row's largest p is exactly 1 and survives the
+    rounding to T; at the lazy m it is some 2^x that rounds by up to half an ulp while l sums the
+    unrounded p, so O of a row with one dominant key is off by that half ulp, and delta = sum(dO O)
+    no longer cancels dP in dS = P (dP - delta): a causal row 0 (one key, exact dq = 0) gets a dq of
+    ~2^-9 |dO . v| |k| in bf16. That is rounding of the design, not a defect; the GPU tests measure
+    the kernels against this emulation."""
+    T, S = q.dtype, q.shape[1]
+    qp, kp, vp, dsp = q, k, v, doc_start
+    if S % 128:       # the launcher pads a causal sequence at its end (pad rows: a document of their own)
+        assert causal and keep is None
+        pad = lambda t: torch.nn.functional.pad(t, (0, 0, 0, 0, 0, -S % 128))
+        qp, kp, vp = pad(q), pad(k), pad(v)
+        if doc_start is not None:
+            dsp = torch.cat([doc_start, doc_start.new_full((doc_start.shape[0], -S % 128), S)], 1)
+    m = flash_lazy_max_twin(qp, kp, vp, scale, causal, T, FLASH_WINDOWS[T], dsp, keep, None, dropout_p,
+                            return_m=True)[2][..., :S]
+    return flash_kernel_emulation(q, k, v, do, scale, causal, dropout_p, keep, doc_start, m_ref=m)
+
+
+FLASH_MUTATIONS = ("no_o_rescale", "no_l_rescale", "lse_without_m", "rescue_ignores_mask", "select_all_lanes")
+
+
+def flash_lazy_max_twin(q, k, v, scale, causal, dtype, window, doc_start=None, keep=None, mutate=None,
+                        dropout_p=0.0, alpha_guard=True, return_m=False):
+    """fwd_kernel of flash_attn.hip in torch, tile by tile, in fp32: 64-key tiles, Q prescaled by
+    scale * log2 e and rounded to ``dtype``, m = 0 at the start and p = exp2(S - m) taken at once;
+    a row is "bad" when its tile sum is above 2^window[1] (or not finite) or, with l == 0, below
+    2^window[0]; a 32-row wave with a bad row recomputes the tile, and d = bad ? tile max : 0 moves
+    m and rescales l and o by alpha = exp2(-d). p is rounded to ``dtype`` (and dropped with ``keep``)
+    before P V; l sums the unrounded, undropped p. ``alpha_guard`` False is the rule before the fix
+    (alpha is applied even where nothing was accumulated: 0 * inf). The causal / DOC tile skips and
+    masks are the kernel's (wave- and block-uniform). ``mutate`` (FLASH_MUTATIONS) breaks one step
+    of the rescue. Returns o ([B, S, H, D], ``dtype``) and lse (fp32 [B, H, S]); ``return_m`` adds the
+    final reference max m (log2 domain, [B, H, S])."""
+    assert mutate is None or mutate in FLASH_MUTATIONS, mutate
+    f32, T = torch.float32, dtype
+    B, S, H, D = q.shape
+    dev = q.device
+    lo, hi = (torch.tensor(2.0 ** w, dtype=f32) for w in window)
+    c2 = torch.tensor(scale, dtype=f32) * torch.tensor(_LOG2E_F32, dtype=f32)
+    Qp = _bhsd((q.float() * c2).to(T), H, torch.float64)
+    K, V = _bhsd(k.to(T), H, torch.float64), _bhsd(v.to(T), H, torch.float64)
+    s2 = torch.matmul(Qp, K.transpose(-1, -2)).to(f32)          # fp32 accumulators of the score MFMAs
+    inv = _drop_consts(dropout_p)[0]
+    ar = torch.arange(S, device=dev)
+    qw, q0 = ar // 32 * 32, ar // 128 * 128
+    m = torch.zeros(B, H, S, dtype=f32, device=dev)
+    l = torch.zeros_like(m)
+    o = torch.zeros(B, H, S, D, dtype=f32, device=dev)
+    doc = doc_start is not None
+    if doc:
+        ds = doc_start.to(dev).long()
+        ds_q, ds_lo = ds[:, None, :], ds[:, qw][:, None, :]
+        tfirst = (torch.minimum(ds[:, q0].clamp_min(0), q0[None]) // FLASH_TILE)[:, None, :]
+    for t in range(S // FLASH_TILE):
+        kb = t * FLASH_TILE
+        keys = kb + torch.arange(FLASH_TILE, device=dev)
+        visit = torch.ones(B, 1, S, dtype=torch.bool, device=dev)
+        masked = torch.zeros(B, 1, S, FLASH_TILE, dtype=torch.bool, device=dev)
+        if causal:
+            visit = visit & (kb <= qw + 31)[None, None, :]
+            masked = masked | (keys[None, :] > ar[:, None])
+        dead = torch.zeros(B, 1, S, dtype=torch.bool, device=dev)
+        if doc:
+            visit = visit & (t >= tfirst) & (kb + FLASH_TILE > ds_lo)
+            masked = masked | (keys[None, None, None, :] < ds_q[..., None])
+            dead = kb + FLASH_TILE <= ds_q
+        raw = s2[..., kb:kb + FLASH_TILE]
+
+        def scores(mask=True):
+            st = raw - m[..., None]
+            return st.masked_fill(masked, float("-inf")) if mask else st
+
+        p = torch.exp2(scores())
+        rsum = p.sum(-1)
+        bad = visit & ~dead & (~(rsum <= hi) | ((l == 0) & (rsum < lo)))
+        ballot = bad.view(B, H, S // 32, 32).any(-1, keepdim=True).expand(B, H, S // 32, 32).reshape(B, H, S)
+        if bool(ballot.any()):
+            st = scores(mask=mutate != "rescue_ignores_mask")
+            tmax = st.amax(-1)
+            sel = ballot if mutate == "select_all_lanes" else bad
+            d = torch.where(sel, tmax, torch.zeros_like(tmax))
+            alpha = torch.exp2(-d)
+            if alpha_guard:
+                alpha = torch.where(l > 0, alpha, torch.ones_like(alpha))
+            if mutate != "no_l_rescale":
+                l = torch.where(ballot, l * alpha, l)
+            if mutate != "no_o_rescale":
+                o = torch.where(ballot[..., None], o * alpha[..., None], o)
+            p2 = torch.exp2(st - d[..., None])
+            m = torch.where(ballot, m + d, m)
+            p = torch.where(ballot[..., None], p2, p)
+            rsum = p.sum(-1)
+        pb = p.to(T)
+        if keep is not None:
+            pb = pb * keep[..., kb:kb + FLASH_TILE].to(T)
+        # fp32 accumulation of P V; 0 * inf and inf - inf come out as in the MFMA (NaN)
+        pv = torch.matmul(pb.double(), V[:, :, kb:kb + FLASH_TILE]).to(f32)
+        l = torch.where(visit.expand_as(l), l + rsum, l)
+        o = torch.where(visit[..., None].expand_as(o), o + pv, o)
+    rinv = torch.where(l > 0, inv / l, torch.zeros_like(l))
+    lse = (torch.log2(l) if mutate == "lse_without_m" else m + torch.log2(l)) * 0.6931471805599453
+    out = (o * rinv[..., None]).to(T).transpose(1, 2)
+    return (out, lse, m) if return_m else (out, lse)
+
+
+def row_rel_errs(out, ref, floor_frac: float = 1e-4):
+    """The per-row terms of ``row_rel_err`` (same floor) and the rows' max|ref|, float64."""
+    o = out.detach().double().reshape(-1, out.shape[-1])
+    r = ref.detach().double().reshape(-1, ref.shape[-1]).to(o.device)
+    rmax = r.abs().amax(-1)
+    den = rmax.clamp_min(floor_frac * r.abs().max().clamp_min(1e-30))
+    return (o - r).abs().amax(-1) / den, rmax, den
+
+
+def ulp_at(x, dtype):
+    """One unit in the last place of ``dtype`` at magnitude x (float64 tensor; the spacing of the
+    smallest normal below it)."""
+    fi = torch.finfo(dtype)
+    return torch.exp2(torch.floor(torch.log2(x.clamp_min(fi.tiny)))) * fi.eps
+
+
+def flash_grad_floors(q, k, v, do, scale, causal, dropout_p=0.0, keep=None, doc_start=None):
+    """Per row of dq / dk / dv ([B, S, heads]), the absolute error that the rounding of the 16-bit
+    MFMA operands alone can put into the row (as ``softmax_grad_floor`` does for the softmax): two
+    implementations with the same rounding points still differ in which way single values round,
+    and a row that sums many of them (exactly cancelling ones included) sees the sum. From float64
+    attention on the same inputs, worst case (all errors aligned), u = half an ulp of the type:
+      dS = P (dP - delta) as a 16-bit operand: |err| <= u |dS| + D 2^-24 P (sum_d |O dO| + sum_d |dO V|)
+        (its rounding, and the fp32 sums of D terms behind delta and dP, which cancel in dP - delta);
+      dq = scale dS K -> scale sum_k err |K|;  dk = scale dS^T Q -> scale sum_q err |Q|;
+      dv = P^T dO with P a 16-bit operand -> sum_q u P |dO|;  each the max over the row's columns."""
+    f64 = torch.float64
+    B, S, H, D = q.shape
+    Hkv = k.shape[2]
+    u, g32 = torch.finfo(q.dtype).eps / 2, D * 2.0 ** -24
+    inv = _drop_consts(dropout_p)[0]
+    Q, K, V, DO = (_bhsd(t, H, f64) for t in (q, k, v, do))
+    s = (torch.matmul(Q, K.transpose(-1, -2)) * scale).masked_fill(_flash_masked(B, S, causal, doc_start, q.device),
+                                                                    float("-inf"))
+    P = torch.softmax(s, -1)
+    Pd = P * inv if keep is None else P * keep.to(f64) * inv
+    O = torch.matmul(Pd, V)
+    dP = torch.matmul(DO, V.transpose(-1, -2))
+    dS = Pd * dP - P * (O * DO).sum(-1, keepdim=True)
+    err = u * dS.abs() + g32 * P * inv * ((O.abs() * DO.abs()).sum(-1, keepdim=True)
+                                         + torch.matmul(DO.abs(), V.abs().transpose(-1, -2)))
+    grp = lambda t: t.view(B, Hkv, H // Hkv, S, D).sum(2)
+    return {"dq": (scale * torch.matmul(err, K.abs())).amax(-1).transpose(1, 2),
+            "dk": grp(scale * torch.matmul(err.transpose(-1, -2), Q.abs())).amax(-1).transpose(1, 2),
+            "dv": grp(torch.matmul((u * Pd).transpose(-1, -2), DO.abs())).amax(-1).transpose(1, 2)}
+
+
+def flash_excess(out, emu, ref, dtype, floor=None):
+    """The flash criterion. Row by row (rows and denominators as in ``row_rel_err``, with its floor):
+    the kernel's error <= 2 x the error of the emulation IN THE SAME ROW against the same float64
+    reference + one ulp of the 16-bit type at the row's denominator + ``floor`` (per row, absolute:
+    ``flash_grad_floors`` for the gradients). A bound taken from the emulation's worst row would let
+    that one row (a causal row 0 with exact dq = 0, judged against the floor) excuse every other
+    row. The criterion as the issue words it, error <= 2 x ``row_rel_err`` of the emulation + one ulp
+    at the row's max, is kept beside it; the result is the larger of the two excesses. Returns
+    (worst kernel error / bound over the rows, largest kernel error, largest emulation error); lse
+    ([B, H, S]) is judged one value per row. Not finite anywhere -> inf."""
+    if out.dim() == 3:
+        out, emu, ref = out[..., None], emu[..., None], ref[..., None]
+    ee = row_rel_errs(emu, ref)[0]
+    if not bool(torch.isfinite(out.detach().double()).all()):
+        return float("inf"), float("inf"), ee.max().item()
+    ek, rmax, den = row_rel_errs(out, ref)
+    fl = 0.0 if floor is None else floor.detach().double().reshape(-1).to(den.device)
+    own = ek / (2.0 * ee + (ulp_at(den, dtype) + fl) / den)
+    worst = ek / (2.0 * ee.max() + ulp_at(rmax, dtype) / den)
+    return max(own.max().item(), worst.max().item()), ek.max().item(), ee.max().item()
+
+
+def assert_flash_close(got, emu, ref, dtype, names=("o", "lse", "dq", "dk", "dv"), what="", floors=None):
+    """``flash_excess`` <= 1 for every named output (``floors``: ``flash_grad_floors``); prints each
+    figure before it asserts."""
+    fails = []
+    for n in names:
+        ratio, ek, ee = flash_excess(got[n], emu[n], ref[n], dtype, (floors or {}).get(n))
+        print(f"flash {what} {n}: kernel {ek:.3e} emulation {ee:.3e} kernel/bound {ratio:.3f}")
+        if not ratio <= 1.0:
+            fails.append(f"{n}: error {ek:.4g} vs emulation {ee:.4g}, {ratio:.3g}x the bound")
+    assert not fails, f"{what}: " + "; ".join(fails)

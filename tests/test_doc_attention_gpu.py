@@ -8,6 +8,7 @@ import math
 import pytest
 import torch
 
+import _numerics as N
 from smdt_amd.ops import functional as SF
 from smdt_amd.train.utils import document_ends, document_starts
 
@@ -42,13 +43,28 @@ def _inputs(heads, D, dt):
     return mk(H), mk(Hkv), mk(Hkv), mk(H)
 
 
-def _check(o, orf, pairs):
+def _rows_check(got, q, k, v, do, scale, p=0.0, keep=None, ds=None):
+    """The row-relative criterion of tests/test_flash_score_range_gpu.py beside the global one: per
+    row within 2 x the error of the kernels' rounding points against float64 attention + one ulp
+    at the row's max, so a single wrong row cannot hide under 0.05 * max|ref|. ``got``: o, dq, dk,
+    dv as [B, S, heads, D]."""
+    ref = N.flash_ref(q, k, v, do, scale, True, p, keep, ds)
+    emu = N.flash_emulation_at_kernel_max(q, k, v, do, scale, True, p, keep, ds)
+    N.assert_flash_close(dict(zip(("o", "dq", "dk", "dv"), got)), emu, ref, q.dtype, names=("o", "dq", "dk", "dv"),
+                         what="doc", floors=N.flash_grad_floors(q, k, v, do, scale, True, p, keep, ds))
+
+
+def _check(o, orf, pairs, rows=None):
+    """``rows`` = (q, k, v, do, scale, p, keep, doc_start) adds ``_rows_check`` on o and the pairs'
+    gradients (dq, dk, dv)."""
     assert torch.isfinite(o.float()).all()
     torch.testing.assert_close(o.float(), orf, atol=2e-2, rtol=2e-2)
     for a, r in pairs:
         assert torch.isfinite(a.float()).all()
         err = (a.float() - r).abs().max().item()
         assert err < 0.05 * max(1.0, r.abs().max().item()), err
+    if rows is not None:
+        _rows_check([o.detach()] + [a for a, _ in pairs], *rows)
 
 
 def _kernel_vs_ref(points, heads, D, dt, p):
@@ -63,7 +79,8 @@ def _kernel_vs_ref(points, heads, D, dt, p):
     orf = SF.attention_ref(qr, kr, vr, scale, True, p, keep, doc_start=ds)
     o.backward(do)
     orf.backward(do.float())
-    _check(o, orf, [(a.grad, r.grad) for a, r in ((q, qr), (k, kr), (v, vr))])
+    _check(o, orf, [(a.grad, r.grad) for a, r in ((q, qr), (k, kr), (v, vr))],
+           rows=(q0, k0, v0, do, scale, p, keep, ds))
 
 
 @pytest.mark.parametrize("p", [0.0, 0.1])
@@ -141,6 +158,9 @@ def test_doc_flash_attention_qkv_fused_strides(seq_first, monkeypatch):
     orf = (orf.transpose(0, 1) if seq_first else orf).flatten(-2)
     orf.backward(do.float())
     _check(o, orf, [(qkv.grad, qr.grad)])
+    unf = lambda t: (t.transpose(0, 1) if seq_first else t).unflatten(-1, (nh, hd))
+    _rows_check([unf(o.detach())] + list(SF._qkv_views(qkv.grad, nh, nkv, hd, seq_first)),
+                *(t.detach() for t in SF._qkv_views(qkv, nh, nkv, hd, seq_first)), unf(do), 1 / math.sqrt(hd), ds=ds)
 
 
 def test_doc_flash_attention_padded_length(monkeypatch):
@@ -163,7 +183,8 @@ def test_doc_flash_attention_padded_length(monkeypatch):
     qr, kr, vr = (t.detach().float().requires_grad_() for t in (q, k, v))
     orf = SF.attention_ref(qr, kr, vr, scale, True, doc_start=ds)
     orf.backward(do.float())
-    _check(o, orf, [(a.grad, r.grad) for a, r in ((q, qr), (k, kr), (v, vr))])
+    _check(o, orf, [(a.grad, r.grad) for a, r in ((q, qr), (k, kr), (v, vr))],
+           rows=(q.detach(), k.detach(), v.detach(), do, scale, 0.0, None, ds))
 
 
 EOD = 5

@@ -254,3 +254,134 @@ def test_causal_softmax_rectangular_is_top_left_aligned():
     assert (y[..., j > i] == 0).all() and (y[..., 39, :40] > 0).any()
     br = torch.softmax((x.double() * 0.125).masked_fill(j > i + 96, float("-inf")), -1)
     assert N.row_rel_err(br, yr) > 0.5
+
+
+# ------------------------------------------------------------------------------------------
+# Flash attention forward: the lazy reference max and its rescue (CPU twin of fwd_kernel).
+
+def _flash_twin_excess(profile, dtype, window, causal, **kw):
+    """max over (o, lse) of twin error / bound (``N.flash_excess``: 2 x the emulation's error + one
+    ulp at the row max) on one profile; B 1, S 256 (4 key tiles, 2 query blocks), GQA 2 : 1, D 64."""
+    doc = kw.pop("doc_start", None)
+    q, k, v, do = N.flash_score_case(profile, B=1, S=256, H=2, Hkv=1, D=64, dtype=dtype)
+    ref = N.flash_ref(q, k, v, do, N.FLASH_SCALE, causal, doc_start=doc)
+    emu = N.flash_kernel_emulation(q, k, v, do, N.FLASH_SCALE, causal, doc_start=doc)
+    o, lse = N.flash_lazy_max_twin(q, k, v, N.FLASH_SCALE, causal, dtype, window, doc_start=doc, **kw)
+    return max(N.flash_excess(o, emu["o"], ref["o"], dtype)[0], N.flash_excess(lse, emu["lse"], ref["lse"], dtype)[0]), o
+
+
+@pytest.mark.parametrize("causal", [True, False])
+@pytest.mark.parametrize("profile", sorted(N.FLASH_PROFILES))
+def test_flash_twin_matches_float64(profile, causal):
+    """fwd_kernel's tile-by-tile algorithm (bf16, window [2^-64, 2^64], the guarded alpha) is within
+    the GPU tests' bound of float64 attention on every score profile (measured: 0.56 - 0.60 of the
+    bound for o, 0.04 - 0.32 for lse)."""
+    e, _ = _flash_twin_excess(profile, torch.bfloat16, N.FLASH_WINDOWS[torch.bfloat16], causal)
+    assert e <= 1.0, e
+
+
+# mutation -> (profile, causal) that must reject it; measured twin error / bound in the comment
+_FLASH_CATCH = {
+    "no_o_rescale": ("up_late", False),            # o 2585x
+    "no_l_rescale": ("up_late", False),            # o 117x, lse 4.3x
+    "lse_without_m": ("low_start", False),         # lse 252x
+    "rescue_ignores_mask": ("low_start", True),    # o 176x, lse 898x (causal only: the mask is the diagonal's)
+    "select_all_lanes": ("opposed", False),        # NaN: the falling lanes' l * exp2(+144) overflows
+}
+
+
+@pytest.mark.parametrize("mutate", N.FLASH_MUTATIONS)
+def test_flash_criterion_rejects_rescue_mutations(mutate):
+    """Every step of the rescue is visible to the criterion: the twin with one step broken exceeds
+    the bound on the profile named in ``_FLASH_CATCH`` (factors there), and stays inside it on
+    ``plain``, which never rescues — randn-like scores cannot see any of these."""
+    prof, causal = _FLASH_CATCH[mutate]
+    e, _ = _flash_twin_excess(prof, torch.bfloat16, (-64, 64), causal, mutate=mutate)
+    assert not e <= 4.0, (mutate, e)
+    e, _ = _flash_twin_excess("plain", torch.bfloat16, (-64, 64), causal, mutate=mutate)
+    assert e <= 1.0, (mutate, e)
+
+
+def test_flash_select_all_lanes_breaks_dead_doc_rows():
+    """DOC: a wave whose rows 0..15 ask for a downward rescue on a tile where rows 16..31 (a later
+    document) are dead: d = tmax = -inf for the dead lanes is NaN, d = bad ? tmax : 0 is not."""
+    ds = torch.zeros(1, 256, dtype=torch.int32)
+    ds[:, 80:] = 80
+    e, _ = _flash_twin_excess("low_start", torch.bfloat16, (-64, 64), True, doc_start=ds)
+    assert e <= 1.0, e
+    e, _ = _flash_twin_excess("low_start", torch.bfloat16, (-64, 64), True, doc_start=ds, mutate="select_all_lanes")
+    assert not e <= 4.0, e
+
+
+@pytest.mark.parametrize("causal", [True, False])
+def test_flash_fp16_needs_its_own_window(causal):
+    """Why fwd_kernel's window depends on the type. With the window bf16 uses, [2^-64, 2^64], the
+    fp16 twin overflows p to inf on ``fp16_high`` (natural score 20 -> p = 2^29 > 65504) and on
+    ``low_start`` (after the move to -60 the -30 tiles give 2^43), and flushes every p to zero on
+    ``fp16_low`` (p = 2^-36: O = 0 while l counts them). A lower bound of 2^-14 that only keeps p
+    non-zero leaves ``fp16_subnormal`` ~16x over the bound (2^-24: ~44x). With [2^0, 2^15] every
+    profile passes."""
+    old = N.FLASH_WINDOW_PARENT
+    e, o = _flash_twin_excess("fp16_high", torch.float16, old, causal)
+    assert not torch.isfinite(o.float()).all() and not e <= 1.0
+    e, o = _flash_twin_excess("low_start", torch.float16, old, causal)
+    assert not torch.isfinite(o.float()).all()
+    e, o = _flash_twin_excess("fp16_low", torch.float16, old, causal)
+    assert (o[:, 1::2].float() == 0).all() and e > 100, e       # the rows with qa = 16: all zero
+    for lo in (-24, -14):
+        e, _ = _flash_twin_excess("fp16_subnormal", torch.float16, (lo, 15), causal)
+        assert e > 4.0, (lo, e)
+    assert N.FLASH_WINDOWS[torch.float16] == (0, 15)
+    for prof in N.FLASH_PROFILES:
+        e, _ = _flash_twin_excess(prof, torch.float16, N.FLASH_WINDOWS[torch.float16], causal)
+        assert e <= 1.0, (prof, e)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("profile", ["very_low", "very_low_first"])
+def test_flash_downward_rescue_needs_alpha_guard(profile, dtype):
+    """A first tile whose row max is below 2^-128 (natural score -100): alpha = exp2(-tmax) = inf,
+    and l = 0 * inf = NaN with the unguarded rescale; alpha = 1 where l == 0 gives the reference."""
+    w = N.FLASH_WINDOWS[dtype]
+    e, o = _flash_twin_excess(profile, dtype, w, False, alpha_guard=False)
+    assert torch.isnan(o[:, 1::2].float()).all() and not e <= 1.0
+    e, o = _flash_twin_excess(profile, dtype, w, False)
+    assert e <= 1.0, e
+
+
+@pytest.mark.parametrize("profile,dtype,causal", [("plain", torch.bfloat16, True), ("up_late", torch.bfloat16, True),
+                                                  ("very_low", torch.bfloat16, False), ("very_low", torch.bfloat16, True),
+                                                  ("very_low", torch.float16, False)])
+def test_flash_criterion_rejects_wrong_gradient_rows(profile, dtype, causal):
+    """The gradients' criterion (per-row emulation error, one ulp, ``flash_grad_floors``) can fail,
+    row by row. The emulation at the kernel's reference max stands in for the kernel (0.33 - 0.5 of
+    the bound against itself); all-zero, x2, x1.25 and ONE zeroed row (37 or 200) of dq, dk and dv
+    are rejected. Measured worst error / bound, bf16: ``plain`` causal zero 79 - 101, x1.25 33 -
+    48, one row 21 - 54; ``up_late`` causal zero 83 - 93, one row 22 - 54; ``very_low`` dq zero
+    2.9 - 7.7, one row 1.7 - 2.9. bf16 dk / dv on ``very_low`` are the weak spot: the dK / dV kernel
+    prescales K where the forward prescales Q, at |score| ~ 100 its P is off by up to 2^0.5, the
+    emulation's own row error is 0.3 - 0.5, and the factor 2 leaves zero 2.4 - 4.8, one row 1.08 -
+    1.5 (fp16: zero 22 - 127, one row 21 - 60); x1.25 is not asked there (0.7 - 1.0 of the bound: on
+    the reserved channel, |k| = 50, the rounding floor of the cancelling dS sum is that large).
+    The emulation with a true row max (no lazy-max rounding of P) misses the bound on causal dq of
+    ``plain`` and ``up_late`` (1.4 - 2x): that rounding point is part of the kernel."""
+    q, k, v, do = N.flash_score_case(profile, B=1, S=256, H=2, Hkv=1, D=64, dtype=dtype)
+    ref = N.flash_ref(q, k, v, do, N.FLASH_SCALE, causal)
+    emu = N.flash_emulation_at_kernel_max(q, k, v, do, N.FLASH_SCALE, causal)
+    fl = N.flash_grad_floors(q, k, v, do, N.FLASH_SCALE, causal)
+    for n in ("dq", "dk", "dv"):
+        g = emu[n]
+        ex = lambda t: N.flash_excess(t, emu[n], ref[n], dtype, fl[n])[0]
+        assert ex(g) <= 0.5 + 1e-9, (n, ex(g))
+        muts = [("zero", torch.zeros_like(g)), ("x2", 2 * g)]
+        if profile != "very_low":
+            muts.append(("x1.25", 1.25 * g.float()))
+        for what, bad in muts:
+            assert ex(bad) > 1.0, (n, what, ex(bad))
+        for r in (37, 200):
+            z = g.clone()
+            z[0, r, 0] = 0
+            assert ex(z) > 1.0, (n, r, ex(z))
+    if profile != "very_low":
+        true_max = N.flash_kernel_emulation(q, k, v, do, N.FLASH_SCALE, causal)
+        assert N.flash_excess(true_max["dq"], emu["dq"], ref["dq"], dtype, fl["dq"])[0] > 1.0
