@@ -992,6 +992,99 @@ std::vector<Tensor> window_attn_bwd(Tensor qkv, Tensor table, Tensor lse, Tensor
   return {dqkv, dtable};
 }
 
+// ------------------------------------------------------------------ incremental decoding
+// q [B, nh, D], caches [B, cap, nkv, D], lens int32 [B] on the device (valid keys per sequence, the
+// new token included); max_len <= cap bounds the grid (0: cap). Everything the kernel does not
+// take is refused here, before any launch.
+static void dec_check_cache(const Tensor& k_cache, const Tensor& v_cache, const Tensor& like, const char* what) {
+  need_contig(k_cache, "k_cache");
+  need_contig(v_cache, "v_cache");
+  TORCH_CHECK(like.scalar_type() == at::kBFloat16 || like.scalar_type() == at::kHalf, what,
+              ": bf16 or fp16 operands, got ", like.scalar_type());
+  TORCH_CHECK(k_cache.dim() == 4 && v_cache.sizes() == k_cache.sizes() && k_cache.scalar_type() == like.scalar_type() &&
+                  v_cache.scalar_type() == like.scalar_type() && k_cache.device() == like.device() &&
+                  v_cache.device() == like.device() && k_cache.size(0) == like.size(0),
+              what, ": k_cache / v_cache must be [B, cap, nkv, D] of the new token's dtype and device");
+  TORCH_CHECK(k_cache.size(1) > 0 && k_cache.size(1) < (1LL << 31) && k_cache.size(0) <= 65535 &&
+                  k_cache.size(2) <= 65535, what, ": cache shape out of range");
+}
+
+static const int* dec_index(const Tensor& t, const Tensor& like, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device() && t.scalar_type() == at::kInt && t.dim() == 1 &&
+                  t.size(0) == like.size(0) && t.is_contiguous(),
+              what, ": lens / pos must be a contiguous int32 [B] tensor on the operands' device");
+  return t.data_ptr<int>();
+}
+
+int64_t decode_attn_chunk() { return smdt_decode_attn_chunk(); }
+
+bool decode_attn_supported(int64_t dtype, int64_t D, int64_t nh, int64_t nkv) {
+  return nh < (1 << 20) && nkv < (1 << 20) && D < (1 << 20) &&
+         smdt_decode_attn_supported((int)dtype, (int)D, (int)nh, (int)nkv) != 0;
+}
+
+Tensor decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor lens, double scale, int64_t max_len) {
+  need_contig(q, "q");
+  TORCH_CHECK(q.dim() == 3, "decode_attn: q must be [B, nh, D]");
+  dec_check_cache(k_cache, v_cache, q, "decode_attn");
+  const int64_t B = q.size(0), nh = q.size(1), D = q.size(2), cap = k_cache.size(1), nkv = k_cache.size(2);
+  TORCH_CHECK(k_cache.size(3) == D, "decode_attn: head dim of q and the caches differ");
+  TORCH_CHECK(decode_attn_supported(dcode(q), D, nh, nkv),
+              "decode_attn: unsupported (needs D in {64, 128} and nh / nkv in {1, 2, 4, 8}): D ", D, ", nh ", nh,
+              ", nkv ", nkv);
+  if (max_len <= 0) max_len = cap;
+  TORCH_CHECK(max_len <= cap, "decode_attn: max_len ", max_len, " exceeds the cache capacity ", cap);
+  const int* lp = dec_index(lens, q, "decode_attn");
+  const int64_t C = smdt_decode_attn_chunk();
+  const int64_t nchunks = (max_len + C - 1) / C;
+  auto f32 = q.options().dtype(at::kFloat);
+  auto ws_ml = torch::empty({B, nh, nchunks, 2}, f32);
+  auto ws_acc = torch::empty({B, nh, nchunks, D}, f32);
+  auto out = torch::empty_like(q);
+  check(smdt_decode_attn(dcode(q), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), lp,
+                         ws_ml.data_ptr<float>(), ws_acc.data_ptr<float>(), out.data_ptr(), (int)B, (int)nh,
+                         (int)nkv, (int)D, (int)cap, (int)max_len, (float)scale, cur_stream()),
+        "decode_attn");
+  return out;
+}
+
+// qkv [B, (nh + 2 nkv) D] -> q [B, nh, D]; k / v written into row pos[b] of the caches. cos / sin
+// (fp32 [max_pos, rot / 2]) and rot > 0 rotate q and k; without them the op is a copy.
+Tensor decode_rope_append(Tensor qkv, Tensor k_cache, Tensor v_cache, Tensor pos, int64_t nh, OptT cos_t,
+                          OptT sin_t, int64_t rot) {
+  need_contig(qkv, "qkv");
+  TORCH_CHECK(qkv.dim() == 2, "decode_rope_append: qkv must be [B, (nh + 2 nkv) D]");
+  dec_check_cache(k_cache, v_cache, qkv, "decode_rope_append");
+  const int64_t B = qkv.size(0), cap = k_cache.size(1), nkv = k_cache.size(2), D = k_cache.size(3);
+  TORCH_CHECK(nh > 0 && nh < (1 << 20) && D % 8 == 0 && D < (1 << 20) && qkv.size(1) == (nh + 2 * nkv) * D,
+              "decode_rope_append: qkv width ", qkv.size(1), " is not (nh + 2 nkv) D with D % 8 == 0");
+  const int* pp = dec_index(pos, qkv, "decode_rope_append");
+  const float *cp = nullptr, *sp = nullptr;
+  int64_t max_pos = 0;
+  if (rot > 0) {
+    TORCH_CHECK(cos_t.has_value() && sin_t.has_value(), "decode_rope_append: rot > 0 needs the cos / sin tables");
+    need_contig(*cos_t, "cos");
+    need_contig(*sin_t, "sin");
+    TORCH_CHECK(cos_t->scalar_type() == at::kFloat && sin_t->scalar_type() == at::kFloat && cos_t->dim() == 2 &&
+                    sin_t->sizes() == cos_t->sizes() && cos_t->device() == qkv.device() &&
+                    sin_t->device() == qkv.device(),
+                "decode_rope_append: fp32 [max_pos, rot / 2] tables on qkv's device");
+    TORCH_CHECK(rot <= D && rot % 16 == 0 && cos_t->size(1) == rot / 2, "decode_rope_append: rotary dim mismatch");
+    max_pos = cos_t->size(0);
+    TORCH_CHECK(max_pos < (1LL << 31), "decode_rope_append: table too long");
+    cp = cos_t->data_ptr<float>();
+    sp = sin_t->data_ptr<float>();
+  } else {
+    TORCH_CHECK(rot == 0, "decode_rope_append: negative rotary dim");
+  }
+  auto q = torch::empty({B, nh, D}, qkv.options());
+  check(smdt_decode_rope_append(dcode(qkv), qkv.data_ptr(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                                pp, (int)B, (int)nh, (int)nkv, (int)D, (int)cap, (int)rot, cp, sp, (int)max_pos,
+                                cur_stream()),
+        "decode_rope_append");
+  return q;
+}
+
 // `out` (optional) is a preallocated [B, S, H, D] view with any strides (e.g. the [s, b, h]
 // activation layout used by the transformer trunk). `doc_start` (optional, causal only) selects the
 // per-document kernels.
@@ -1360,6 +1453,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("wgrad_fp8_grouped", &wgrad_fp8_grouped, arg("main_grads"), arg("dys"), arg("xs"), arg("inv_dys"),
         arg("inv_xs"), arg("overwrite") = std::vector<bool>{}, arg("cus") = 0);
   m.def("wgrad_fp8_supported", &wgrad_fp8_supported);
+  m.def("decode_attn_chunk", &decode_attn_chunk);
+  m.def("decode_attn_supported", &decode_attn_supported, arg("dtype"), arg("D"), arg("nh"), arg("nkv"));
+  m.def("decode_attn", &decode_attn, arg("q"), arg("k_cache"), arg("v_cache"), arg("lens"), arg("scale"),
+        arg("max_len") = 0);
+  m.def("decode_rope_append", &decode_rope_append, arg("qkv"), arg("k_cache"), arg("v_cache"), arg("pos"), arg("nh"),
+        arg("cos") = pybind11::none(), arg("sin") = pybind11::none(), arg("rot") = 0);
   m.def("window_attn_fwd", &window_attn_fwd, arg("qkv"), arg("table"), arg("window"), arg("shift"), arg("heads"));
   m.def("window_attn_bwd", &window_attn_bwd, arg("qkv"), arg("table"), arg("lse"), arg("dout"), arg("window"),
         arg("shift"), arg("heads"));

@@ -150,6 +150,24 @@ hipError_t smdt_flash_bwd_sums(int dtype, const void* q, const void* k, const vo
                                float scale, int causal, float dropout_p, uint64_t seed, uint64_t offset,
                                const int* doc_start, const int* doc_end, float* colpart, hipStream_t st);
 
+// decode_attn.hip: incremental decoding. smdt_decode_attn: out [B, nh, D] = attention of one query
+// per sequence, q [B, nh, D], against k_cache / v_cache [B, cap, nkv, D] (contiguous, q's dtype:
+// bf16 / fp16), keys 0 .. lens[b] - 1 (device int32 [B]); max_len <= cap only bounds the grid.
+// Two launches, no atomics. Workspaces for nchunks = ceil(max_len / smdt_decode_attn_chunk()):
+// ws_ml fp32 [B, nh, nchunks, 2], ws_acc fp32 [B, nh, nchunks, D]. Supported: D in {64, 128}, nh /
+// nkv in {1, 2, 4, 8}; anything else returns hipErrorInvalidValue unlaunched.
+int smdt_decode_attn_chunk();
+int smdt_decode_attn_supported(int dtype, int D, int nh, int nkv);
+hipError_t smdt_decode_attn(int dtype, const void* q, const void* k_cache, const void* v_cache, const int* lens,
+                            float* ws_ml, float* ws_acc, void* out, int B, int nh, int nkv, int D, int cap,
+                            int max_len, float scale, hipStream_t st);
+// qkv [B, (nh + 2 nkv) D] of one new token per sequence: q / k rotated at pos[b] (device int32 [B])
+// over their first rot elements (rope.hip's arithmetic bit for bit; rot == 0: no RoPE, tables
+// unused), q -> q_out [B, nh, D], k / v -> row pos[b] of the caches. cos / sin fp32 [max_pos, rot / 2].
+hipError_t smdt_decode_rope_append(int dtype, const void* qkv, void* q_out, void* k_cache, void* v_cache,
+                                   const int* pos, int B, int nh, int nkv, int D, int cap, int rot,
+                                   const float* cos_t, const float* sin_t, int max_pos, hipStream_t st);
+
 // window_attn.hip: Swin shifted-window attention on the qkv linear's output over the padded,
 // unrolled grid, qkv [B, ph, pw, 3 heads d] read as (3, heads, d); roll, window partition and head
 // split are address arithmetic. table: fp32 [(2 ws - 1)^2, heads]. out [B, ph, pw, heads d] at the

@@ -1,0 +1,200 @@
+"""KV-cache text generation for ``GPTModel`` (and ``HFCausalLM.generate`` on top of it).
+
+Prefill: the right-padded prompt batch [B, Lmax] runs through the unchanged causal forward (flash
+attention on the GPU); causality keeps a real token blind to the pads on its right. Every attention
+layer copies its post-RoPE K and V into cache rows 0 .. Lmax - 1 (``transformer.kv_prefill``),
+``lens`` is set to the prompt lengths and only the last real position of each row goes through the
+LM head.
+
+Decode step: one new token per sequence. ``ParallelAttention.forward_decode`` runs the QKV linear,
+rotates q / k at ``pos = lens`` and appends k / v into that cache row (over the pad K / V the
+prefill left there), then single-query attention over ``lens + 1`` keys (csrc/kernels/
+decode_attn.hip). ``lens`` and ``pos`` live on the device and advance there once per step: no
+kernel and no Python code of a step reads a length on the host, so with the static shapes
+(``max_len = capacity``) a step can be captured in a graph (``use_graph=True``,
+``train.graphs.CapturedStep``).
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+
+from ..ops import functional as SF
+from ..parallel import state as ps
+from . import transformer as _T
+from .transformer import TransformerConfig
+
+EOS_POLL_STEPS = 16     # the host asks whether every row has finished at most this often
+
+
+class KVCache:
+    """Per-layer K / V of shape [B, capacity, nkv, D], ``lens`` (int32 [B], device: the valid keys
+    of each sequence) and ``pos`` (int32 [B]: the row the current step's token is written to)."""
+
+    def __init__(self, cfg: TransformerConfig, batch: int, capacity: int, dtype=None, device=None):
+        if batch < 1 or capacity < 1:
+            raise ValueError(f"KVCache: batch {batch} and capacity {capacity} must be positive")
+        self.batch, self.capacity = int(batch), int(capacity)
+        self.max_len = self.capacity          # bounds the decode kernel's grid (static: capturable)
+        dtype = dtype or cfg.params_dtype
+        shape = (self.batch, self.capacity, cfg.num_query_groups, cfg.kv_channels)
+        self.k = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(cfg.num_layers)]
+        self.v = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(cfg.num_layers)]
+        self.lens = torch.zeros(self.batch, dtype=torch.int32, device=device)
+        self.pos = torch.zeros(self.batch, dtype=torch.int32, device=device)
+
+    def store_prefill(self, attn, qkv):
+        """Called by every attention layer under ``transformer.kv_prefill``: ``qkv`` [L, B, W] is the
+        layer's fused projection output after RoPE."""
+        L, B = qkv.shape[0], qkv.shape[1]
+        if B != self.batch or L > self.capacity:
+            raise RuntimeError(f"KVCache: a prompt batch [{B}, {L}] does not fit the cache "
+                               f"[{self.batch}, capacity {self.capacity}]")
+        _, k, v = SF._qkv_views(qkv, attn.nh, attn.nkv, attn.hd, True)            # [B, L, nkv, D]
+        self.k[attn.layer_number][:, :L].copy_(k)
+        self.v[attn.layer_number][:, :L].copy_(v)
+
+    def advance(self):
+        """Start a decode step: the new token goes to row ``pos = lens`` and is one more key."""
+        self.pos.copy_(self.lens)
+        self.lens.add_(1)
+
+
+def _refuse(model, input_ids, attention_mask, max_new_tokens, cache):
+    """Everything generation does not do raises here, naming the cause."""
+    cfg = model.cfg
+    st = ps.get_state()
+    if st.tp > 1 or st.pp > 1 or st.cp > 1:
+        raise NotImplementedError(f"generate: tensor / pipeline / context parallel models are not supported "
+                                  f"(TP {st.tp}, PP {st.pp}, CP {st.cp}); generate from an unsharded model")
+    if cfg.sequence_parallel:
+        raise NotImplementedError("generate: sequence parallelism (sequence_parallel=True) is not supported")
+    if _T._PACK["idx"] is not None:
+        raise RuntimeError("generate: a padding-free packed_sequences context is active; generation takes the "
+                           "padded [B, L] batch")
+    if not (model.pre_process and model.post_process):
+        raise NotImplementedError("generate: the model must own the embedding and the LM head (one pipeline stage)")
+    if input_ids.dim() != 2 or input_ids.shape[1] < 1:
+        raise ValueError(f"generate: input_ids must be [B, L] with L >= 1, got {tuple(input_ids.shape)}")
+    if max_new_tokens < 1:
+        raise ValueError(f"generate: max_new_tokens must be positive, got {max_new_tokens}")
+    B, L = input_ids.shape
+    if attention_mask is not None:
+        if attention_mask.shape != input_ids.shape:
+            raise ValueError(f"generate: attention_mask {tuple(attention_mask.shape)} does not match input_ids "
+                             f"{tuple(input_ids.shape)}")
+        m = attention_mask.bool().cpu()            # once per call, before the loop
+        if not bool(m[:, 0].all()) or bool((m[:, 1:] & ~m[:, :-1]).any()):
+            raise ValueError("generate: prompts must be right-padded (attention_mask rows of ones followed by zeros, "
+                             "at least one token per row)")
+    total = L + max_new_tokens
+    if total > cfg.max_position_embeddings:
+        raise ValueError(f"generate: prompt length {L} + max_new_tokens {max_new_tokens} = {total} exceeds "
+                         f"max_position_embeddings {cfg.max_position_embeddings}")
+    if cache is not None and (cache.batch != B or total > cache.capacity):
+        raise ValueError(f"generate: prompt length {L} + max_new_tokens {max_new_tokens} = {total} for batch {B} "
+                         f"exceeds the KV cache (batch {cache.batch}, capacity {cache.capacity})")
+
+
+def filter_logits(logits, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0):
+    """fp32 logits [B, V] -> the logits sampling draws from: divided by the temperature, all but
+    the ``top_k`` largest and everything outside the ``top_p`` nucleus (the smallest set of most
+    likely tokens whose probability reaches ``top_p``) set to -inf."""
+    logits = logits.float()
+    if temperature != 1.0:
+        logits = logits / temperature
+    if top_k and 0 < top_k < logits.shape[-1]:
+        kth = logits.topk(top_k, dim=-1).values[:, -1:]
+        logits = logits.masked_fill(logits < kth, float("-inf"))
+    if top_p < 1.0:
+        srt, idx = logits.sort(dim=-1, descending=True)
+        probs = torch.softmax(srt, dim=-1)
+        before = probs.cumsum(dim=-1) - probs            # mass of the more likely tokens
+        drop = before >= top_p                           # never the most likely token (before = 0)
+        logits = logits.masked_fill(torch.zeros_like(drop).scatter(1, idx, drop), float("-inf"))
+    return logits
+
+
+def _pick(logits, do_sample, temperature, top_k, top_p, generator):
+    if not do_sample:
+        return logits.argmax(dim=-1)
+    probs = torch.softmax(filter_logits(logits, temperature, top_k, top_p), dim=-1)
+    # exponential race (the draw torch.multinomial makes for one sample), without a host sync
+    q = torch.empty_like(probs).exponential_(1.0, generator=generator)
+    return (probs / q).argmax(dim=-1)
+
+
+@torch.no_grad()
+def generate(model, input_ids, attention_mask=None, max_new_tokens: int = 32, do_sample: bool = False,
+             temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, eos_token_id: Optional[int] = None,
+             pad_token_id: int = 0, generator: Optional[torch.Generator] = None, use_graph: bool = False,
+             cache: Optional[KVCache] = None):
+    """Greedy or sampled continuation of the right-padded prompts ``input_ids`` [B, Lmax]
+    (``attention_mask`` marks the real tokens; None: every row is Lmax long) with a KV cache.
+
+    Returns ``sequences`` [B, Lmax + max_new_tokens]: row b holds its prompt, then its new tokens
+    immediately after, then ``pad_token_id``. A row that has emitted ``eos_token_id`` emits pad from
+    then on; the loop stops once every row has finished, which the host checks every
+    ``EOS_POLL_STEPS`` steps (no per-step synchronisation). Sampling (``do_sample``) draws from
+    ``filter_logits`` over the real vocabulary (``model.loss_vocab_size``), so vocab padding columns
+    are never returned. ``use_graph=True`` (GPU) captures one decode step and replays it.
+    ``cache``: a ``KVCache`` to reuse (its capacity must hold Lmax + max_new_tokens)."""
+    _refuse(model, input_ids, attention_mask, max_new_tokens, cache)
+    if do_sample and temperature <= 0:
+        raise ValueError(f"generate: temperature must be positive, got {temperature}")
+    was_training = model.training
+    model.eval()
+    try:
+        return _generate(model, input_ids, attention_mask, int(max_new_tokens), do_sample, float(temperature),
+                         int(top_k), float(top_p), eos_token_id, int(pad_token_id), generator, use_graph, cache)
+    finally:
+        model.train(was_training)
+
+
+def _generate(model, input_ids, attention_mask, max_new, do_sample, temperature, top_k, top_p, eos, pad, generator,
+              use_graph, cache):
+    cfg = model.cfg
+    dev = input_ids.device
+    B, L = input_ids.shape
+    vocab = int(model.loss_vocab_size or cfg.padded_vocab_size)
+    if attention_mask is None:
+        plen = torch.full((B,), L, dtype=torch.int64, device=dev)
+    else:
+        plen = attention_mask.to(dev).long().sum(dim=1)
+    if cache is None:
+        cache = KVCache(cfg, B, L + max_new, cfg.params_dtype, dev)
+
+    seq = torch.full((B, L + max_new), pad, dtype=input_ids.dtype, device=dev)
+    keep = torch.arange(L, device=dev)[None, :] < plen[:, None]
+    seq[:, :L] = torch.where(keep, input_ids, seq[:, :L])
+    finished = torch.zeros(B, dtype=torch.bool, device=dev)
+
+    def emit(logits, t):
+        tok = _pick(logits[:, :vocab], do_sample, temperature, top_k, top_p, generator)
+        tok = torch.where(finished, torch.full_like(tok, pad), tok)
+        seq.scatter_(1, (plen + t).unsqueeze(1), tok.unsqueeze(1).to(seq.dtype))
+        if eos is not None:
+            finished.logical_or_(tok == eos)
+        return tok
+
+    logits = model.forward_prefill(input_ids, plen, cache)
+    cache.lens.copy_(plen)
+    tok = emit(logits, 0)
+
+    def step(tokens):
+        cache.advance()
+        return model.forward_decode(tokens, cache)
+
+    captured = None
+    if use_graph and dev.type == "cuda":
+        # the first decode step runs eagerly (GEMM algorithm selection), the second is captured
+        from ..train.graphs import CapturedStep
+        step = captured = CapturedStep(step, warmup=1)
+    for t in range(1, max_new):
+        if eos is not None and t % EOS_POLL_STEPS == 0 and bool(finished.all()):
+            break
+        tok = emit(step(tok), t)
+    if captured is not None and captured.note.startswith("capture failed"):
+        raise RuntimeError(f"generate(use_graph=True): the decode step could not be captured ({captured.note})")
+    return seq

@@ -162,6 +162,28 @@ class GPTModel(nn.Module):
             logits = tp.gather_from_tensor_model_parallel_region(logits)
         return logits                                            # [s, b, V / tp]
 
+    # ---- text generation (models/generation.py): a whole, unsharded model in eval mode
+    def forward_prefill(self, tokens, lens, cache):
+        """The right-padded prompts ``tokens`` [b, L] through the causal forward (a real token never
+        sees the pads on its right), every layer's K / V copied into ``cache`` rows 0 .. L - 1; only
+        the hidden state at position ``lens[b] - 1`` (int64 [b], device) of each row goes through
+        the LM head. Returns the next-token logits [b, V]."""
+        from .transformer import kv_prefill
+        b, L = tokens.shape
+        x = self._embed(tokens, None, 0)                       # positions 0 .. L - 1 in every row
+        with kv_prefill(cache):
+            h = self.decoder(x, None, None)                                          # [L, b, h]
+        last = h[lens - 1, torch.arange(b, device=h.device)]                         # [b, h]
+        return self.lm_logits(last.unsqueeze(0)).squeeze(0)
+
+    def forward_decode(self, tokens, cache):
+        """One new token per sequence, ``tokens`` [b], at position ``cache.pos`` against the cache:
+        the next-token logits [b, V]. Learned positions take ``cache.pos`` through the
+        ``position_ids`` path."""
+        x = self._embed(tokens.unsqueeze(1), cache.pos.long().unsqueeze(1))          # [1, b, h]
+        h = self.decoder.forward_decode(x, cache)
+        return self.lm_logits(h).squeeze(0)
+
     def forward(self, tokens, position_ids=None, attention_mask=None, labels=None, loss_mask=None,
                 doc_start=None):
         """Returns per-token losses [b, s] when ``labels`` are given, else the logits. ``loss_mask``

@@ -423,6 +423,18 @@ class HFCausalLM(nn.Module):
         return loss, tok_loss
 
 
+    def generate(self, input_ids, attention_mask=None, **kw):
+        """KV-cache generation (``models.generation.generate``; same keyword arguments). The end-of-
+        sequence and pad ids default to the HF config's (pad falls back to eos, then 0); pass
+        ``eos_token_id=None`` to generate ``max_new_tokens`` whatever is emitted."""
+        from .generation import generate
+        eos = self.hf_config.get("eos_token_id")
+        kw.setdefault("eos_token_id", eos)
+        pad = self.hf_config.get("pad_token_id")
+        kw.setdefault("pad_token_id", pad if pad is not None else eos if eos is not None else 0)
+        return generate(self.model, input_ids, attention_mask, **kw)
+
+
 def _grouped_mean(tl, valid, rows, row_groups):
     """Mean of per-group token-means (``row_groups[rows]`` = group of each token), or the plain
     token-mean without groups."""

@@ -369,6 +369,27 @@ def _pack_rows(x):
     return x.reshape(-1, C).index_select(0, _PACK["idx"]).unsqueeze(1)
 
 
+# Text generation (models/generation.py). During the prefill of a ``KVCache`` every attention layer
+# copies its post-RoPE K and V into the cache on its way through the unchanged causal forward.
+_KV_PREFILL = {"cache": None}
+
+
+class kv_prefill:
+    """Context: attention layers store their K / V rows into ``cache`` (``KVCache.store_prefill``)."""
+
+    def __init__(self, cache):
+        self.cache = cache
+
+    def __enter__(self):
+        self.prev = _KV_PREFILL["cache"]
+        _KV_PREFILL["cache"] = self.cache
+        return self
+
+    def __exit__(self, *exc):
+        _KV_PREFILL["cache"] = self.prev
+        return False
+
+
 class ParallelAttention(nn.Module):
     def __init__(self, cfg: TransformerConfig, layer_number: int, device=None):
         super().__init__()
@@ -472,6 +493,18 @@ class ParallelAttention(nn.Module):
             return self.proj(_pack_rows(self._attend(_unpack_rows(qkv), training)))
         return self.proj(self._attend(qkv, training, doc_start))  # (out, bias)
 
+    def forward_decode(self, x, cache, layer: int):
+        """One new token per sequence, x [1, b, h], against ``cache`` (models/generation.KVCache):
+        QKV linear, RoPE at ``cache.pos`` and the append of K / V into that row of layer ``layer``'s
+        cache (decode_attn.hip), single-query attention over the ``cache.lens`` keys, projection.
+        Returns what ``forward`` returns."""
+        qkv = self.qkv(x)                                        # [1, b, (nh + 2 nkv) d]
+        b = qkv.shape[1]
+        k, v = cache.k[layer], cache.v[layer]
+        q = SF.decode_rope_append(qkv.view(b, -1), k, v, cache.pos, self.nh, self.nkv, self.hd, rope=self.rope)
+        ctx = SF.decode_attention(q, k, v, cache.lens, 1.0 / math.sqrt(self.hd), max_len=cache.max_len)
+        return self.proj(ctx.view(1, b, self.nh * self.hd))
+
     def _groups_ok(self, qkv) -> bool:
         g = _PACK.get("groups")
         W = qkv.shape[-1]
@@ -506,6 +539,8 @@ class ParallelAttention(nn.Module):
                 off = ps.get_state().cp_rank * qkv.shape[0]
                 cos, sin = cos[off: off + qkv.shape[0]], sin[off: off + qkv.shape[0]]
             qkv = _RopeQKV.apply(qkv, cos, sin, rot, self.nh, self.nkv, self.hd)
+        if _KV_PREFILL["cache"] is not None:
+            _KV_PREFILL["cache"].store_prefill(self, qkv)
         if cp > 1:
             return self.core_attention_context_parallel(qkv, training)
         if self.cfg.use_flash_attn:
@@ -784,6 +819,21 @@ class ParallelTransformerLayer(nn.Module):
         m, mb = self.mlp(ln2)
         return m, mb, residual
 
+    def forward_decode(self, x, xbias, residual, cache, layer: int):
+        """``forward`` for one new token per sequence against a K/V cache (no sequence parallelism):
+        the same norms and MLP, attention through ``ParallelAttention.forward_decode``."""
+        training = self.training
+        p = self.cfg.hidden_dropout
+        ln1, residual = self.input_norm.fused(x, xbias, residual, p, training)
+        if self.post_ln_residual:
+            residual = ln1
+        a, ab = self.attention.forward_decode(ln1, cache, layer)
+        ln2, residual = self.post_attention_norm.fused(a, ab, residual, p, training)
+        if self.post_ln_residual:
+            residual = ln2
+        m, mb = self.mlp(ln2)
+        return m, mb, residual
+
     def forward_phases(self, st):
         """``forward`` cut at its four sequence-parallel exchanges for the sub-batch interleave
         (``ParallelTransformer._forward_subbatch``): each phase ends right after it STARTS an
@@ -908,6 +958,14 @@ class ParallelTransformer(nn.Module):
         xbias = halves[0]["xbias"]
         residual = torch.cat([h["residual"] for h in halves], dim=1)
         return x, xbias, residual
+
+    def forward_decode(self, x, cache):
+        """The whole stack (it must own the final norm) on one new token per sequence, x [1, b, h],
+        against ``cache``: the normalised output [1, b, h]."""
+        xbias = residual = None
+        for i, layer in enumerate(self.layers):
+            x, xbias, residual = layer.forward_decode(x, xbias, residual, cache, i)
+        return self.final_norm.fused(x, xbias, residual, self.cfg.hidden_dropout, self.training)[0]
 
     def forward(self, x, xbias=None, residual=None, doc_start=None):
         """Returns (pending_x, pending_bias, residual) or, with ``final_norm``, the normalised

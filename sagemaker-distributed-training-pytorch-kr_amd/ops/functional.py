@@ -820,6 +820,110 @@ def apply_rope(x, cos, sin, pos_div: int, pos_mod: int, rot: Optional[int] = Non
 
 
 # --------------------------------------------------------------------------------------------
+# Incremental decoding (csrc/kernels/decode_attn.hip): one new token per sequence against a K/V
+# cache [B, cap, nkv, D]. Lengths and positions are device int32 [B] tensors and are never read on
+# the host, so a decode step has static shapes and can be captured in a graph.
+
+DECODE_CHUNK = 256      # keys per workgroup of the split-KV kernel (smdt_decode_attn_chunk)
+
+
+def decode_attention_supported(q, k_cache, v_cache=None) -> bool:
+    """The operands decode_attn.hip takes (smdt_decode_attn_supported in launchers.h): q [B, nh, D]
+    and caches [B, cap, nkv, D] of one 16-bit dtype, D in {64, 128}, nh / nkv in {1, 2, 4, 8}."""
+    if q.dim() != 3 or k_cache.dim() != 4 or q.dtype not in (torch.bfloat16, torch.float16):
+        return False
+    if k_cache.dtype != q.dtype or (v_cache is not None and (v_cache.dtype != q.dtype or v_cache.shape != k_cache.shape)):
+        return False
+    (B, nh, D), (Bk, cap, nkv, Dk) = q.shape, k_cache.shape
+    if B != Bk or D != Dk or D not in (64, 128) or B < 1 or cap < 1 or nkv < 1 or nh % nkv:
+        return False
+    return nh // nkv in (1, 2, 4, 8) and B <= 65535 and nkv <= 65535
+
+
+def decode_attention_ref(q, k_cache, v_cache, lens, scale, max_len=None):
+    """Torch twin of the kernel: softmax(scale q . K[:lens[b]]) V[:lens[b]] per sequence and head,
+    kv head h // (nh / nkv) serving query head h. fp32 math (float64 for float64 operands), one
+    rounding at the output. Rows at or beyond ``lens[b]`` are selected out before any arithmetic,
+    so NaN / Inf there cannot reach the result. ``max_len`` only bounds the kernel's grid."""
+    B, nh, D = q.shape
+    cap, nkv = k_cache.shape[1], k_cache.shape[2]
+    if nh % nkv:
+        raise ValueError(f"decode_attention: {nh} query heads are not a multiple of {nkv} kv heads")
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    valid = torch.arange(cap, device=q.device)[None, :] < lens[:, None]                       # [B, cap]
+    zero = torch.zeros((), dtype=ct, device=q.device)
+    kk = torch.where(valid[:, :, None, None], k_cache.to(ct), zero)
+    vv = torch.where(valid[:, :, None, None], v_cache.to(ct), zero)
+    qg = q.to(ct).view(B, nkv, nh // nkv, D)
+    s = torch.einsum("bkgd,bckd->bkgc", qg, kk) * scale
+    s = s.masked_fill(~valid[:, None, None, :], float("-inf"))
+    o = torch.einsum("bkgc,bckd->bkgd", torch.softmax(s, dim=-1), vv)
+    return o.reshape(B, nh, D).to(q.dtype)
+
+
+def decode_attention(q, k_cache, v_cache, lens, scale, max_len=None):
+    """Attention of one new query per sequence, q [B, nh, D], against the caches [B, cap, nkv, D]:
+    keys 0 .. lens[b] - 1 (``lens`` int32 [B] on q's device, the new token included). ``max_len``
+    (host int <= cap, default cap) only bounds the kernel's grid: every lens[b] must be <= it.
+    GPU operands run decode_attn.hip or raise (``decode_attention_supported``); CPU operands run
+    the torch twin."""
+    if not _ext.use_kernels(q, k_cache, v_cache):
+        return decode_attention_ref(q, k_cache, v_cache, lens, scale, max_len)
+    if not decode_attention_supported(q, k_cache, v_cache):
+        raise RuntimeError(f"decode_attention on the GPU needs bf16 / fp16 q [B, nh, D] and caches [B, cap, nkv, D] "
+                           f"of one dtype, D in (64, 128) and nh / nkv in (1, 2, 4, 8); got q {tuple(q.shape)} "
+                           f"{q.dtype}, k_cache {tuple(k_cache.shape)} {k_cache.dtype}, v_cache "
+                           f"{tuple(v_cache.shape)} {v_cache.dtype}")
+    cap = k_cache.shape[1]
+    max_len = cap if max_len is None else int(max_len)
+    if not 0 < max_len <= cap:
+        raise ValueError(f"decode_attention: max_len {max_len} must be in 1 .. the capacity {cap}")
+    return _ext.ext().decode_attn(q.contiguous(), k_cache, v_cache, lens, float(scale), max_len)
+
+
+def decode_rope_append_ref(qkv, k_cache, v_cache, pos, nh, nkv, hd, rope=None):
+    """Torch twin of ``decode_rope_append`` (``_rope_ref`` at position pos[b], index writes)."""
+    B = qkv.shape[0]
+    q = qkv[:, : nh * hd].reshape(B, nh, hd)
+    k = qkv[:, nh * hd:(nh + nkv) * hd].reshape(B, nkv, hd)
+    v = qkv[:, (nh + nkv) * hd:].reshape(B, nkv, hd)
+    p = pos.long()
+    if rope is not None:
+        cos, sin, rot = rope
+        q = _rope_ref(q, cos.to(qkv.device), sin.to(qkv.device), rot, p)
+        k = _rope_ref(k, cos.to(qkv.device), sin.to(qkv.device), rot, p)
+    rows = torch.arange(B, device=qkv.device)
+    k_cache[rows, p] = k.to(k_cache.dtype)
+    v_cache[rows, p] = v.to(v_cache.dtype)
+    return q.contiguous()
+
+
+def decode_rope_append(qkv, k_cache, v_cache, pos, nh, nkv, hd, rope=None):
+    """One new token per sequence: ``qkv`` [B, (nh + 2 nkv) hd] is the QKV projection's output,
+    ``pos`` int32 [B] (device) each token's position. q and k are rotated at pos[b] (``rope`` =
+    (cos, sin, rot) tables of the model, None: no RoPE), k and v are written into row pos[b] of the
+    caches [B, cap, nkv, hd] and q [B, nh, hd] is returned. The rotation is bit for bit what the
+    ``rope_`` kernel writes for the same row at the same position. GPU operands run the kernel or
+    raise; CPU operands run the torch twin."""
+    if qkv.dim() != 2 or qkv.shape[1] != (nh + 2 * nkv) * hd:
+        raise ValueError(f"decode_rope_append: qkv {tuple(qkv.shape)} is not [B, (nh + 2 nkv) hd] = "
+                         f"[B, {(nh + 2 * nkv) * hd}]")
+    if tuple(k_cache.shape[2:]) != (nkv, hd) or k_cache.shape != v_cache.shape or k_cache.shape[0] != qkv.shape[0]:
+        raise ValueError(f"decode_rope_append: caches {tuple(k_cache.shape)} / {tuple(v_cache.shape)} are not "
+                         f"[B, cap, {nkv}, {hd}]")
+    if not _ext.use_kernels(qkv, k_cache, v_cache):
+        return decode_rope_append_ref(qkv, k_cache, v_cache, pos, nh, nkv, hd, rope)
+    if qkv.dtype not in (torch.bfloat16, torch.float16) or k_cache.dtype != qkv.dtype or v_cache.dtype != qkv.dtype \
+            or hd % 8 or (rope is not None and rope[2] % 16):
+        raise RuntimeError(f"decode_rope_append on the GPU needs bf16 / fp16 qkv and caches of one dtype, hd % 8 == 0 "
+                           f"and a rotary dim % 16 == 0; got {qkv.dtype} / {k_cache.dtype} / {v_cache.dtype}, hd {hd}")
+    if rope is None:
+        return _ext.ext().decode_rope_append(qkv.contiguous(), k_cache, v_cache, pos, nh)
+    cos, sin, rot = rope
+    return _ext.ext().decode_rope_append(qkv.contiguous(), k_cache, v_cache, pos, nh, cos, sin, int(rot))
+
+
+# --------------------------------------------------------------------------------------------
 # (Vocab-parallel) cross entropy
 
 
