@@ -8,7 +8,18 @@ cache bytes the algorithm needs (2 * B * S * nkv * D * 2), computed here from th
 End to end: new tokens/s of ``generate`` on random-init built-in models, eager against
 ``use_graph=True`` (the prefill-only time, a 1-token call, is subtracted).
 
-    python benchmarks/bench_decode.py [--kernel] [--e2e] [--only llama-7b:8:4096] [--out decode.jsonl] [--quick]
+Linear (``--linear``): per decode-step GEMM shape of LLaMA-7B and OPT-125m and per M, the library
+path (``F.linear``, what a decode step calls without ``weight_format``) against
+``ops.functional.decode_linear`` (decode_linear.hip) in each weight format. Every timed call reads
+another copy of the weight out of a ring larger than the chip's last-level cache, as a decode step
+does (it streams every layer's weights once); bytes are the weight bytes of the format (elements
+plus scale bytes), computed here from the shape.
+
+``--e2e --weight-format F[,F...]`` adds ``generate(weight_format=F)`` beside the parent path (no
+format), alternating, with ``use_graph=True``.
+
+    python benchmarks/bench_decode.py [--kernel] [--e2e] [--linear] [--weight-format native,mxfp8,mxfp4]
+                                      [--only llama-7b:8:4096] [--out decode.jsonl] [--quick]
 
 One JSON line per measurement. Needs a GPU: there is no CPU fallback for a timing.
 """
@@ -86,6 +97,121 @@ def bench_kernel(emit, quick=False, only=None):
                 torch.cuda.empty_cache()
 
 
+LINEAR_SHAPES = {      # (N, K) of the decode step's GEMMs
+    "llama-7b": {"qkv": (12288, 4096), "proj": (4096, 4096), "fc1": (22016, 4096), "fc2": (4096, 11008),
+                 "head": (32000, 4096)},
+    "opt-125m": {"qkv": (2304, 768), "proj": (768, 768), "fc1": (3072, 768), "fc2": (768, 3072),
+                 "head": (50272, 768)},
+}
+COPY_RATE = 6.3e12          # what a streaming copy reaches (the yardstick of the fractions below)
+RING_BYTES = 768 << 20      # per format: beyond the 256 MB last-level cache several times over
+
+
+def _weight_bytes(N, K, fmt):
+    return N * K * 2 if fmt == "native" else N * K // (1 if fmt == "mxfp8" else 2) + N * K // 32
+
+
+def bench_linear(emit, quick=False, only=None):
+    from smdt_amd.ops import functional as SF
+    dev = torch.device("cuda", 0)
+    fmts = list(SF.DECODE_LINEAR_FORMATS)
+    for model, shapes in LINEAR_SHAPES.items():
+        for lname, (N, K) in shapes.items():
+            if only and only != f"{model}:{lname}":
+                continue
+            if quick and lname not in ("proj", "fc2"):
+                continue
+            ncopy = max(2, min(256, RING_BYTES // (N * K * 2)))
+            ws16 = [torch.empty(N, K, device=dev, dtype=torch.bfloat16).normal_(0, 0.02) for _ in range(ncopy)]
+            q8, s8 = SF.decode_weight_quantize(ws16[0], "mxfp8")
+            q4, s4 = SF.decode_weight_quantize(ws16[0], "mxfp4")
+            ring = {"native": [(w, None) for w in ws16],
+                    "mxfp8": [(q8.clone(), s8.clone()) for _ in range(max(2, min(256, RING_BYTES // (N * K))))],
+                    "mxfp4": [(q4.clone(), s4.clone()) for _ in range(max(2, min(256, 2 * RING_BYTES // (N * K))))]}
+            for M in (1, 2, 4, 8, 16):
+                x = torch.empty(M, K, device=dev, dtype=torch.bfloat16).normal_()
+                wsp = {f: (torch.empty(n, dtype=torch.float32, device=dev) if n else None)
+                       for f in fmts for n in [SF.decode_linear_workspace_numel(M, N, K, f)]}
+                pos = {"lib": 0, **{f: 0 for f in fmts}}
+
+                def lib():
+                    pos["lib"] = (pos["lib"] + 1) % len(ws16)
+                    return F.linear(x, ws16[pos["lib"]])
+
+                def ours(f):
+                    def run():
+                        pos[f] = (pos[f] + 1) % len(ring[f])
+                        w, sc = ring[f][pos[f]]
+                        return SF.decode_linear(x, w, sc, None, f, wsp[f])
+                    return run
+                fns = {"lib": lib, **{f: ours(f) for f in fmts}}
+                ref = F.linear(x, ws16[0]).float()
+                diff = {f: (SF.decode_linear(x, *ring[f][0], None, f, wsp[f]).float() - ref).abs().max().item()
+                        for f in fmts}
+                reps = max(20, min(400, int(0.05 / max(N * K * 2 / 2.5e12, 1e-5))))
+                for fn in fns.values():
+                    _time(fn, 5)
+                t = {n: [] for n in fns}
+                names = list(fns)
+                for r in range(4):                                             # alternate the order
+                    for n in (names if r % 2 == 0 else names[::-1]):
+                        t[n].append(_time(fns[n], reps))
+                best = {n: min(v) for n, v in t.items()}
+                rec = {"bench": "decode_linear", "model": model, "linear": lname, "N": N, "K": K, "M": M,
+                       "reps": reps, "ring_copies": {"native": len(ws16), "mxfp8": len(ring["mxfp8"]),
+                                                     "mxfp4": len(ring["mxfp4"])},
+                       "splits": {f: SF.decode_linear_plan(N, K, f)[0] for f in fmts},
+                       "lib_us": best["lib"] * 1e6, "lib_GBps": _weight_bytes(N, K, "native") / best["lib"] / 1e9,
+                       "max_abs_diff_vs_lib": diff, "runs_us": {n: [x_ * 1e6 for x_ in v] for n, v in t.items()}}
+                for f in fmts:
+                    b = _weight_bytes(N, K, f)
+                    rec[f + "_us"] = best[f] * 1e6
+                    rec[f + "_GBps"] = b / best[f] / 1e9
+                    rec[f + "_copy_rate_frac"] = b / best[f] / COPY_RATE
+                    rec["lib_over_" + f] = best["lib"] / best[f]
+                emit(rec)
+            del ws16, ring
+            torch.cuda.empty_cache()
+
+
+def bench_e2e_formats(emit, models, formats, quick=False):
+    """``generate`` (graph replay) on the parent path and under each weight format, alternating."""
+    from smdt_amd.models.hf import HFCausalLM
+    dev = torch.device("cuda", 0)
+    prompt, new = (32, 33) if quick else (128, 129)
+    for name in models:
+        model = HFCausalLM.from_pretrained(name, params_dtype=torch.bfloat16, device=dev).eval()
+        for B in (1, 8):
+            ids = torch.randint(3, 30000, (B, prompt), device=dev)
+
+            def run(fmt, n):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                model.generate(ids, max_new_tokens=n, eos_token_id=None, use_graph=True, weight_format=fmt)
+                torch.cuda.synchronize()
+                return time.perf_counter() - t0
+            arms = [None] + list(formats)
+            for f in arms:
+                run(f, new)                                 # warm up every shape, quantise once
+            full = {f: [] for f in arms}
+            pre = {f: [] for f in arms}
+            for r in range(3):
+                for f in (arms if r % 2 == 0 else arms[::-1]):
+                    run(f, 1)                               # a weight keeps one copy: re-made here, untimed
+                    full[f].append(run(f, new))
+                    pre[f].append(run(f, 1))
+            base = None
+            for f in arms:
+                tps = B * (new - 1) / (min(full[f]) - min(pre[f]))
+                base = tps if f is None else base
+                emit({"bench": "generate_weight_format", "model": name, "B": B, "prompt": prompt, "new_tokens": new,
+                      "weight_format": f, "use_graph": True, "call_s": min(full[f]), "prefill_call_s": min(pre[f]),
+                      "decode_tokens_per_s": tps, "ms_per_step": 1e3 * (min(full[f]) - min(pre[f])) / (new - 1),
+                      "over_parent": tps / base, "calls_s": full[f]})
+        del model
+        torch.cuda.empty_cache()
+
+
 def bench_e2e(emit, models, quick=False):
     from smdt_amd.models.hf import HFCausalLM
     dev = torch.device("cuda", 0)
@@ -118,9 +244,13 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--kernel", action="store_true")
     ap.add_argument("--e2e", action="store_true")
+    ap.add_argument("--linear", action="store_true", help="decode_linear against F.linear per shape and M")
+    ap.add_argument("--weight-format", default=None,
+                    help="with --e2e: comma-separated weight formats to run beside the parent path")
     ap.add_argument("--models", default="facebook/opt-125m,llama-7b")
     ap.add_argument("--quick", action="store_true", help="two small shapes only (a rehearsal)")
-    ap.add_argument("--only", default=None, help="one kernel shape, geometry:B:S (e.g. for a profiler run)")
+    ap.add_argument("--only", default=None, help="one kernel shape, geometry:B:S (e.g. for a profiler run); "
+                    "with --linear, model:linear (llama-7b:fc2)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -134,11 +264,16 @@ def main():
             out.write(line + "\n")
             out.flush()
 
-    both = not (args.kernel or args.e2e)
+    both = not (args.kernel or args.e2e or args.linear)
     with torch.no_grad():
         if args.kernel or both:
             bench_kernel(emit, args.quick, args.only)
-        if args.e2e or both:
+        if args.linear:
+            bench_linear(emit, args.quick, args.only)
+        if args.e2e and args.weight_format:
+            bench_e2e_formats(emit, [m for m in args.models.split(",") if m],
+                              [f for f in args.weight_format.split(",") if f], args.quick)
+        elif args.e2e or both:
             bench_e2e(emit, [m for m in args.models.split(",") if m], args.quick)
 
 

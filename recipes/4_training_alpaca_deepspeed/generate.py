@@ -2,12 +2,16 @@
 
     python generate.py --model_dir out --instruction "Name three primary colours." \
         [--input "..."] [--max_new_tokens 64] [--temperature 0.7 --top_p 0.9] [--graph]
+        [--weight_format {native,mxfp8,mxfp4}]
 
 ``--model_dir`` is a directory written by ``train.py`` (config.json + weights + tokenizer). The
 prompt is built from the templates the training data used (``smdt_amd.data.sft.PROMPT_DICT``) and
 continued with the KV-cache decoder (``HFCausalLM.generate``; greedy unless ``--temperature`` is
 given). The new token ids are printed, and the decoded text when the tokenizer can decode: the
-offline ``HashWordTokenizer`` hashes words to ids and cannot.
+offline ``HashWordTokenizer`` hashes words to ids and cannot. ``--weight_format`` (GPU) streams the
+layers' weights through the decode GEMM kernel: ``native`` reads the 16-bit parameters, ``mxfp8`` /
+``mxfp4`` (bf16 models) a block-scaled copy made once; the LM head stays 16-bit and the 16-bit
+parameters stay in memory.
 """
 import argparse
 import json
@@ -33,6 +37,8 @@ def main(argv=None):
     ap.add_argument("--top_p", type=float, default=1.0)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--graph", action="store_true", help="capture the decode step in a graph (GPU)")
+    ap.add_argument("--weight_format", choices=["native", "mxfp8", "mxfp4"], default=None,
+                    help="how the decode steps read the layers' weights (default: the model's own linears)")
     args = ap.parse_args(argv)
 
     gpu = torch.cuda.is_available()
@@ -52,7 +58,8 @@ def main(argv=None):
     sample = args.temperature > 0
     gen = torch.Generator(device=device).manual_seed(args.seed) if sample else None
     out = model.generate(ids, max_new_tokens=new, do_sample=sample, temperature=args.temperature if sample else 1.0,
-                         top_p=args.top_p, eos_token_id=eos, generator=gen, use_graph=args.graph)
+                         top_p=args.top_p, eos_token_id=eos, generator=gen, use_graph=args.graph,
+                         weight_format=args.weight_format)
     tokens = out[0, ids.shape[1]:].tolist()
     if eos is not None and eos in tokens:
         tokens = tokens[: tokens.index(eos) + 1]

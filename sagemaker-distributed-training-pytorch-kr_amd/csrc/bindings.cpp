@@ -1085,6 +1085,97 @@ Tensor decode_rope_append(Tensor qkv, Tensor k_cache, Tensor v_cache, Tensor pos
   return q;
 }
 
+// ------------------------------------------------------------------ decode linear (decode_linear.hip)
+// fmt: 0 native, 1 mxfp8, 2 mxfp4. The limits live in smdt_decode_linear_supported alone.
+bool decode_linear_supported(int64_t dtype, int64_t fmt, int64_t M, int64_t N, int64_t K) {
+  return fmt >= 0 && fmt <= 2 && smdt_decode_linear_supported((int)dtype, (int)fmt, M, N, K) != 0;
+}
+
+// {rows per workgroup, largest M, "split K below this many workgroups", k per workgroup step and
+// steps per unrolled iteration for fmt 0, 1, 2}
+std::vector<int64_t> decode_linear_constants() {
+  return {smdt_decode_linear_rows(), smdt_decode_linear_max_m(), smdt_decode_linear_split_below(),
+          smdt_decode_linear_step_k(0), smdt_decode_linear_step_k(1), smdt_decode_linear_step_k(2),
+          smdt_decode_linear_unroll(0), smdt_decode_linear_unroll(1), smdt_decode_linear_unroll(2)};
+}
+
+// (splits, slice length in k) of a weight [N, K] in format fmt
+std::vector<int64_t> decode_linear_plan(int64_t fmt, int64_t N, int64_t K) {
+  TORCH_CHECK(fmt >= 0 && fmt <= 2 && N >= 8 && K >= 32 && N < (1LL << 30) && K < (1LL << 30),
+              "decode_linear_plan: fmt ", fmt, ", N ", N, ", K ", K);
+  int s = 1, sl = 0;
+  smdt_decode_linear_plan((int)fmt, N, K, &s, &sl);
+  return {s, sl};
+}
+
+static bool aligned16(const Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0; }
+
+Tensor decode_linear(Tensor x, Tensor w, OptT scales, OptT bias, int64_t fmt, OptT workspace, OptT out_) {
+  need_contig(x, "x");
+  need_contig(w, "w");
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2, "decode_linear: x must be [M, K] and w 2-D");
+  TORCH_CHECK(fmt >= 0 && fmt <= 2, "decode_linear: fmt must be 0 (native), 1 (mxfp8) or 2 (mxfp4), got ", fmt);
+  const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf, "decode_linear: bf16 or fp16 x, got ",
+              x.scalar_type());
+  TORCH_CHECK(fmt == 0 || x.scalar_type() == at::kBFloat16,
+              "decode_linear: the quantised formats dequantise to bf16 (fp16 cannot hold the small blocks); x is ",
+              x.scalar_type());
+  TORCH_CHECK(decode_linear_supported(dcode(x), fmt, M, N, K), "decode_linear: unsupported M x N x K = ", M, " x ", N,
+              " x ", K, " (smdt_decode_linear_supported; the largest M is ", smdt_decode_linear_max_m(), ")");
+  TORCH_CHECK(w.device() == x.device(), "decode_linear: w is on another device");
+  const void* sp = nullptr;
+  if (fmt == 0) {
+    TORCH_CHECK(w.scalar_type() == x.scalar_type() && w.size(1) == K, "decode_linear: native w must be [N, K] of x's "
+                "dtype, got ", w.sizes(), " ", w.scalar_type());
+  } else {
+    TORCH_CHECK(scales.has_value(), "decode_linear: the quantised formats need scales");
+    need_contig(*scales, "scales");
+    TORCH_CHECK(scales->scalar_type() == at::kByte && scales->dim() == 2 && scales->size(0) == N &&
+                    scales->size(1) == K / 32 && scales->device() == x.device(),
+                "decode_linear: scales must be uint8 [N, K / 32] on x's device");
+    if (fmt == 1) {
+      TORCH_CHECK(w.scalar_type() == at::kFloat8_e4m3fn && w.size(1) == K, "decode_linear: mxfp8 w must be E4M3 [N, K]");
+    } else {
+      TORCH_CHECK(w.scalar_type() == at::kByte && w.size(1) == K / 2, "decode_linear: mxfp4 w must be uint8 [N, K / 2]");
+    }
+    sp = scales->data_ptr();
+  }
+  const void* bp = nullptr;
+  if (bias.has_value()) {
+    need_contig(*bias, "bias");
+    TORCH_CHECK(bias->scalar_type() == x.scalar_type() && bias->dim() == 1 && bias->size(0) == N &&
+                    bias->device() == x.device(), "decode_linear: bias must be [N] of x's dtype on its device");
+    bp = bias->data_ptr();
+  }
+  TORCH_CHECK(aligned16(x) && aligned16(w), "decode_linear: x and w must be 16-byte aligned");
+  int S = 1, slice = 0;
+  smdt_decode_linear_plan((int)fmt, N, K, &S, &slice);
+  float* wsp = nullptr;
+  if (S > 1) {
+    TORCH_CHECK(workspace.has_value(), "decode_linear: N ", N, " x K ", K, " splits K ", S,
+                " ways and needs a workspace of ", S * M * N, " fp32 elements");
+    TORCH_CHECK(workspace->scalar_type() == at::kFloat && workspace->is_contiguous() && workspace->device() == x.device() &&
+                    workspace->numel() >= S * M * N && aligned16(*workspace),
+                "decode_linear: the workspace must be contiguous fp32 on x's device with at least ", S * M * N, " elements");
+    wsp = workspace->data_ptr<float>();
+  }
+  Tensor out;
+  if (out_.has_value()) {
+    out = *out_;
+    need_contig(out, "out");
+    TORCH_CHECK(out.dim() == 2 && out.size(0) == M && out.size(1) == N && out.scalar_type() == x.scalar_type() &&
+                    out.device() == x.device() && aligned16(out),
+                "decode_linear: out must be a contiguous, 16-byte aligned [M, N] tensor of x's dtype on its device");
+  } else {
+    out = torch::empty({M, N}, x.options());
+  }
+  check(smdt_decode_linear(dcode(x), (int)fmt, x.data_ptr(), w.data_ptr(), sp, bp, out.data_ptr(), wsp, M, N, K,
+                           cur_stream()),
+        "decode_linear");
+  return out;
+}
+
 // `out` (optional) is a preallocated [B, S, H, D] view with any strides (e.g. the [s, b, h]
 // activation layout used by the transformer trunk). `doc_start` (optional, causal only) selects the
 // per-document kernels.
@@ -1459,6 +1550,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         arg("max_len") = 0);
   m.def("decode_rope_append", &decode_rope_append, arg("qkv"), arg("k_cache"), arg("v_cache"), arg("pos"), arg("nh"),
         arg("cos") = pybind11::none(), arg("sin") = pybind11::none(), arg("rot") = 0);
+  m.def("decode_linear_supported", &decode_linear_supported, arg("dtype"), arg("fmt"), arg("M"), arg("N"), arg("K"));
+  m.def("decode_linear_constants", &decode_linear_constants);
+  m.def("decode_linear_plan", &decode_linear_plan, arg("fmt"), arg("N"), arg("K"));
+  m.def("decode_linear", &decode_linear, arg("x"), arg("w"), arg("scales") = pybind11::none(),
+        arg("bias") = pybind11::none(), arg("fmt") = 0, arg("workspace") = pybind11::none(),
+        arg("out") = pybind11::none());
   m.def("window_attn_fwd", &window_attn_fwd, arg("qkv"), arg("table"), arg("window"), arg("shift"), arg("heads"));
   m.def("window_attn_bwd", &window_attn_bwd, arg("qkv"), arg("table"), arg("lse"), arg("dout"), arg("window"),
         arg("shift"), arg("heads"));

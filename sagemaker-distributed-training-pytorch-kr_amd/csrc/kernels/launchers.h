@@ -168,6 +168,23 @@ hipError_t smdt_decode_rope_append(int dtype, const void* qkv, void* q_out, void
                                    const int* pos, int B, int nh, int nkv, int D, int cap, int rot,
                                    const float* cos_t, const float* sin_t, int max_pos, hipStream_t st);
 
+// decode_linear.hip: weight-streaming out [M, N] = x [M, K] . W [N, K]^T (+ bias [N]) for decode steps
+// (M <= smdt_decode_linear_max_m()). fmt 0: W is the 16-bit parameter (x's dtype); 1: E4M3 bytes
+// [N, K] + E8M0 scales [N, K / 32] (mx_quant.hip's row form); 2: E2M1 nibbles [N, K / 2] (element
+// 2 j in the low nibble of byte j) + the same scales. x / bias / out bf16 or fp16 (fmt 0), bf16
+// (fmt 1, 2); N % 8 == 0, K % 32 == 0; x, W, out 16-byte aligned, ws too. smdt_decode_linear_plan
+// gives the K split: with splits > 1 the caller provides ws, fp32 [splits, M, N], and a second
+// launch sums it (no atomics). Anything unsupported returns hipErrorInvalidValue unlaunched.
+int smdt_decode_linear_rows();
+int smdt_decode_linear_max_m();
+int smdt_decode_linear_split_below();
+int smdt_decode_linear_step_k(int fmt);
+int smdt_decode_linear_unroll(int fmt);
+int smdt_decode_linear_supported(int dtype, int fmt, int64_t M, int64_t N, int64_t K);
+void smdt_decode_linear_plan(int fmt, int64_t N, int64_t K, int* splits, int* slice);
+hipError_t smdt_decode_linear(int dtype, int fmt, const void* x, const void* w, const void* scales, const void* bias,
+                              void* out, float* ws, int64_t M, int64_t N, int64_t K, hipStream_t st);
+
 // window_attn.hip: Swin shifted-window attention on the qkv linear's output over the padded,
 // unrolled grid, qkv [B, ph, pw, 3 heads d] read as (3, heads, d); roll, window partition and head
 // split are address arithmetic. table: fp32 [(2 ws - 1)^2, heads]. out [B, ph, pw, heads d] at the

@@ -22,6 +22,7 @@ import torch
 
 from ..ops import functional as SF
 from ..parallel import state as ps
+from ..parallel import tensor_parallel as tp
 from . import transformer as _T
 from .transformer import TransformerConfig
 
@@ -97,6 +98,33 @@ def _refuse(model, input_ids, attention_mask, max_new_tokens, cache):
                          f"exceeds the KV cache (batch {cache.batch}, capacity {cache.capacity})")
 
 
+def _decode_weights(model, weight_format):
+    """The ``tp.DecodeWeights`` of a ``generate(weight_format=...)`` call (None for None): every
+    refusal raises here, the quantised copies are made (or found in the cache) and the kernel's
+    workspace and the dequantisation scratch are allocated, all before the first decode step."""
+    if weight_format is None:
+        return None
+    if weight_format not in SF.DECODE_LINEAR_FORMATS:
+        raise ValueError(f"generate: weight_format must be None or one of {SF.DECODE_LINEAR_FORMATS}, "
+                         f"got {weight_format!r}")
+    cfg = model.cfg
+    if cfg.num_experts:
+        raise NotImplementedError(f"generate(weight_format={weight_format!r}): Switch MLP models (num_experts "
+                                  f"{cfg.num_experts}) are not supported")
+    head = model.output_weight if model.output_weight is not None else model.embedding.weight
+    linears = []
+    for name, mod in model.decoder.named_modules():
+        if isinstance(mod, (tp.ColumnParallelLinear, tp.RowParallelLinear)):
+            if mod._fp8 is not None:
+                raise RuntimeError(f"generate(weight_format={weight_format!r}): {name} carries _fp8 (an FP8 / MXFP8 "
+                                   "training linear); weight formats are for models with plain 16-bit linears")
+            linears.append((name, mod.weight, False))
+    linears.append(("the LM head", head, True))
+    state = tp.DecodeWeights(weight_format, head_weight=head)
+    state.prepare(linears)
+    return state
+
+
 def filter_logits(logits, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0):
     """fp32 logits [B, V] -> the logits sampling draws from: divided by the temperature, all but
     the ``top_k`` largest and everything outside the ``top_p`` nucleus (the smallest set of most
@@ -129,7 +157,7 @@ def _pick(logits, do_sample, temperature, top_k, top_p, generator):
 def generate(model, input_ids, attention_mask=None, max_new_tokens: int = 32, do_sample: bool = False,
              temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, eos_token_id: Optional[int] = None,
              pad_token_id: int = 0, generator: Optional[torch.Generator] = None, use_graph: bool = False,
-             cache: Optional[KVCache] = None):
+             cache: Optional[KVCache] = None, weight_format: Optional[str] = None):
     """Greedy or sampled continuation of the right-padded prompts ``input_ids`` [B, Lmax]
     (``attention_mask`` marks the real tokens; None: every row is Lmax long) with a KV cache.
 
@@ -139,15 +167,24 @@ def generate(model, input_ids, attention_mask=None, max_new_tokens: int = 32, do
     ``EOS_POLL_STEPS`` steps (no per-step synchronisation). Sampling (``do_sample``) draws from
     ``filter_logits`` over the real vocabulary (``model.loss_vocab_size``), so vocab padding columns
     are never returned. ``use_graph=True`` (GPU) captures one decode step and replays it.
-    ``cache``: a ``KVCache`` to reuse (its capacity must hold Lmax + max_new_tokens)."""
+    ``cache``: a ``KVCache`` to reuse (its capacity must hold Lmax + max_new_tokens).
+
+    ``weight_format``: None (the model's own linears), or how the layers' linears read their
+    weights: "native" streams the 16-bit parameters through the decode GEMM kernel
+    (csrc/kernels/decode_linear.hip) in steps of up to 16 sequences; "mxfp8" / "mxfp4" (bf16 models)
+    stream a cached block-scaled copy instead, and the prefill and batches above 16 run the
+    ordinary linear over the same dequantised values. The LM head always uses the native form; the
+    16-bit parameters stay resident and ``state_dict`` is unchanged."""
     _refuse(model, input_ids, attention_mask, max_new_tokens, cache)
+    state = _decode_weights(model, weight_format)
     if do_sample and temperature <= 0:
         raise ValueError(f"generate: temperature must be positive, got {temperature}")
     was_training = model.training
     model.eval()
     try:
-        return _generate(model, input_ids, attention_mask, int(max_new_tokens), do_sample, float(temperature),
-                         int(top_k), float(top_p), eos_token_id, int(pad_token_id), generator, use_graph, cache)
+        with tp.decode_weights(state):
+            return _generate(model, input_ids, attention_mask, int(max_new_tokens), do_sample, float(temperature),
+                             int(top_k), float(top_p), eos_token_id, int(pad_token_id), generator, use_graph, cache)
     finally:
         model.train(was_training)
 

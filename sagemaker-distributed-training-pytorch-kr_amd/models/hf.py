@@ -426,7 +426,9 @@ class HFCausalLM(nn.Module):
     def generate(self, input_ids, attention_mask=None, **kw):
         """KV-cache generation (``models.generation.generate``; same keyword arguments). The end-of-
         sequence and pad ids default to the HF config's (pad falls back to eos, then 0); pass
-        ``eos_token_id=None`` to generate ``max_new_tokens`` whatever is emitted."""
+        ``eos_token_id=None`` to generate ``max_new_tokens`` whatever is emitted.
+        ``weight_format="native" | "mxfp8" | "mxfp4"`` streams the layers' weights through the
+        decode GEMM kernel (see ``generate``); the default leaves the linears as they are."""
         from .generation import generate
         eos = self.hf_config.get("eos_token_id")
         kw.setdefault("eos_token_id", eos)

@@ -466,7 +466,8 @@ class ParallelAttention(nn.Module):
         16-bit linear) and a shape the kernels take as it is."""
         lin = self.qkv
         if (_PACK["idx"] is not None or self.rope is not None or not self.cfg.use_flash_attn
-                or ps.get_state().cp != 1 or lin._fp8 is not None or lin.sequence_parallel or lin.gather_output
+                or ps.get_state().cp != 1 or lin._fp8 is not None or tp.decode_quantised() or lin.sequence_parallel
+                or lin.gather_output
                 or lin.skip_bias_add or not torch.is_grad_enabled() or x.dim() != 3
                 or lin.bias is None or lin.weight.dtype != x.dtype or lin.bias.dtype != x.dtype):
             return None
@@ -628,7 +629,8 @@ class ParallelMLP(nn.Module):
     def forward(self, x):
         act = self.cfg.activation
         # FP8 linears take the unfused route: FP8 GEMM, then the bias-activation kernel
-        fused = act == "gelu" and self.cfg.bias_gelu_fusion and not self.cfg.fp8
+        # (nor under a quantised generation weight format: the fused forms would read the 16-bit weights)
+        fused = act == "gelu" and self.cfg.bias_gelu_fusion and not self.cfg.fp8 and not tp.decode_quantised()
         if fused:
             # the fused forms read fc1 / fc2 weights without calling fc1(x) / fc2(x)
             _gather_wait(self.fc1, x)

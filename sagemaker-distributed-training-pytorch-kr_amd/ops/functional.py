@@ -1254,6 +1254,185 @@ def gemm_mx(a, sa, b, sb, bias=None, out_dtype=torch.bfloat16, max_blocks: int =
 
 
 # --------------------------------------------------------------------------------------------
+# Decode linear (csrc/kernels/decode_linear.hip): y = x W^T (+ b) for the M <= 16 rows of a decode
+# step, streaming W once in one of three forms: "native" (the 16-bit parameter), "mxfp8" (the row
+# form of ``mx_quantize(w, "e4m3")``) and "mxfp4" (E2M1 nibbles [N, K / 2], element 2 j in the low
+# nibble of byte j, E8M0 scales [N, K / 32]). The quantised forms dequantise exactly to bf16, so the
+# kernel computes a bf16 linear over dequant(quant(W)) up to the summation order.
+
+DECODE_LINEAR_FORMATS = ("native", "mxfp8", "mxfp4")
+_DL_FMT = {"native": 0, "mxfp8": 1, "mxfp4": 2}
+FP4_EMAX = 2                 # exponent of E2M1's largest power of two (4; the largest value is 6)
+FP4_MAX = 6.0
+_FP4_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def _dl_fmt(fmt):
+    if fmt not in _DL_FMT:
+        raise ValueError(f"decode_linear: the weight format must be one of {DECODE_LINEAR_FORMATS}, got {fmt!r}")
+    return _DL_FMT[fmt]
+
+
+def mx4_quantize_ref(w, name: str = "the weight"):
+    """MXFP4 of w [N, K] (K % 32 == 0), the rule of ``mx_quantize_ref`` with E2M1 elements: per block
+    of 32 along K, a = max |v|, e = clamp(floor(log2 a) - 2, -127, 127) (0 when a == 0), s = e + 127,
+    element = RNE(v * 2^-e) on {0, .5, 1, 1.5, 2, 3, 4, 6} saturating at +-6 (ties to the even code).
+    Returns (q uint8 [N, K / 2], element 2 j in the low nibble of byte j; s uint8 [N, K / 32]).
+    FP4 has no NaN or Inf: a non-finite weight raises, naming ``name``. Runs on either device."""
+    if w.dim() != 2 or w.shape[1] < MX_BLOCK or w.shape[1] % MX_BLOCK:
+        raise ValueError(f"mx4_quantize: {name} must be [N, K multiple of 32], got {tuple(w.shape)}")
+    wf = w.detach().float()
+    if not bool(torch.isfinite(wf).all()):
+        raise ValueError(f"mx4_quantize: {name} holds NaN or Inf, which MXFP4 (E2M1) cannot represent")
+    N, K = wf.shape
+    b = wf.reshape(N, K // MX_BLOCK, MX_BLOCK)
+    a = b.abs().amax(dim=-1)
+    ex = (a.contiguous().view(torch.int32) >> 23) & 0xFF          # floor(log2 a) + 127
+    e = (ex - 127 - FP4_EMAX).clamp(-127, 127)
+    e = torch.where(a == 0, torch.zeros_like(e), e)
+    mult = ((127 - e) << 23).to(torch.int32).view(torch.float32)   # 2^-e, exact
+    v = (b * mult.unsqueeze(-1)).abs().clamp(max=FP4_MAX)
+    # torch.round is round-half-to-even; on each binade's grid an even multiple is an even code
+    code = torch.where(v < 2, torch.round(v * 2), torch.where(v < 4, torch.round(v) + 2, torch.round(v / 2) + 4))
+    code = code.to(torch.uint8) | (torch.signbit(b).to(torch.uint8) << 3)      # -0.0 keeps its sign
+    code = code.reshape(N, K // 2, 2)
+    q = code[..., 0] | (code[..., 1] << 4)
+    return q.contiguous(), (e + 127).to(torch.uint8)
+
+
+def _e8m0_to_f32(s):
+    """2^(s - 127) of E8M0 bytes, built from the exponent field (exact on every device; 0 is the
+    fp32 subnormal 2^-127, 255 the E8M0 NaN)."""
+    si = s.to(torch.int32)
+    bits = torch.where(si == 0, torch.full_like(si, 0x00400000), si << 23)
+    bits = torch.where(si == 255, torch.full_like(si, 0x7FC00000), bits)
+    return bits.view(torch.float32)
+
+
+def mx4_dequantize_ref(q, s):
+    """fp32 [N, K] of MXFP4 (q uint8 [N, K / 2], s uint8 [N, K / 32]): value(code) * 2^(s - 127)."""
+    N, K2 = q.shape
+    lut = torch.tensor(_FP4_VALUES + tuple(-x for x in _FP4_VALUES), dtype=torch.float32, device=q.device)
+    codes = torch.stack((q & 0xF, q >> 4), dim=-1).reshape(N, 2 * K2)
+    scale = _e8m0_to_f32(s)
+    return (lut[codes.long()].reshape(N, 2 * K2 // MX_BLOCK, MX_BLOCK) * scale.unsqueeze(-1)).reshape(N, 2 * K2)
+
+
+def decode_weight_quantize(w, fmt: str, name: str = "the weight"):
+    """(q, scales) of a weight [N, K] in the decode format ``fmt`` ("mxfp8" | "mxfp4"). mxfp8 uses the
+    ``mx_quantize`` kernel where it takes the weight and its torch twin (same bytes) elsewhere."""
+    if _dl_fmt(fmt) == 0:
+        raise ValueError("decode_weight_quantize: the native format has no quantised copy")
+    if w.dim() != 2 or w.shape[1] < MX_BLOCK or w.shape[1] % MX_BLOCK:
+        raise ValueError(f"decode_linear: {name} [{', '.join(map(str, w.shape))}] cannot take the {fmt} format: "
+                         f"the input size must be a multiple of {MX_BLOCK}")
+    if fmt == "mxfp4":
+        return mx4_quantize_ref(w, name)
+    w = w.detach()
+    if _ext.use_kernels(w) and w.dtype in (torch.bfloat16, torch.float16):
+        return mx_quantize(w, "e4m3")
+    return mx_quantize_ref(w, "e4m3")
+
+
+def decode_weight_dequantize_into(out, q, s, fmt: str):
+    """``out`` [N, K] (bf16, or fp32) = the dequantised weight, computed in ``out`` itself: every
+    value is exact in bf16 (a 1- or 3-bit mantissa times a power of two), so each step below is exact
+    and the result equals ``decode_weight_dequantize`` cast to ``out``'s dtype. No fp32 or index
+    tensor of the weight's size is built."""
+    N, K = out.shape
+    if fmt == "mxfp4":
+        for half in (0, 1):                          # element 2 j: low nibble of byte j
+            c = (q >> 4) if half else (q & 0xF)
+            mag, odd = c & 7, (c & 1).to(out.dtype)
+            # codes 0, 1: 0 and 0.5; codes 2 .. 7: (2 + odd) * {0.5, 1, 2}
+            v = torch.where(mag < 2, odd * 0.5,
+                            (2 + odd) * torch.where(mag < 4, 0.5, torch.where(mag < 6, 1.0, 2.0)).to(out.dtype))
+            out[:, half::2] = torch.where(c >= 8, -v, v)
+    else:
+        out.copy_(q)
+    out.view(N, K // MX_BLOCK, MX_BLOCK).mul_(_e8m0_to_f32(s).to(out.dtype).unsqueeze(-1))
+    return out
+
+
+def decode_weight_dequantize(q, s, fmt: str):
+    """fp32 [N, K] of a quantised decode weight."""
+    if fmt == "mxfp4":
+        return mx4_dequantize_ref(q, s)
+    N, K = q.shape
+    return (q.float().reshape(N, K // MX_BLOCK, MX_BLOCK) * _e8m0_to_f32(s).unsqueeze(-1)).reshape(N, K)
+
+
+def decode_linear_supported(M: int, N: int, K: int, dtype, fmt: str) -> bool:
+    """Whether decode_linear.hip takes x [M, K] of ``dtype`` against a weight [N, K] in ``fmt``:
+    the limits live in the kernel file alone (smdt_decode_linear_supported) and this asks it."""
+    code = {torch.bfloat16: 1, torch.float16: 2}.get(dtype)
+    if code is None or fmt not in _DL_FMT or not _ext.available():
+        return False
+    return bool(_ext.ext().decode_linear_supported(code, _DL_FMT[fmt], int(M), int(N), int(K)))
+
+
+def decode_linear_max_m() -> int:
+    """The largest M the kernel takes (0 without the extension: nothing runs on the kernel)."""
+    return int(_ext.ext().decode_linear_constants()[1]) if _ext.available() else 0
+
+
+def decode_linear_constants() -> dict:
+    """The kernel's tiling constants: rows of W per workgroup, the largest M, the workgroup count
+    below which K is split, and per format the k a workgroup covers per step and the steps per
+    unrolled iteration."""
+    c = [int(v) for v in _ext.ext().decode_linear_constants()]
+    return {"rows": c[0], "max_m": c[1], "split_below": c[2],
+            "step_k": dict(zip(DECODE_LINEAR_FORMATS, c[3:6])), "unroll": dict(zip(DECODE_LINEAR_FORMATS, c[6:9]))}
+
+
+def decode_linear_plan(N: int, K: int, fmt: str):
+    """(splits, slice length) of the kernel's K split for a weight [N, K]."""
+    s, sl = _ext.ext().decode_linear_plan(_dl_fmt(fmt), int(N), int(K))
+    return int(s), int(sl)
+
+
+def decode_linear_workspace_numel(M: int, N: int, K: int, fmt: str) -> int:
+    """fp32 elements of workspace ``decode_linear`` needs for this shape (0: no split)."""
+    s, _ = decode_linear_plan(N, K, fmt)
+    return s * int(M) * int(N) if s > 1 else 0
+
+
+def decode_linear_ref(x, w, scales=None, bias=None, fmt: str = "native"):
+    """Torch twin: the linear of x's dtype over the dequantised weight."""
+    if _dl_fmt(fmt) != 0:
+        w = decode_weight_dequantize(w, scales, fmt).to(x.dtype)
+    return F.linear(x, w, bias)
+
+
+def decode_linear(x, w, scales=None, bias=None, fmt: str = "native", workspace=None, out=None):
+    """y [..., N] = x [..., K] W^T (+ bias) with W in ``fmt`` (see the section comment; ``scales`` for
+    the quantised formats). GPU operands run decode_linear.hip or raise
+    (``decode_linear_supported``); ``workspace``: fp32, at least ``decode_linear_workspace_numel``
+    elements, needed when the kernel splits K; ``out``: a [M, N] tensor to write (default: a new
+    one). CPU operands run the torch twin."""
+    f = _dl_fmt(fmt)
+    if f != 0 and scales is None:
+        raise ValueError(f"decode_linear: the {fmt} format needs its scales")
+    if not _ext.use_kernels(x, w):
+        y = decode_linear_ref(x, w, scales, bias, fmt)
+        return y if out is None else out.copy_(y.view(out.shape))
+    if f != 0 and x.dtype == torch.float16:
+        raise ValueError(f"decode_linear: the {fmt} format is for bf16 models: its blocks dequantise to bf16, and "
+                         "fp16 cannot hold the small ones")
+    K = x.shape[-1]
+    M = x.numel() // K
+    N = w.shape[0]
+    if not decode_linear_supported(M, N, K, x.dtype, fmt):
+        raise RuntimeError(f"decode_linear: the kernel does not take M x N x K = {M} x {N} x {K}, {x.dtype}, {fmt} "
+                           f"(decode_linear_supported; the largest M is {decode_linear_max_m()})")
+    x2 = x.reshape(M, K)
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    y = _ext.ext().decode_linear(x2, w, scales, bias, f, workspace, out)
+    return y.view(tuple(x.shape[:-1]) + (N,))
+
+
+# --------------------------------------------------------------------------------------------
 # Switch MLP without host syncs (--moe-grouped-gemm): device routing into an expert-sorted,
 # tile-padded row layout, and expert GEMMs that pick their weight per 256-row tile on the device
 # (csrc/kernels/moe_route.hip, gemm_tn.hip GROUPED, wgrad_gemm.hip wgrad_ranged_kernel).
