@@ -18,7 +18,13 @@ plus scale bytes), computed here from the shape.
 ``--e2e --weight-format F[,F...]`` adds ``generate(weight_format=F)`` beside the parent path (no
 format), alternating, with ``use_graph=True``.
 
+``--kv-format mxfp8`` (with ``--kernel``): ``decode_attention_mx`` (decode_attn_mx.hip) on an MXFP8
+cache against ``decode_attention`` on the 16-bit cache of the same shape, same protocol; bytes are
+2 * B * S * nkv * (D + D / 32). With ``--e2e``: ``generate(kv_cache_format=...)`` beside the 16-bit
+cache on LLaMA-7B with a long prompt (``--kv-e2e B:S[,B:S...]``, default 8:3968,64:3968; Llama-2-7B geometry, 4096 positions).
+
     python benchmarks/bench_decode.py [--kernel] [--e2e] [--linear] [--weight-format native,mxfp8,mxfp4]
+                                      [--kv-format mxfp8] [--kv-e2e 8:4096]
                                       [--only llama-7b:8:4096] [--out decode.jsonl] [--quick]
 
 One JSON line per measurement. Needs a GPU: there is no CPU fallback for a timing.
@@ -95,6 +101,95 @@ def bench_kernel(emit, quick=False, only=None):
                       "max_abs_diff": diff, "reps": reps})
                 del q, k, v
                 torch.cuda.empty_cache()
+
+
+def bench_kernel_kv(emit, fmt, quick=False, only=None):
+    """``decode_attention_mx`` on an MXFP8 cache against ``decode_attention`` on the 16-bit cache."""
+    from smdt_amd.ops import functional as SF
+    assert fmt in SF.KV_CACHE_FORMATS, fmt
+    dev = torch.device("cuda", 0)
+    for name, (nh, nkv, D) in GEOMETRIES.items():
+        for B in (1, 8, 64):
+            for S in (1024, 4096, 16384):
+                if quick and (B, S) not in ((1, 1024), (8, 4096)):
+                    continue
+                if only and only != f"{name}:{B}:{S}":
+                    continue
+                q = torch.empty(B, nh, D, device=dev, dtype=torch.bfloat16).normal_()
+                k = torch.empty(B, S, nkv, D, device=dev, dtype=torch.bfloat16).normal_()
+                v = torch.empty(B, S, nkv, D, device=dev, dtype=torch.bfloat16).normal_()
+                kq = torch.empty(B, S, nkv, D, device=dev, dtype=torch.float8_e4m3fn)
+                vq = torch.empty_like(kq)
+                ks = torch.empty(B, S, nkv, D // 32, device=dev, dtype=torch.uint8)
+                vs = torch.empty_like(ks)
+                SF.kv_store_mx(k, v, kq, ks, vq, vs)
+                lens = torch.full((B,), S, dtype=torch.int32, device=dev)
+                scale = 1.0 / math.sqrt(D)
+
+                def base():
+                    return SF.decode_attention(q, k, v, lens, scale)
+
+                def mx():
+                    return SF.decode_attention_mx(q, kq, ks, vq, vs, lens, scale)
+
+                diff = (mx().float() - base().float()).abs().max().item()
+                b16, bmx = 2 * B * S * nkv * D * 2, 2 * B * S * nkv * (D + D // 32)
+                reps = max(5, min(200, int(0.1 / max(b16 / 4e12, 2e-5))))
+                for fn in (base, mx):
+                    _time(fn, 3)
+                t = {"bf16": [], fmt: []}
+                for r in range(4):                                             # alternate the order
+                    order = (("bf16", base), (fmt, mx)) if r % 2 == 0 else ((fmt, mx), ("bf16", base))
+                    for n, fn in order:
+                        t[n].append(_time(fn, reps))
+                tb, tm = min(t["bf16"]), min(t[fmt])
+                emit({"bench": "decode_attention_kv_format", "kv_format": fmt, "geometry": name, "nh": nh, "nkv": nkv,
+                      "D": D, "B": B, "S": S, "kv_bytes_16bit": b16, "kv_bytes": bmx, "bf16_us": tb * 1e6,
+                      "mx_us": tm * 1e6, "bf16_over_mx": tb / tm, "bf16_GBps": b16 / tb / 1e9, "mx_GBps": bmx / tm / 1e9,
+                      "bf16_runs_us": [x * 1e6 for x in t["bf16"]], "mx_runs_us": [x * 1e6 for x in t[fmt]],
+                      "max_abs_diff_vs_16bit_cache": diff, "reps": reps})
+                del q, k, v, kq, ks, vq, vs
+                torch.cuda.empty_cache()
+
+
+def bench_e2e_kv(emit, fmt, cases, new=65):
+    """``generate`` (graph replay) on LLaMA-7B with the 16-bit cache and with ``fmt``, alternating;
+    the prefill-only time (a 1-token call) is subtracted. Reports the cache bytes allocated."""
+    from smdt_amd.models.generation import KVCache
+    from smdt_amd.models.hf import HFCausalLM
+    dev = torch.device("cuda", 0)
+    model = HFCausalLM.from_pretrained("meta-llama/Llama-2-7b-hf", params_dtype=torch.bfloat16, device=dev).eval()
+    for B, S in cases:
+        ids = torch.randint(3, 30000, (B, S), device=dev)
+        arms = [None, fmt]
+        caches = {f: KVCache(model.model.cfg, B, S + new, device=dev, format=f) for f in arms}
+        nbytes = {f: sum(t.numel() * t.element_size() for t in c.k + c.v + getattr(c, "k_scale", []) +
+                         getattr(c, "v_scale", [])) for f, c in caches.items()}
+
+        def run(f, n):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            model.generate(ids, max_new_tokens=n, eos_token_id=None, use_graph=True, cache=caches[f])
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0
+        for f in arms:
+            run(f, new)
+        full = {f: [] for f in arms}
+        pre = {f: [] for f in arms}
+        for r in range(2):
+            for f in (arms if r % 2 == 0 else arms[::-1]):
+                full[f].append(run(f, new))
+                pre[f].append(run(f, 1))
+        base = None
+        for f in arms:
+            step = (min(full[f]) - min(pre[f])) / (new - 1)
+            base = step if f is None else base
+            emit({"bench": "generate_kv_cache_format", "model": "llama-2-7b", "B": B, "prompt": S, "new_tokens": new,
+                  "kv_cache_format": f, "use_graph": True, "cache_bytes": nbytes[f], "ms_per_step": 1e3 * step,
+                  "decode_tokens_per_s": B / step, "over_16bit": base / step, "calls_s": full[f],
+                  "prefill_calls_s": pre[f]})
+        del caches
+        torch.cuda.empty_cache()
 
 
 LINEAR_SHAPES = {      # (N, K) of the decode step's GEMMs
@@ -247,6 +342,9 @@ def main():
     ap.add_argument("--linear", action="store_true", help="decode_linear against F.linear per shape and M")
     ap.add_argument("--weight-format", default=None,
                     help="with --e2e: comma-separated weight formats to run beside the parent path")
+    ap.add_argument("--kv-format", default=None, help="with --kernel: decode_attention_mx against decode_attention; "
+                    "with --e2e: generate(kv_cache_format=...) against the 16-bit cache on LLaMA-7B")
+    ap.add_argument("--kv-e2e", default="8:3968,64:3968", help="B:S cases of --e2e --kv-format")
     ap.add_argument("--models", default="facebook/opt-125m,llama-7b")
     ap.add_argument("--quick", action="store_true", help="two small shapes only (a rehearsal)")
     ap.add_argument("--only", default=None, help="one kernel shape, geometry:B:S (e.g. for a profiler run); "
@@ -266,6 +364,12 @@ def main():
 
     both = not (args.kernel or args.e2e or args.linear)
     with torch.no_grad():
+        if args.kv_format:
+            if args.kernel or both:
+                bench_kernel_kv(emit, args.kv_format, args.quick, args.only)
+            if args.e2e:
+                bench_e2e_kv(emit, args.kv_format, [tuple(int(x) for x in c.split(":")) for c in args.kv_e2e.split(",")])
+            return
         if args.kernel or both:
             bench_kernel(emit, args.quick, args.only)
         if args.linear:

@@ -2,7 +2,7 @@
 
     python generate.py --model_dir out --instruction "Name three primary colours." \
         [--input "..."] [--max_new_tokens 64] [--temperature 0.7 --top_p 0.9] [--graph]
-        [--weight_format {native,mxfp8,mxfp4}]
+        [--weight_format {native,mxfp8,mxfp4}] [--kv_cache_format {mxfp8}]
 
 ``--model_dir`` is a directory written by ``train.py`` (config.json + weights + tokenizer). The
 prompt is built from the templates the training data used (``smdt_amd.data.sft.PROMPT_DICT``) and
@@ -11,7 +11,8 @@ given). The new token ids are printed, and the decoded text when the tokenizer c
 offline ``HashWordTokenizer`` hashes words to ids and cannot. ``--weight_format`` (GPU) streams the
 layers' weights through the decode GEMM kernel: ``native`` reads the 16-bit parameters, ``mxfp8`` /
 ``mxfp4`` (bf16 models) a block-scaled copy made once; the LM head stays 16-bit and the 16-bit
-parameters stay in memory.
+parameters stay in memory. ``--kv_cache_format mxfp8`` keeps the K/V cache as MXFP8 (E4M3 elements,
+one scale byte per 32: 51.6 % of the 16-bit cache; head dimension 64 or 128).
 """
 import argparse
 import json
@@ -39,6 +40,8 @@ def main(argv=None):
     ap.add_argument("--graph", action="store_true", help="capture the decode step in a graph (GPU)")
     ap.add_argument("--weight_format", choices=["native", "mxfp8", "mxfp4"], default=None,
                     help="how the decode steps read the layers' weights (default: the model's own linears)")
+    ap.add_argument("--kv_cache_format", choices=["mxfp8"], default=None,
+                    help="how the K/V cache is stored (default: the model dtype)")
     args = ap.parse_args(argv)
 
     gpu = torch.cuda.is_available()
@@ -59,7 +62,7 @@ def main(argv=None):
     gen = torch.Generator(device=device).manual_seed(args.seed) if sample else None
     out = model.generate(ids, max_new_tokens=new, do_sample=sample, temperature=args.temperature if sample else 1.0,
                          top_p=args.top_p, eos_token_id=eos, generator=gen, use_graph=args.graph,
-                         weight_format=args.weight_format)
+                         weight_format=args.weight_format, kv_cache_format=args.kv_cache_format)
     tokens = out[0, ids.shape[1]:].tolist()
     if eos is not None and eos in tokens:
         tokens = tokens[: tokens.index(eos) + 1]

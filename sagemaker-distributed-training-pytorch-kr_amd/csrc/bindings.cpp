@@ -1048,6 +1048,33 @@ Tensor decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor lens, double
   return out;
 }
 
+// cos / sin (fp32 [max_pos, rot / 2]) of an op that rotates the first rot elements (rot == 0: none).
+struct RopeTables {
+  const float *cos = nullptr, *sin = nullptr;
+  int64_t max_pos = 0;
+};
+static RopeTables dec_rope_tables(const OptT& cos_t, const OptT& sin_t, int64_t rot, int64_t D, const Tensor& qkv,
+                                  const char* what) {
+  RopeTables rt;
+  if (rot > 0) {
+    TORCH_CHECK(cos_t.has_value() && sin_t.has_value(), what, ": rot > 0 needs the cos / sin tables");
+    need_contig(*cos_t, "cos");
+    need_contig(*sin_t, "sin");
+    TORCH_CHECK(cos_t->scalar_type() == at::kFloat && sin_t->scalar_type() == at::kFloat && cos_t->dim() == 2 &&
+                    sin_t->sizes() == cos_t->sizes() && cos_t->device() == qkv.device() &&
+                    sin_t->device() == qkv.device(),
+                what, ": fp32 [max_pos, rot / 2] tables on qkv's device");
+    TORCH_CHECK(rot <= D && rot % 16 == 0 && cos_t->size(1) == rot / 2, what, ": rotary dim mismatch");
+    rt.max_pos = cos_t->size(0);
+    TORCH_CHECK(rt.max_pos < (1LL << 31), what, ": table too long");
+    rt.cos = cos_t->data_ptr<float>();
+    rt.sin = sin_t->data_ptr<float>();
+  } else {
+    TORCH_CHECK(rot == 0, what, ": negative rotary dim");
+  }
+  return rt;
+}
+
 // qkv [B, (nh + 2 nkv) D] -> q [B, nh, D]; k / v written into row pos[b] of the caches. cos / sin
 // (fp32 [max_pos, rot / 2]) and rot > 0 rotate q and k; without them the op is a copy.
 Tensor decode_rope_append(Tensor qkv, Tensor k_cache, Tensor v_cache, Tensor pos, int64_t nh, OptT cos_t,
@@ -1059,29 +1086,83 @@ Tensor decode_rope_append(Tensor qkv, Tensor k_cache, Tensor v_cache, Tensor pos
   TORCH_CHECK(nh > 0 && nh < (1 << 20) && D % 8 == 0 && D < (1 << 20) && qkv.size(1) == (nh + 2 * nkv) * D,
               "decode_rope_append: qkv width ", qkv.size(1), " is not (nh + 2 nkv) D with D % 8 == 0");
   const int* pp = dec_index(pos, qkv, "decode_rope_append");
-  const float *cp = nullptr, *sp = nullptr;
-  int64_t max_pos = 0;
-  if (rot > 0) {
-    TORCH_CHECK(cos_t.has_value() && sin_t.has_value(), "decode_rope_append: rot > 0 needs the cos / sin tables");
-    need_contig(*cos_t, "cos");
-    need_contig(*sin_t, "sin");
-    TORCH_CHECK(cos_t->scalar_type() == at::kFloat && sin_t->scalar_type() == at::kFloat && cos_t->dim() == 2 &&
-                    sin_t->sizes() == cos_t->sizes() && cos_t->device() == qkv.device() &&
-                    sin_t->device() == qkv.device(),
-                "decode_rope_append: fp32 [max_pos, rot / 2] tables on qkv's device");
-    TORCH_CHECK(rot <= D && rot % 16 == 0 && cos_t->size(1) == rot / 2, "decode_rope_append: rotary dim mismatch");
-    max_pos = cos_t->size(0);
-    TORCH_CHECK(max_pos < (1LL << 31), "decode_rope_append: table too long");
-    cp = cos_t->data_ptr<float>();
-    sp = sin_t->data_ptr<float>();
-  } else {
-    TORCH_CHECK(rot == 0, "decode_rope_append: negative rotary dim");
-  }
+  const RopeTables rt = dec_rope_tables(cos_t, sin_t, rot, D, qkv, "decode_rope_append");
   auto q = torch::empty({B, nh, D}, qkv.options());
   check(smdt_decode_rope_append(dcode(qkv), qkv.data_ptr(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-                                pp, (int)B, (int)nh, (int)nkv, (int)D, (int)cap, (int)rot, cp, sp, (int)max_pos,
-                                cur_stream()),
+                                pp, (int)B, (int)nh, (int)nkv, (int)D, (int)cap, (int)rot, rt.cos, rt.sin,
+                                (int)rt.max_pos, cur_stream()),
         "decode_rope_append");
+  return q;
+}
+
+// ------------------------------------------------------------------ MXFP8 K/V cache (decode_attn_mx.hip)
+// kq / vq [B, cap, nkv, D] E4M3, ksc / vsc [B, cap, nkv, D / 32] uint8 E8M0; q / qkv stay 16-bit.
+static bool aligned16(const Tensor& t);
+static void dec_check_cache_mx(const Tensor& kq, const Tensor& ks, const Tensor& vq, const Tensor& vs,
+                               const Tensor& like, const char* what) {
+  TORCH_CHECK(like.scalar_type() == at::kBFloat16 || like.scalar_type() == at::kHalf, what,
+              ": bf16 or fp16 q / qkv, got ", like.scalar_type());
+  for (const Tensor* t : {&kq, &ks, &vq, &vs}) {
+    TORCH_CHECK(t->is_cuda() && t->device() == like.device() && t->is_contiguous() && t->dim() == 4 && aligned16(*t),
+                what, ": the cache tensors must be contiguous, 16-byte aligned and 4-D on the new token's device");
+  }
+  TORCH_CHECK(kq.scalar_type() == at::kFloat8_e4m3fn && vq.scalar_type() == at::kFloat8_e4m3fn &&
+                  ks.scalar_type() == at::kByte && vs.scalar_type() == at::kByte,
+              what, ": the cache must be float8_e4m3fn elements and uint8 (E8M0) scales");
+  const int64_t D = kq.size(3);
+  TORCH_CHECK(D % 32 == 0 && vq.sizes() == kq.sizes() && vs.sizes() == ks.sizes() && ks.size(0) == kq.size(0) &&
+                  ks.size(1) == kq.size(1) && ks.size(2) == kq.size(2) && ks.size(3) == D / 32 &&
+                  kq.size(0) == like.size(0),
+              what, ": the cache must be q [B, cap, nkv, D] and s [B, cap, nkv, D / 32] with D % 32 == 0");
+  TORCH_CHECK(kq.size(1) > 0 && kq.size(1) < (1LL << 31) && kq.size(0) <= 65535 && kq.size(2) <= 65535, what,
+              ": cache shape out of range");
+}
+
+Tensor decode_attn_mx(Tensor q, Tensor kq, Tensor ks, Tensor vq, Tensor vs, Tensor lens, double scale,
+                      int64_t max_len) {
+  need_contig(q, "q");
+  TORCH_CHECK(q.dim() == 3, "decode_attn_mx: q must be [B, nh, D]");
+  dec_check_cache_mx(kq, ks, vq, vs, q, "decode_attn_mx");
+  const int64_t B = q.size(0), nh = q.size(1), D = q.size(2), cap = kq.size(1), nkv = kq.size(2);
+  TORCH_CHECK(kq.size(3) == D, "decode_attn_mx: head dim of q and the cache differ");
+  TORCH_CHECK(decode_attn_supported(dcode(q), D, nh, nkv),
+              "decode_attn_mx: unsupported (needs D in {64, 128} and nh / nkv in {1, 2, 4, 8}): D ", D, ", nh ", nh,
+              ", nkv ", nkv);
+  TORCH_CHECK(aligned16(q), "decode_attn_mx: q must be 16-byte aligned");
+  if (max_len <= 0) max_len = cap;
+  TORCH_CHECK(max_len <= cap, "decode_attn_mx: max_len ", max_len, " exceeds the cache capacity ", cap);
+  const int* lp = dec_index(lens, q, "decode_attn_mx");
+  const int64_t C = smdt_decode_attn_chunk();
+  const int64_t nchunks = (max_len + C - 1) / C;
+  auto f32 = q.options().dtype(at::kFloat);
+  auto ws_ml = torch::empty({B, nh, nchunks, 2}, f32);
+  auto ws_acc = torch::empty({B, nh, nchunks, D}, f32);
+  auto out = torch::empty_like(q);
+  check(smdt_decode_attn_mx(dcode(q), q.data_ptr(), kq.data_ptr(), ks.data_ptr(), vq.data_ptr(), vs.data_ptr(), lp,
+                            ws_ml.data_ptr<float>(), ws_acc.data_ptr<float>(), out.data_ptr(), (int)B, (int)nh,
+                            (int)nkv, (int)D, (int)cap, (int)max_len, (float)scale, cur_stream()),
+        "decode_attn_mx");
+  return out;
+}
+
+Tensor decode_rope_append_mx(Tensor qkv, Tensor kq, Tensor ks, Tensor vq, Tensor vs, Tensor pos, int64_t nh,
+                             OptT cos_t, OptT sin_t, int64_t rot) {
+  need_contig(qkv, "qkv");
+  TORCH_CHECK(qkv.dim() == 2, "decode_rope_append_mx: qkv must be [B, (nh + 2 nkv) D]");
+  dec_check_cache_mx(kq, ks, vq, vs, qkv, "decode_rope_append_mx");
+  const int64_t B = qkv.size(0), cap = kq.size(1), nkv = kq.size(2), D = kq.size(3);
+  TORCH_CHECK(nh > 0 && nh < (1 << 20) && D < (1 << 20) && qkv.size(1) == (nh + 2 * nkv) * D,
+              "decode_rope_append_mx: qkv width ", qkv.size(1), " is not (nh + 2 nkv) D");
+  TORCH_CHECK(nkv * D <= 8192, "decode_rope_append_mx: nkv * D = ", nkv * D, " exceeds 8192 (the kernel stages the "
+              "token's k and v rows in LDS)");
+  TORCH_CHECK(aligned16(qkv), "decode_rope_append_mx: qkv must be 16-byte aligned");
+  const int* pp = dec_index(pos, qkv, "decode_rope_append_mx");
+  const RopeTables rt = dec_rope_tables(cos_t, sin_t, rot, D, qkv, "decode_rope_append_mx");
+  auto q = torch::empty({B, nh, D}, qkv.options());
+  check(smdt_decode_rope_append_mx(dcode(qkv), qkv.data_ptr(), q.data_ptr(), kq.data_ptr(), ks.data_ptr(),
+                                   vq.data_ptr(), vs.data_ptr(), pp, (int)B, (int)nh, (int)nkv, (int)D, (int)cap,
+                                   (int)rot, rt.cos, rt.sin, (int)rt.max_pos, cur_stream()),
+        "decode_rope_append_mx");
   return q;
 }
 
@@ -1550,6 +1631,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         arg("max_len") = 0);
   m.def("decode_rope_append", &decode_rope_append, arg("qkv"), arg("k_cache"), arg("v_cache"), arg("pos"), arg("nh"),
         arg("cos") = pybind11::none(), arg("sin") = pybind11::none(), arg("rot") = 0);
+  m.def("decode_attn_mx", &decode_attn_mx, arg("q"), arg("kq"), arg("ks"), arg("vq"), arg("vs"), arg("lens"),
+        arg("scale"), arg("max_len") = 0);
+  m.def("decode_rope_append_mx", &decode_rope_append_mx, arg("qkv"), arg("kq"), arg("ks"), arg("vq"), arg("vs"),
+        arg("pos"), arg("nh"), arg("cos") = pybind11::none(), arg("sin") = pybind11::none(), arg("rot") = 0);
   m.def("decode_linear_supported", &decode_linear_supported, arg("dtype"), arg("fmt"), arg("M"), arg("N"), arg("K"));
   m.def("decode_linear_constants", &decode_linear_constants);
   m.def("decode_linear_plan", &decode_linear_plan, arg("fmt"), arg("N"), arg("K"));

@@ -328,3 +328,21 @@ extern "C" hipError_t smdt_decode_rope_append(int dtype, const void* qkv, void* 
                        max_pos, 1.f);
   return hipGetLastError();
 }
+
+// The combine launch alone, for partials written by another kernel with this file's workspace
+// layout and chunk length (decode_attn_mx.hip).
+extern "C" hipError_t smdt_decode_attn_combine(int dtype, const float* ws_ml, const float* ws_acc, const int* lens,
+                                               void* out, int B, int nh, int D, int cap, int nchunks, hipStream_t st) {
+  if ((dtype != 1 && dtype != 2) || (D != 64 && D != 128) || B <= 0 || B > 65535 || nh <= 0 || cap <= 0 ||
+      nchunks <= 0)
+    return hipErrorInvalidValue;
+  const dim3 grid((unsigned)nh, (unsigned)B);
+  if (dtype == 1) {
+    if (D == 64) hipLaunchKernelGGL((decode_attn_combine_kernel<bf16, 64>), grid, dim3(64), 0, st, ws_ml, ws_acc, lens, (bf16*)out, cap, nchunks);
+    else hipLaunchKernelGGL((decode_attn_combine_kernel<bf16, 128>), grid, dim3(128), 0, st, ws_ml, ws_acc, lens, (bf16*)out, cap, nchunks);
+  } else {
+    if (D == 64) hipLaunchKernelGGL((decode_attn_combine_kernel<f16, 64>), grid, dim3(64), 0, st, ws_ml, ws_acc, lens, (f16*)out, cap, nchunks);
+    else hipLaunchKernelGGL((decode_attn_combine_kernel<f16, 128>), grid, dim3(128), 0, st, ws_ml, ws_acc, lens, (f16*)out, cap, nchunks);
+  }
+  return hipGetLastError();
+}

@@ -167,6 +167,21 @@ hipError_t smdt_decode_attn(int dtype, const void* q, const void* k_cache, const
 hipError_t smdt_decode_rope_append(int dtype, const void* qkv, void* q_out, void* k_cache, void* v_cache,
                                    const int* pos, int B, int nh, int nkv, int D, int cap, int rot,
                                    const float* cos_t, const float* sin_t, int max_pos, hipStream_t st);
+// The second launch of smdt_decode_attn alone, over partials in its workspace layout.
+hipError_t smdt_decode_attn_combine(int dtype, const float* ws_ml, const float* ws_acc, const int* lens, void* out,
+                                    int B, int nh, int D, int cap, int nchunks, hipStream_t st);
+
+// decode_attn_mx.hip: the same two operations against an MXFP8 cache: kq / vq [B, cap, nkv, D] E4M3
+// bytes, ksc / vsc [B, cap, nkv, D / 32] E8M0 bytes (mx_quant.hip's row form of every 16-bit row),
+// all contiguous and 16-byte aligned. q / qkv / out stay bf16 / fp16. Attention: the limits,
+// workspaces and guarantees of smdt_decode_attn. Append: D % 32 == 0 and nkv * D <= 8192 (the k and
+// v rows are staged in LDS); k and v are rounded to the 16-bit dtype before they are quantised.
+hipError_t smdt_decode_attn_mx(int dtype, const void* q, const void* kq, const void* ksc, const void* vq,
+                               const void* vsc, const int* lens, float* ws_ml, float* ws_acc, void* out, int B,
+                               int nh, int nkv, int D, int cap, int max_len, float scale, hipStream_t st);
+hipError_t smdt_decode_rope_append_mx(int dtype, const void* qkv, void* q_out, void* kq, void* ksc, void* vq,
+                                      void* vsc, const int* pos, int B, int nh, int nkv, int D, int cap, int rot,
+                                      const float* cos_t, const float* sin_t, int max_pos, hipStream_t st);
 
 // decode_linear.hip: weight-streaming out [M, N] = x [M, K] . W [N, K]^T (+ bias [N]) for decode steps
 // (M <= smdt_decode_linear_max_m()). fmt 0: W is the 16-bit parameter (x's dtype); 1: E4M3 bytes

@@ -13,6 +13,12 @@ decode_attn.hip). ``lens`` and ``pos`` live on the device and advance there once
 kernel and no Python code of a step reads a length on the host, so with the static shapes
 (``max_len = capacity``) a step can be captured in a graph (``use_graph=True``,
 ``train.graphs.CapturedStep``).
+
+``kv_cache_format="mxfp8"`` stores the cache as MXFP8 (E4M3 elements and one E8M0 scale byte per 32,
+51.6 % of the 16-bit bytes; ``ops.functional.KV_CACHE_FORMATS``): every row is the MX quantisation
+of the 16-bit row the default cache would have held, written by the prefill store and by the
+quantising append, and read by csrc/kernels/decode_attn_mx.hip. The prefill's own attention still
+runs on the 16-bit K / V through flash attention.
 """
 from __future__ import annotations
 
@@ -29,17 +35,46 @@ from .transformer import TransformerConfig
 EOS_POLL_STEPS = 16     # the host asks whether every row has finished at most this often
 
 
+def _check_kv_format(cfg: TransformerConfig, fmt, who: str):
+    """Every refusal of a ``kv_cache_format``, naming the cause, before anything is allocated."""
+    if fmt is None:
+        return
+    if fmt not in SF.KV_CACHE_FORMATS:
+        raise ValueError(f"{who}: kv_cache_format must be None or one of {SF.KV_CACHE_FORMATS}, got {fmt!r}")
+    D, nh, nkv = cfg.kv_channels, cfg.num_attention_heads, cfg.num_query_groups
+    if D % SF.MX_BLOCK:
+        raise ValueError(f"{who}: kv_cache_format {fmt!r} needs a head dimension that is a multiple of "
+                         f"{SF.MX_BLOCK} (one scale per {SF.MX_BLOCK} elements), got {D}")
+    if D not in (64, 128) or nh % nkv or nh // nkv not in (1, 2, 4, 8):
+        raise ValueError(f"{who}: kv_cache_format {fmt!r} needs a head dimension in (64, 128) and "
+                         f"num_attention_heads / num_query_groups in (1, 2, 4, 8) (the decode kernel's set), got "
+                         f"head dimension {D} and {nh} / {nkv}")
+    if nkv * D > SF._KV_MX_MAX_ROW:
+        raise ValueError(f"{who}: kv_cache_format {fmt!r} needs num_query_groups * head dimension <= "
+                         f"{SF._KV_MX_MAX_ROW} (the append kernel's staged row), got {nkv * D}")
+
+
 class KVCache:
     """Per-layer K / V of shape [B, capacity, nkv, D], ``lens`` (int32 [B], device: the valid keys
-    of each sequence) and ``pos`` (int32 [B]: the row the current step's token is written to)."""
+    of each sequence) and ``pos`` (int32 [B]: the row the current step's token is written to).
+    ``format="mxfp8"``: ``k`` / ``v`` hold float8_e4m3fn elements and ``k_scale`` / ``v_scale``
+    [B, capacity, nkv, D / 32] their uint8 E8M0 scales (``dtype`` is then unused)."""
 
-    def __init__(self, cfg: TransformerConfig, batch: int, capacity: int, dtype=None, device=None):
+    def __init__(self, cfg: TransformerConfig, batch: int, capacity: int, dtype=None, device=None, format=None):
         if batch < 1 or capacity < 1:
             raise ValueError(f"KVCache: batch {batch} and capacity {capacity} must be positive")
+        _check_kv_format(cfg, format, "KVCache")
         self.batch, self.capacity = int(batch), int(capacity)
         self.max_len = self.capacity          # bounds the decode kernel's grid (static: capturable)
+        self.format = format
         dtype = dtype or cfg.params_dtype
         shape = (self.batch, self.capacity, cfg.num_query_groups, cfg.kv_channels)
+        if format is not None:
+            dtype = torch.float8_e4m3fn
+            sshape = shape[:3] + (cfg.kv_channels // SF.MX_BLOCK,)
+            # scale byte 127 is 2^0: an unwritten row reads as zeros, as in the 16-bit cache
+            self.k_scale = [torch.full(sshape, 127, dtype=torch.uint8, device=device) for _ in range(cfg.num_layers)]
+            self.v_scale = [torch.full(sshape, 127, dtype=torch.uint8, device=device) for _ in range(cfg.num_layers)]
         self.k = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(cfg.num_layers)]
         self.v = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(cfg.num_layers)]
         self.lens = torch.zeros(self.batch, dtype=torch.int32, device=device)
@@ -53,6 +88,9 @@ class KVCache:
             raise RuntimeError(f"KVCache: a prompt batch [{B}, {L}] does not fit the cache "
                                f"[{self.batch}, capacity {self.capacity}]")
         _, k, v = SF._qkv_views(qkv, attn.nh, attn.nkv, attn.hd, True)            # [B, L, nkv, D]
+        if self.format is not None:
+            i = attn.layer_number
+            return SF.kv_store_mx(k, v, self.k[i], self.k_scale[i], self.v[i], self.v_scale[i])
         self.k[attn.layer_number][:, :L].copy_(k)
         self.v[attn.layer_number][:, :L].copy_(v)
 
@@ -62,7 +100,7 @@ class KVCache:
         self.lens.add_(1)
 
 
-def _refuse(model, input_ids, attention_mask, max_new_tokens, cache):
+def _refuse(model, input_ids, attention_mask, max_new_tokens, cache, kv_cache_format=None):
     """Everything generation does not do raises here, naming the cause."""
     cfg = model.cfg
     st = ps.get_state()
@@ -96,6 +134,10 @@ def _refuse(model, input_ids, attention_mask, max_new_tokens, cache):
     if cache is not None and (cache.batch != B or total > cache.capacity):
         raise ValueError(f"generate: prompt length {L} + max_new_tokens {max_new_tokens} = {total} for batch {B} "
                          f"exceeds the KV cache (batch {cache.batch}, capacity {cache.capacity})")
+    _check_kv_format(cfg, kv_cache_format, "generate")
+    if cache is not None and kv_cache_format is not None and cache.format != kv_cache_format:
+        raise ValueError(f"generate: kv_cache_format {kv_cache_format!r} disagrees with the passed cache, whose format "
+                         f"is {cache.format!r}")
 
 
 def _decode_weights(model, weight_format):
@@ -157,7 +199,8 @@ def _pick(logits, do_sample, temperature, top_k, top_p, generator):
 def generate(model, input_ids, attention_mask=None, max_new_tokens: int = 32, do_sample: bool = False,
              temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, eos_token_id: Optional[int] = None,
              pad_token_id: int = 0, generator: Optional[torch.Generator] = None, use_graph: bool = False,
-             cache: Optional[KVCache] = None, weight_format: Optional[str] = None):
+             cache: Optional[KVCache] = None, weight_format: Optional[str] = None,
+             kv_cache_format: Optional[str] = None):
     """Greedy or sampled continuation of the right-padded prompts ``input_ids`` [B, Lmax]
     (``attention_mask`` marks the real tokens; None: every row is Lmax long) with a KV cache.
 
@@ -174,8 +217,13 @@ def generate(model, input_ids, attention_mask=None, max_new_tokens: int = 32, do
     (csrc/kernels/decode_linear.hip) in steps of up to 16 sequences; "mxfp8" / "mxfp4" (bf16 models)
     stream a cached block-scaled copy instead, and the prefill and batches above 16 run the
     ordinary linear over the same dequantised values. The LM head always uses the native form; the
-    16-bit parameters stay resident and ``state_dict`` is unchanged."""
-    _refuse(model, input_ids, attention_mask, max_new_tokens, cache)
+    16-bit parameters stay resident and ``state_dict`` is unchanged.
+
+    ``kv_cache_format``: None (a cache in the model dtype) or "mxfp8": K and V are stored as MXFP8,
+    the MX quantisation of the 16-bit rows, at 51.6 % of the bytes (head dimension 64 or 128,
+    heads / kv heads in 1, 2, 4, 8; bf16 and fp16 models). A passed ``cache`` keeps its own format;
+    naming a different one here raises. Independent of ``weight_format`` and ``use_graph``."""
+    _refuse(model, input_ids, attention_mask, max_new_tokens, cache, kv_cache_format)
     state = _decode_weights(model, weight_format)
     if do_sample and temperature <= 0:
         raise ValueError(f"generate: temperature must be positive, got {temperature}")
@@ -184,13 +232,14 @@ def generate(model, input_ids, attention_mask=None, max_new_tokens: int = 32, do
     try:
         with tp.decode_weights(state):
             return _generate(model, input_ids, attention_mask, int(max_new_tokens), do_sample, float(temperature),
-                             int(top_k), float(top_p), eos_token_id, int(pad_token_id), generator, use_graph, cache)
+                             int(top_k), float(top_p), eos_token_id, int(pad_token_id), generator, use_graph, cache,
+                             kv_cache_format)
     finally:
         model.train(was_training)
 
 
 def _generate(model, input_ids, attention_mask, max_new, do_sample, temperature, top_k, top_p, eos, pad, generator,
-              use_graph, cache):
+              use_graph, cache, kv_cache_format=None):
     cfg = model.cfg
     dev = input_ids.device
     B, L = input_ids.shape
@@ -200,7 +249,7 @@ def _generate(model, input_ids, attention_mask, max_new, do_sample, temperature,
     else:
         plen = attention_mask.to(dev).long().sum(dim=1)
     if cache is None:
-        cache = KVCache(cfg, B, L + max_new, cfg.params_dtype, dev)
+        cache = KVCache(cfg, B, L + max_new, cfg.params_dtype, dev, format=kv_cache_format)
 
     seq = torch.full((B, L + max_new), pad, dtype=input_ids.dtype, device=dev)
     keep = torch.arange(L, device=dev)[None, :] < plen[:, None]

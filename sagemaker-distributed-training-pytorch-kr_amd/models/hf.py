@@ -428,7 +428,8 @@ class HFCausalLM(nn.Module):
         sequence and pad ids default to the HF config's (pad falls back to eos, then 0); pass
         ``eos_token_id=None`` to generate ``max_new_tokens`` whatever is emitted.
         ``weight_format="native" | "mxfp8" | "mxfp4"`` streams the layers' weights through the
-        decode GEMM kernel (see ``generate``); the default leaves the linears as they are."""
+        decode GEMM kernel (see ``generate``); the default leaves the linears as they are.
+        ``kv_cache_format="mxfp8"`` keeps the K/V cache as MXFP8; the default is the model dtype."""
         from .generation import generate
         eos = self.hf_config.get("eos_token_id")
         kw.setdefault("eos_token_id", eos)

@@ -498,10 +498,18 @@ class ParallelAttention(nn.Module):
         """One new token per sequence, x [1, b, h], against ``cache`` (models/generation.KVCache):
         QKV linear, RoPE at ``cache.pos`` and the append of K / V into that row of layer ``layer``'s
         cache (decode_attn.hip), single-query attention over the ``cache.lens`` keys, projection.
-        Returns what ``forward`` returns."""
+        ``cache.format`` picks the op pair: the 16-bit one, or the MXFP8 one. Returns what
+        ``forward`` returns."""
         qkv = self.qkv(x)                                        # [1, b, (nh + 2 nkv) d]
         b = qkv.shape[1]
         k, v = cache.k[layer], cache.v[layer]
+        if cache.format is not None:                             # MXFP8 cache (decode_attn_mx.hip)
+            ks, vs = cache.k_scale[layer], cache.v_scale[layer]
+            q = SF.decode_rope_append_mx(qkv.view(b, -1), k, ks, v, vs, cache.pos, self.nh, self.nkv, self.hd,
+                                         rope=self.rope)
+            ctx = SF.decode_attention_mx(q, k, ks, v, vs, cache.lens, 1.0 / math.sqrt(self.hd),
+                                         max_len=cache.max_len)
+            return self.proj(ctx.view(1, b, self.nh * self.hd))
         q = SF.decode_rope_append(qkv.view(b, -1), k, v, cache.pos, self.nh, self.nkv, self.hd, rope=self.rope)
         ctx = SF.decode_attention(q, k, v, cache.lens, 1.0 / math.sqrt(self.hd), max_len=cache.max_len)
         return self.proj(ctx.view(1, b, self.nh * self.hd))

@@ -881,20 +881,25 @@ def decode_attention(q, k_cache, v_cache, lens, scale, max_len=None):
     return _ext.ext().decode_attn(q.contiguous(), k_cache, v_cache, lens, float(scale), max_len)
 
 
-def decode_rope_append_ref(qkv, k_cache, v_cache, pos, nh, nkv, hd, rope=None):
-    """Torch twin of ``decode_rope_append`` (``_rope_ref`` at position pos[b], index writes)."""
+def _decode_rope_rows(qkv, pos, nh, nkv, hd, rope):
+    """q [B, nh, hd], k and v [B, nkv, hd] of the new tokens, q / k rotated at pos[b] (``_rope_ref``)."""
     B = qkv.shape[0]
     q = qkv[:, : nh * hd].reshape(B, nh, hd)
     k = qkv[:, nh * hd:(nh + nkv) * hd].reshape(B, nkv, hd)
     v = qkv[:, (nh + nkv) * hd:].reshape(B, nkv, hd)
-    p = pos.long()
     if rope is not None:
         cos, sin, rot = rope
-        q = _rope_ref(q, cos.to(qkv.device), sin.to(qkv.device), rot, p)
-        k = _rope_ref(k, cos.to(qkv.device), sin.to(qkv.device), rot, p)
-    rows = torch.arange(B, device=qkv.device)
-    k_cache[rows, p] = k.to(k_cache.dtype)
-    v_cache[rows, p] = v.to(v_cache.dtype)
+        q = _rope_ref(q, cos.to(qkv.device), sin.to(qkv.device), rot, pos.long())
+        k = _rope_ref(k, cos.to(qkv.device), sin.to(qkv.device), rot, pos.long())
+    return q, k, v
+
+
+def decode_rope_append_ref(qkv, k_cache, v_cache, pos, nh, nkv, hd, rope=None):
+    """Torch twin of ``decode_rope_append`` (``_rope_ref`` at position pos[b], index writes)."""
+    q, k, v = _decode_rope_rows(qkv, pos, nh, nkv, hd, rope)
+    rows = torch.arange(qkv.shape[0], device=qkv.device)
+    k_cache[rows, pos.long()] = k.to(k_cache.dtype)
+    v_cache[rows, pos.long()] = v.to(v_cache.dtype)
     return q.contiguous()
 
 
@@ -921,6 +926,159 @@ def decode_rope_append(qkv, k_cache, v_cache, pos, nh, nkv, hd, rope=None):
         return _ext.ext().decode_rope_append(qkv.contiguous(), k_cache, v_cache, pos, nh)
     cos, sin, rot = rope
     return _ext.ext().decode_rope_append(qkv.contiguous(), k_cache, v_cache, pos, nh, cos, sin, int(rot))
+
+
+# --------------------------------------------------------------------------------------------
+# MXFP8 K/V cache (csrc/kernels/decode_attn_mx.hip, generate(kv_cache_format="mxfp8")). K and V of
+# a layer are each stored as q [B, cap, nkv, D] float8_e4m3fn and s [B, cap, nkv, D / 32] uint8
+# (E8M0, bias 127): a (sequence, position, kv head) row of D elements is D / 32 MX blocks and its
+# bytes are ``mx_quantize_ref(row, "e4m3")`` of the row a 16-bit cache would have stored (the
+# post-RoPE K, and V, in the model dtype). A value is q * 2^(s - 127) (``_e8m0_to_f32``). No
+# calibration and no state: a row's bytes depend on that row alone, so the prefill and the decode
+# step write the same bytes for the same token. (D + D / 32) / 2 D = 51.6 % of the 16-bit cache.
+
+KV_CACHE_FORMATS = ("mxfp8",)
+_KV_MX_MAX_ROW = 8192        # nkv * D the append kernel stages in LDS (smdt_decode_rope_append_mx)
+
+
+def _kv_mx_shapes(kq, ks, vq, vs, name):
+    """(B, cap, nkv, D) of an MXFP8 cache after checking the four tensors against each other."""
+    if kq.dim() != 4 or kq.shape[3] % MX_BLOCK or kq.shape[3] < MX_BLOCK:
+        raise ValueError(f"{name}: the cache elements {tuple(kq.shape)} are not [B, cap, nkv, D] with D a multiple "
+                         f"of {MX_BLOCK}")
+    B, cap, nkv, D = kq.shape
+    if vq.shape != kq.shape or tuple(ks.shape) != (B, cap, nkv, D // MX_BLOCK) or vs.shape != ks.shape:
+        raise ValueError(f"{name}: k / v elements {tuple(kq.shape)} / {tuple(vq.shape)} and scales {tuple(ks.shape)} / "
+                         f"{tuple(vs.shape)} are not [B, cap, nkv, D] and [B, cap, nkv, D / {MX_BLOCK}]")
+    if kq.dtype != torch.float8_e4m3fn or vq.dtype != torch.float8_e4m3fn or ks.dtype != torch.uint8 \
+            or vs.dtype != torch.uint8:
+        raise ValueError(f"{name}: an MXFP8 cache is float8_e4m3fn elements and uint8 scales, got {kq.dtype} / "
+                         f"{vq.dtype} and {ks.dtype} / {vs.dtype}")
+    return B, cap, nkv, D
+
+
+def kv_dequantize_mx(q, s):
+    """fp32 [..., D] of MXFP8 cache rows (q [..., D] E4M3, s [..., D / 32] E8M0): q * 2^(s - 127), exact."""
+    D = q.shape[-1]
+    v = q.float().unflatten(-1, (D // MX_BLOCK, MX_BLOCK)) * _e8m0_to_f32(s).unsqueeze(-1)
+    return v.flatten(-2)
+
+
+def _kv_quantize_rows(x):
+    """``mx_quantize_ref`` of rows x [..., D]: (uint8 view of the E4M3 bytes [..., D], scales [..., D / 32])."""
+    D = x.shape[-1]
+    q, s = mx_quantize_ref(x.reshape(-1, D), "e4m3")
+    return q.view(torch.uint8).reshape(x.shape), s.reshape(*x.shape[:-1], D // MX_BLOCK)
+
+
+def decode_attention_mx_supported(q, kq, ks, vq, vs) -> bool:
+    """The operands decode_attn_mx.hip takes: q [B, nh, D] bf16 / fp16 against an MXFP8 cache
+    (elements [B, cap, nkv, D], scales [B, cap, nkv, D / 32]), D in {64, 128}, nh / nkv in
+    {1, 2, 4, 8}: the limits of ``decode_attention_supported``."""
+    if q.dim() != 3 or q.dtype not in (torch.bfloat16, torch.float16):
+        return False
+    try:
+        Bk, cap, nkv, Dk = _kv_mx_shapes(kq, ks, vq, vs, "decode_attention_mx")
+    except ValueError:
+        return False
+    B, nh, D = q.shape
+    if B != Bk or D != Dk or D not in (64, 128) or B < 1 or cap < 1 or nkv < 1 or nh % nkv:
+        return False
+    return nh // nkv in (1, 2, 4, 8) and B <= 65535 and nkv <= 65535
+
+
+def decode_attention_mx_ref(q, kq, ks, vq, vs, lens, scale, max_len=None):
+    """Torch twin of ``decode_attention_mx`` and its definition: ``decode_attention_ref`` on the
+    dequantised cache (fp32, exact). Rows at or beyond ``lens[b]`` are selected out there, elements
+    and scales alike."""
+    _kv_mx_shapes(kq, ks, vq, vs, "decode_attention_mx")
+    return decode_attention_ref(q, kv_dequantize_mx(kq, ks), kv_dequantize_mx(vq, vs), lens, scale, max_len)
+
+
+def decode_attention_mx(q, kq, ks, vq, vs, lens, scale, max_len=None):
+    """``decode_attention`` against an MXFP8 cache: q [B, nh, D] (bf16 / fp16), K as ``kq``
+    [B, cap, nkv, D] float8_e4m3fn with ``ks`` [B, cap, nkv, D / 32] uint8, V likewise; ``lens`` and
+    ``max_len`` as there. The cache is dequantised in fp32 in registers, so fp16 models are served
+    too. GPU operands run decode_attn_mx.hip or raise (``decode_attention_mx_supported``); CPU
+    operands run the torch twin."""
+    if not _ext.use_kernels(q, kq, vq):
+        return decode_attention_mx_ref(q, kq, ks, vq, vs, lens, scale, max_len)
+    _kv_mx_shapes(kq, ks, vq, vs, "decode_attention_mx")
+    if not decode_attention_mx_supported(q, kq, ks, vq, vs):
+        raise RuntimeError(f"decode_attention_mx on the GPU needs bf16 / fp16 q [B, nh, D], an MXFP8 cache "
+                           f"[B, cap, nkv, D], D in (64, 128) and nh / nkv in (1, 2, 4, 8); got q {tuple(q.shape)} "
+                           f"{q.dtype}, cache {tuple(kq.shape)}")
+    cap = kq.shape[1]
+    max_len = cap if max_len is None else int(max_len)
+    if not 0 < max_len <= cap:
+        raise ValueError(f"decode_attention_mx: max_len {max_len} must be in 1 .. the capacity {cap}")
+    return _ext.ext().decode_attn_mx(q.contiguous(), kq, ks, vq, vs, lens, float(scale), max_len)
+
+
+def decode_rope_append_mx_ref(qkv, kq, ks, vq, vs, pos, nh, nkv, hd, rope=None):
+    """Torch twin of ``decode_rope_append_mx`` and its definition: ``decode_rope_append_ref``'s q, and
+    ``mx_quantize_ref`` of the k / v rows it stores (in qkv's dtype) into row pos[b]."""
+    q, k, v = _decode_rope_rows(qkv, pos, nh, nkv, hd, rope)
+    rows = torch.arange(qkv.shape[0], device=qkv.device)
+    for x, qc, sc in ((k.to(qkv.dtype), kq, ks), (v, vq, vs)):
+        qb, sb = _kv_quantize_rows(x)
+        qc.view(torch.uint8)[rows, pos.long()] = qb
+        sc[rows, pos.long()] = sb
+    return q.contiguous()
+
+
+def decode_rope_append_mx(qkv, kq, ks, vq, vs, pos, nh, nkv, hd, rope=None):
+    """``decode_rope_append`` into an MXFP8 cache: q [B, nh, hd] comes back in qkv's dtype with the
+    bytes ``decode_rope_append`` returns; k (rotated) and v are rounded to qkv's dtype, quantised per
+    32-block (``mx_quantize_ref``) and written, elements and scale bytes, into row pos[b]. A position
+    outside the cache writes nothing. GPU operands run decode_attn_mx.hip or raise; CPU operands
+    run the torch twin."""
+    if qkv.dim() != 2 or qkv.shape[1] != (nh + 2 * nkv) * hd:
+        raise ValueError(f"decode_rope_append_mx: qkv {tuple(qkv.shape)} is not [B, (nh + 2 nkv) hd] = "
+                         f"[B, {(nh + 2 * nkv) * hd}]")
+    B, cap, ckv, D = _kv_mx_shapes(kq, ks, vq, vs, "decode_rope_append_mx")
+    if (ckv, D) != (nkv, hd) or B != qkv.shape[0]:
+        raise ValueError(f"decode_rope_append_mx: the cache {tuple(kq.shape)} is not [{qkv.shape[0]}, cap, {nkv}, {hd}]")
+    if not _ext.use_kernels(qkv, kq, vq):
+        return decode_rope_append_mx_ref(qkv, kq, ks, vq, vs, pos, nh, nkv, hd, rope)
+    if qkv.dtype not in (torch.bfloat16, torch.float16) or (rope is not None and rope[2] % 16):
+        raise RuntimeError(f"decode_rope_append_mx on the GPU needs bf16 / fp16 qkv and a rotary dim % 16 == 0; got "
+                           f"{qkv.dtype}, rotary dim {None if rope is None else rope[2]}")
+    if nkv * hd > _KV_MX_MAX_ROW:
+        raise RuntimeError(f"decode_rope_append_mx: nkv * hd = {nkv * hd} exceeds {_KV_MX_MAX_ROW}, the k / v row the "
+                           "kernel stages in LDS")
+    if rope is None:
+        return _ext.ext().decode_rope_append_mx(qkv.contiguous(), kq, ks, vq, vs, pos, nh)
+    cos, sin, rot = rope
+    return _ext.ext().decode_rope_append_mx(qkv.contiguous(), kq, ks, vq, vs, pos, nh, cos, sin, int(rot))
+
+
+def kv_store_mx_ref(k, v, kq, ks, vq, vs):
+    """Torch twin of ``kv_store_mx``: ``mx_quantize_ref`` of every row."""
+    L = k.shape[1]
+    for x, qc, sc in ((k, kq, ks), (v, vq, vs)):
+        qb, sb = _kv_quantize_rows(x)
+        qc.view(torch.uint8)[:, :L] = qb
+        sc[:, :L] = sb
+
+
+def kv_store_mx(k, v, kq, ks, vq, vs):
+    """The prefill store: k / v [B, L, nkv, D] (views of the post-RoPE QKV, model dtype) quantised
+    row by row into rows 0 .. L - 1 of an MXFP8 cache. Not a hot path: GPU operands go through the
+    ``mx_quantize`` kernel on a contiguous [B L nkv, D] copy and two strided copies per tensor; its
+    bytes are the twin's."""
+    B, cap, nkv, D = _kv_mx_shapes(kq, ks, vq, vs, "kv_store_mx")
+    if k.dim() != 4 or k.shape != v.shape or (k.shape[0], k.shape[2], k.shape[3]) != (B, nkv, D) or k.shape[1] > cap:
+        raise ValueError(f"kv_store_mx: k / v {tuple(k.shape)} / {tuple(v.shape)} do not fit the cache {tuple(kq.shape)}")
+    if not _ext.use_kernels(k, v, kq):
+        return kv_store_mx_ref(k, v, kq, ks, vq, vs)
+    if k.dtype not in (torch.bfloat16, torch.float16) or v.dtype != k.dtype:
+        raise RuntimeError(f"kv_store_mx on the GPU needs bf16 / fp16 k and v of one dtype, got {k.dtype} / {v.dtype}")
+    L = k.shape[1]
+    for x, qc, sc in ((k, kq, ks), (v, vq, vs)):
+        qb, sb = mx_quantize(x.reshape(B * L * nkv, D), "e4m3")
+        qc.view(torch.uint8)[:, :L].copy_(qb.view(torch.uint8).view(B, L, nkv, D))
+        sc[:, :L].copy_(sb.view(B, L, nkv, D // MX_BLOCK))
 
 
 # --------------------------------------------------------------------------------------------
