@@ -27,6 +27,15 @@ cache on LLaMA-7B with a long prompt (``--kv-e2e B:S[,B:S...]``, default 8:3968,
                                       [--kv-format mxfp8] [--kv-e2e 8:4096]
                                       [--only llama-7b:8:4096] [--out decode.jsonl] [--quick]
 
+``--speculative``: the multi-token decode step and speculative ``generate`` (same protocol: device
+events, alternating order, minimum of four): ``decode_attention_multi`` (decode_attn_multi.hip) at
+T = 1, 2, 4, 8 against T calls of ``decode_attention`` and against SDPA with the tail mask;
+``forward_extend(T)`` against ``forward_decode`` on LLaMA-7B at B 1 / 2 under each weight format; one
+whole speculative round (OPT-125m-sized draft with the target's vocabulary, graph replay) against
+the plain decode step, with the break-even number of accepted drafts per round that follows from the
+two times; and a self-draft ``generate`` on OPT-125m for the accounting. Random-init pairs accept
+almost nothing, so no tokens/s gain of a real pair is measured here.
+
 One JSON line per measurement. Needs a GPU: there is no CPU fallback for a timing.
 """
 import argparse
@@ -335,11 +344,162 @@ def bench_e2e(emit, models, quick=False):
         torch.cuda.empty_cache()
 
 
+def _alternate(arms, reps):
+    """{name: min of four timings}, the arms alternating in order."""
+    for fn in arms.values():
+        _time(fn, 3)
+    t = {n: [] for n in arms}
+    names = list(arms)
+    for r in range(4):
+        for n in (names if r % 2 == 0 else names[::-1]):
+            t[n].append(_time(arms[n], reps))
+    return {n: min(v) for n, v in t.items()}
+
+
+def bench_spec_kernel(emit, quick=False):
+    from smdt_amd.ops import functional as SF
+    dev = torch.device("cuda", 0)
+    for name, (nh, nkv, D) in GEOMETRIES.items():
+        for B, S in ((1, 4096), (8, 4096)) if not quick else ((1, 1024),):
+            k = torch.empty(B, S, nkv, D, device=dev, dtype=torch.bfloat16).normal_()
+            v = torch.empty(B, S, nkv, D, device=dev, dtype=torch.bfloat16).normal_()
+            lens = torch.full((B,), S, dtype=torch.int32, device=dev)
+            scale, rep = 1.0 / math.sqrt(D), nh // nkv
+            for T in (1, 2, 4, 8):
+                q = torch.empty(B, T, nh, D, device=dev, dtype=torch.bfloat16).normal_()
+                qs = [q[:, t].contiguous() for t in range(T)]
+                lt = [lens - (T - 1 - t) for t in range(T)]
+                mask = torch.arange(S, device=dev)[None, :] <= (S - T + torch.arange(T, device=dev))[:, None]
+
+                def multi():
+                    return SF.decode_attention_multi(q, k, v, lens, scale)
+
+                def calls():
+                    return [SF.decode_attention(qs[t], k, v, lt[t], scale) for t in range(T)]
+
+                def sdpa():
+                    kk, vv = k.transpose(1, 2), v.transpose(1, 2)
+                    if rep > 1:
+                        kk, vv = kk.repeat_interleave(rep, dim=1), vv.repeat_interleave(rep, dim=1)
+                    return F.scaled_dot_product_attention(q.transpose(1, 2), kk, vv, attn_mask=mask, scale=scale)
+
+                diff = (multi().float() - sdpa().transpose(1, 2).float()).abs().max().item()
+                nbytes = 2 * B * S * nkv * D * 2
+                reps = max(5, min(200, int(0.1 / max(nbytes / 4e12, 2e-5))))
+                t = _alternate({"multi": multi, "calls": calls, "sdpa": sdpa}, reps)
+                emit({"bench": "decode_attention_multi", "geometry": name, "B": B, "S": S, "T": T, "kv_bytes": nbytes,
+                      "multi_us": t["multi"] * 1e6, "t_calls_us": t["calls"] * 1e6, "sdpa_us": t["sdpa"] * 1e6,
+                      "t_calls_over_multi": t["calls"] / t["multi"], "sdpa_over_multi": t["sdpa"] / t["multi"],
+                      "multi_GBps": nbytes / t["multi"] / 1e9, "max_abs_diff_vs_sdpa": diff, "reps": reps})
+            del k, v
+            torch.cuda.empty_cache()
+
+
+def bench_spec_model(emit, quick=False):
+    """forward_extend(T) against forward_decode, and a whole round against the plain step."""
+    from smdt_amd.models import generation as G
+    from smdt_amd.models.hf import BUILTIN, HFCausalLM
+    from smdt_amd.parallel import tensor_parallel as tp
+    from smdt_amd.train.graphs import CapturedStep
+    dev = torch.device("cuda", 0)
+    tname = "facebook/opt-125m" if quick else "llama-7b"
+    target = HFCausalLM.from_pretrained(tname, params_dtype=torch.bfloat16, device=dev).eval()
+    model, S = target.model, 128
+    with torch.no_grad():
+        for B in (1, 2):
+            ids = torch.randint(3, 30000, (B, S), device=dev)
+            plen = torch.full((B,), S, dtype=torch.int64, device=dev)
+            cache = G.KVCache(model.cfg, B, S + 16, torch.bfloat16, dev)
+            model.forward_prefill(ids, plen, cache)
+            for fmt in (None, "native", "mxfp8", "mxfp4"):
+                state = G._decode_weights(model, fmt)
+                arms = {}
+                for T in (1, 2, 5, 8):
+                    toks = torch.randint(3, 30000, (B, T), device=dev)
+
+                    def ext(T=T, toks=toks):
+                        cache.lens.fill_(S)
+                        cache.advance(T)
+                        return model.forward_extend(toks, cache)
+                    arms[f"extend{T}"] = ext
+
+                def dec(tok=torch.randint(3, 30000, (B,), device=dev)):
+                    cache.lens.fill_(S)
+                    cache.advance()
+                    return model.forward_decode(tok, cache)
+                arms["decode"] = dec
+                with tp.decode_weights(state):
+                    t = _alternate(arms, 10)
+                emit({"bench": "forward_extend", "model": tname, "B": B, "S": S, "weight_format": fmt,
+                      "decode_ms": t["decode"] * 1e3,
+                      **{f"extend{T}_ms": t[f"extend{T}"] * 1e3 for T in (1, 2, 5, 8)},
+                      **{f"extend{T}_over_decode": t[f"extend{T}"] / t["decode"] for T in (1, 2, 5, 8)}})
+        # one whole round (graph replay) against the plain step (graph replay), B = 1, k = 4
+        vocab = target.vocab_size
+        draft = HFCausalLM(dict(BUILTIN["facebook/opt-125m"], vocab_size=vocab), params_dtype=torch.bfloat16,
+                           device=dev).eval()
+        for fmt in (None, "mxfp4"):
+            state = G._decode_weights(model, fmt)
+            ids = torch.randint(3, 30000, (1, S), device=dev)
+            for k in (2, 4, 7):
+                st = G.SpeculativeState(model, draft.model, ids, None, 1500, k, None, 0, None, state)
+                rnd = CapturedStep(st.round, warmup=1)
+                cache = G.KVCache(model.cfg, 1, S + 1500, torch.bfloat16, dev)
+                model.forward_prefill(ids, torch.full((1,), S, dtype=torch.int64, device=dev), cache)
+                cache.lens.fill_(S)
+
+                def plain(tok):
+                    cache.advance()
+                    with tp.decode_weights(state):
+                        return model.forward_decode(tok, cache)[:, :vocab].argmax(-1)
+                stp = CapturedStep(plain, warmup=1)
+                x = {"r": st.x0, "p": st.x0.clone()}
+
+                def one_round():
+                    x["r"] = rnd(x["r"])
+
+                def one_step():
+                    x["p"] = stp(x["p"])
+                for _ in range(3):
+                    one_round(), one_step()
+                assert rnd.note == "captured" and stp.note == "captured", (rnd.note, stp.note)
+                t = _alternate({"round": one_round, "step": one_step}, 10)
+                emit({"bench": "speculative_round", "target": tname, "draft": "opt-125m-sized", "B": 1, "k": k,
+                      "weight_format": fmt, "round_ms": t["round"] * 1e3, "plain_step_ms": t["step"] * 1e3,
+                      "round_over_step": t["round"] / t["step"],
+                      # a round emits accepted + 1 tokens: it pays once accepted + 1 > round / step
+                      "break_even_accepted_per_round": t["round"] / t["step"] - 1.0})
+                del st, rnd, stp, cache
+                torch.cuda.empty_cache()
+        del target, model, draft
+        torch.cuda.empty_cache()
+        # the accounting on a self-draft: every draft is accepted, k + 1 tokens per round
+        m = HFCausalLM.from_pretrained("facebook/opt-125m", params_dtype=torch.bfloat16, device=dev).eval()
+        ids = torch.randint(3, 30000, (1, S), device=dev)
+        new = 33 if quick else 129
+
+        def run(n, **kw):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = m.generate(ids, max_new_tokens=n, eos_token_id=None, use_graph=True, **kw)
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0, out
+        stats = {}
+        spec = dict(draft_model=m, num_draft_tokens=4)
+        run(new), run(new, **spec)
+        tp_, op = min(run(new)[0] for _ in range(3)), run(new)[1]
+        ts_, os_ = min(run(new, **spec)[0] for _ in range(3)), run(new, stats=stats, **spec)[1]
+        emit({"bench": "generate_self_draft", "model": "facebook/opt-125m", "B": 1, "k": 4, "new_tokens": new,
+              "plain_call_s": tp_, "speculative_call_s": ts_, "tokens_equal": bool(torch.equal(op, os_)), **stats,
+              "acceptance": stats["accepted"] / max(stats["drafted"], 1)})
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--kernel", action="store_true")
     ap.add_argument("--e2e", action="store_true")
     ap.add_argument("--linear", action="store_true", help="decode_linear against F.linear per shape and M")
+    ap.add_argument("--speculative", action="store_true", help="the multi-token step and speculative generate")
     ap.add_argument("--weight-format", default=None,
                     help="with --e2e: comma-separated weight formats to run beside the parent path")
     ap.add_argument("--kv-format", default=None, help="with --kernel: decode_attention_mx against decode_attention; "
@@ -364,6 +524,12 @@ def main():
 
     both = not (args.kernel or args.e2e or args.linear)
     with torch.no_grad():
+        if args.speculative:
+            if args.kernel or both:
+                bench_spec_kernel(emit, args.quick)
+            if args.e2e or both:
+                bench_spec_model(emit, args.quick)
+            return
         if args.kv_format:
             if args.kernel or both:
                 bench_kernel_kv(emit, args.kv_format, args.quick, args.only)

@@ -42,6 +42,9 @@ def main(argv=None):
                     help="how the decode steps read the layers' weights (default: the model's own linears)")
     ap.add_argument("--kv_cache_format", choices=["mxfp8"], default=None,
                     help="how the K/V cache is stored (default: the model dtype)")
+    ap.add_argument("--draft_model_dir", default=None,
+                    help="a smaller model with the same vocabulary: greedy speculative decoding (temperature 0)")
+    ap.add_argument("--num_draft_tokens", type=int, default=4, help="tokens the draft proposes per round (1 .. 7)")
     args = ap.parse_args(argv)
 
     gpu = torch.cuda.is_available()
@@ -52,21 +55,28 @@ def main(argv=None):
     key = "prompt_input" if args.input else "prompt_no_input"
     prompt = sft.PROMPT_DICT[key].format_map({"instruction": args.instruction, "input": args.input})
     ids = tokenizer(prompt, return_tensors="pt").input_ids.to(device)
-    room = model.cfg.max_position_embeddings - ids.shape[1]
+    spec, reach = {}, model.cfg.max_position_embeddings
+    if args.draft_model_dir:
+        draft = HFCausalLM.from_pretrained(args.draft_model_dir, params_dtype=torch.bfloat16 if gpu else torch.float32,
+                                           device=device).eval()
+        spec = dict(draft_model=draft, num_draft_tokens=args.num_draft_tokens, stats={})
+        # rejected drafts touch num_draft_tokens positions beyond the last new token, in both models
+        reach = min(reach, draft.cfg.max_position_embeddings) - args.num_draft_tokens
+    room = reach - ids.shape[1]
     if room < 1:
         raise SystemExit(f"the prompt ({ids.shape[1]} tokens) leaves no room within max_position_embeddings "
-                         f"{model.cfg.max_position_embeddings}")
+                         f"{reach}")
     new = min(args.max_new_tokens, room)
     eos = tokenizer.eos_token_id
     sample = args.temperature > 0
     gen = torch.Generator(device=device).manual_seed(args.seed) if sample else None
     out = model.generate(ids, max_new_tokens=new, do_sample=sample, temperature=args.temperature if sample else 1.0,
                          top_p=args.top_p, eos_token_id=eos, generator=gen, use_graph=args.graph,
-                         weight_format=args.weight_format, kv_cache_format=args.kv_cache_format)
+                         weight_format=args.weight_format, kv_cache_format=args.kv_cache_format, **spec)
     tokens = out[0, ids.shape[1]:].tolist()
     if eos is not None and eos in tokens:
         tokens = tokens[: tokens.index(eos) + 1]
-    print(json.dumps({"prompt_tokens": int(ids.shape[1]), "new_token_ids": tokens}))
+    print(json.dumps({"prompt_tokens": int(ids.shape[1]), "new_token_ids": tokens, **spec.get("stats", {})}))
     if hasattr(tokenizer, "decode"):
         print(tokenizer.decode(tokens, skip_special_tokens=True))
     else:

@@ -1095,6 +1095,71 @@ Tensor decode_rope_append(Tensor qkv, Tensor k_cache, Tensor v_cache, Tensor pos
   return q;
 }
 
+// ------------------------------------------------------------------ multi-token decode (decode_attn_multi.hip)
+// q [B, T, nh, D] against the 16-bit caches; lens counts the keys after the T appends and query t
+// sees keys 0 .. lens[b] - T + t. Returns out [B, T, nh, D].
+int64_t decode_attn_multi_max_t() { return smdt_decode_attn_multi_max_t(); }
+
+bool decode_attn_multi_supported(int64_t dtype, int64_t D, int64_t nh, int64_t nkv, int64_t T) {
+  return nh < (1 << 20) && nkv < (1 << 20) && D < (1 << 20) && T < (1 << 20) &&
+         smdt_decode_attn_multi_supported((int)dtype, (int)D, (int)nh, (int)nkv, (int)T) != 0;
+}
+
+Tensor decode_attn_multi(Tensor q, Tensor k_cache, Tensor v_cache, Tensor lens, double scale, int64_t max_len) {
+  need_contig(q, "q");
+  TORCH_CHECK(q.dim() == 4, "decode_attn_multi: q must be [B, T, nh, D]");
+  dec_check_cache(k_cache, v_cache, q, "decode_attn_multi");
+  const int64_t B = q.size(0), T = q.size(1), nh = q.size(2), D = q.size(3), cap = k_cache.size(1),
+                nkv = k_cache.size(2);
+  TORCH_CHECK(k_cache.size(3) == D, "decode_attn_multi: head dim of q and the caches differ");
+  TORCH_CHECK(decode_attn_multi_supported(dcode(q), D, nh, nkv, T) && T * nh <= 65535,
+              "decode_attn_multi: unsupported (needs D in {64, 128}, nh / nkv in {1, 2, 4, 8} and 1 <= T <= ",
+              smdt_decode_attn_multi_max_t(), "): D ", D, ", nh ", nh, ", nkv ", nkv, ", T ", T);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(k_cache.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(v_cache.data_ptr()) % 16 == 0,
+              "decode_attn_multi: q and the caches must be 16-byte aligned");
+  if (max_len <= 0) max_len = cap;
+  TORCH_CHECK(max_len <= cap, "decode_attn_multi: max_len ", max_len, " exceeds the cache capacity ", cap);
+  const int* lp = dec_index(lens, q, "decode_attn_multi");
+  const int64_t C = smdt_decode_attn_chunk();
+  const int64_t nchunks = (max_len + C - 1) / C;
+  auto f32 = q.options().dtype(at::kFloat);
+  auto ws_ml = torch::empty({B, T * nh, nchunks, 2}, f32);
+  auto ws_acc = torch::empty({B, T * nh, nchunks, D}, f32);
+  auto out = torch::empty_like(q);
+  check(smdt_decode_attn_multi(dcode(q), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), lp,
+                               ws_ml.data_ptr<float>(), ws_acc.data_ptr<float>(), out.data_ptr(), (int)B, (int)T,
+                               (int)nh, (int)nkv, (int)D, (int)cap, (int)max_len, (float)scale, cur_stream()),
+        "decode_attn_multi");
+  return out;
+}
+
+// qkv [B, T, (nh + 2 nkv) D]: any batch / token strides (multiples of 8 elements) over contiguous
+// rows, so the model's sequence-first [T, B, W] is passed as a transposed view without a copy.
+// Token t of sequence b is rotated at pos[b] + t and appended to that cache row; -> q [B, T, nh, D].
+Tensor decode_rope_append_multi(Tensor qkv, Tensor k_cache, Tensor v_cache, Tensor pos, int64_t nh, OptT cos_t,
+                                OptT sin_t, int64_t rot) {
+  TORCH_CHECK(qkv.is_cuda() && qkv.dim() == 3, "decode_rope_append_multi: qkv must be a GPU [B, T, (nh + 2 nkv) D]");
+  dec_check_cache(k_cache, v_cache, qkv, "decode_rope_append_multi");
+  const int64_t B = qkv.size(0), T = qkv.size(1), cap = k_cache.size(1), nkv = k_cache.size(2), D = k_cache.size(3);
+  TORCH_CHECK(T >= 1 && T <= smdt_decode_attn_multi_max_t(), "decode_rope_append_multi: T ", T, " is outside 1 .. ",
+              smdt_decode_attn_multi_max_t());
+  TORCH_CHECK(nh > 0 && nh < (1 << 20) && D % 8 == 0 && D < (1 << 20) && qkv.size(2) == (nh + 2 * nkv) * D,
+              "decode_rope_append_multi: qkv width ", qkv.size(2), " is not (nh + 2 nkv) D with D % 8 == 0");
+  TORCH_CHECK(qkv.stride(2) == 1 && qkv.stride(0) % 8 == 0 && qkv.stride(1) % 8 == 0 && qkv.stride(0) >= 0 &&
+                  qkv.stride(1) >= 0 && reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0,
+              "decode_rope_append_multi: qkv rows must be contiguous and 16-byte aligned (strides ", qkv.strides(), ")");
+  const int* pp = dec_index(pos, qkv, "decode_rope_append_multi");
+  const RopeTables rt = dec_rope_tables(cos_t, sin_t, rot, D, qkv, "decode_rope_append_multi");
+  auto q = torch::empty({B, T, nh, D}, qkv.options());
+  check(smdt_decode_rope_append_multi(dcode(qkv), qkv.data_ptr(), qkv.stride(0), qkv.stride(1), q.data_ptr(),
+                                      k_cache.data_ptr(), v_cache.data_ptr(), pp, (int)B, (int)T, (int)nh, (int)nkv,
+                                      (int)D, (int)cap, (int)rot, rt.cos, rt.sin, (int)rt.max_pos, cur_stream()),
+        "decode_rope_append_multi");
+  return q;
+}
+
 // ------------------------------------------------------------------ MXFP8 K/V cache (decode_attn_mx.hip)
 // kq / vq [B, cap, nkv, D] E4M3, ksc / vsc [B, cap, nkv, D / 32] uint8 E8M0; q / qkv stay 16-bit.
 static bool aligned16(const Tensor& t);
@@ -1631,6 +1696,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         arg("max_len") = 0);
   m.def("decode_rope_append", &decode_rope_append, arg("qkv"), arg("k_cache"), arg("v_cache"), arg("pos"), arg("nh"),
         arg("cos") = pybind11::none(), arg("sin") = pybind11::none(), arg("rot") = 0);
+  m.def("decode_attn_multi_max_t", &decode_attn_multi_max_t);
+  m.def("decode_attn_multi_supported", &decode_attn_multi_supported, arg("dtype"), arg("D"), arg("nh"), arg("nkv"),
+        arg("T"));
+  m.def("decode_attn_multi", &decode_attn_multi, arg("q"), arg("k_cache"), arg("v_cache"), arg("lens"), arg("scale"),
+        arg("max_len") = 0);
+  m.def("decode_rope_append_multi", &decode_rope_append_multi, arg("qkv"), arg("k_cache"), arg("v_cache"), arg("pos"),
+        arg("nh"), arg("cos") = pybind11::none(), arg("sin") = pybind11::none(), arg("rot") = 0);
   m.def("decode_attn_mx", &decode_attn_mx, arg("q"), arg("kq"), arg("ks"), arg("vq"), arg("vs"), arg("lens"),
         arg("scale"), arg("max_len") = 0);
   m.def("decode_rope_append_mx", &decode_rope_append_mx, arg("qkv"), arg("kq"), arg("ks"), arg("vq"), arg("vs"),

@@ -171,6 +171,28 @@ hipError_t smdt_decode_rope_append(int dtype, const void* qkv, void* q_out, void
 hipError_t smdt_decode_attn_combine(int dtype, const float* ws_ml, const float* ws_acc, const int* lens, void* out,
                                     int B, int nh, int D, int cap, int nchunks, hipStream_t st);
 
+// decode_attn_multi.hip: a decode step with T new tokens per sequence (speculative verification).
+// smdt_decode_attn_multi: q [B, T, nh, D] against the 16-bit caches with lens[b] counting the keys
+// AFTER the T appends; query t sees keys 0 .. lens[b] - T + t. The score and P V products run on
+// v_mfma_f32_16x16x32 over the R = T nh / nkv query rows of a kv head. It writes partials only, in
+// smdt_decode_attn's workspace layout with nh' = T nh heads per sequence and head index t nh + h
+// (ws_ml fp32 [B, T nh, nchunks, 2], ws_acc fp32 [B, T nh, nchunks, D]) and finishes them with
+// smdt_decode_attn_combine(nh' = T nh), which leaves out [B, T, nh, D]. Supported: bf16 /
+// fp16, D in {64, 128}, nh / nkv in {1, 2, 4, 8}, 1 <= T <= smdt_decode_attn_multi_max_t().
+int smdt_decode_attn_multi_max_t();
+int smdt_decode_attn_multi_supported(int dtype, int D, int nh, int nkv, int T);
+hipError_t smdt_decode_attn_multi(int dtype, const void* q, const void* k_cache, const void* v_cache,
+                                  const int* lens, float* ws_ml, float* ws_acc, void* out, int B, int T, int nh,
+                                  int nkv, int D, int cap, int max_len, float scale, hipStream_t st);
+// qkv: token t of sequence b at qkv + b * stride_b + t * stride_t (elements; rows of (nh + 2 nkv) D
+// contiguous elements, so both [B, T, W] and the model's [T, B, W] are taken without a copy). Token
+// t is rotated at pos[b] + t and appended to cache row pos[b] + t; q -> q_out [B, T, nh, D]. The
+// arithmetic of smdt_decode_rope_append, so the bytes equal T calls of it.
+hipError_t smdt_decode_rope_append_multi(int dtype, const void* qkv, int64_t stride_b, int64_t stride_t,
+                                         void* q_out, void* k_cache, void* v_cache, const int* pos, int B, int T,
+                                         int nh, int nkv, int D, int cap, int rot, const float* cos_t,
+                                         const float* sin_t, int max_pos, hipStream_t st);
+
 // decode_attn_mx.hip: the same two operations against an MXFP8 cache: kq / vq [B, cap, nkv, D] E4M3
 // bytes, ksc / vsc [B, cap, nkv, D / 32] E8M0 bytes (mx_quant.hip's row form of every 16-bit row),
 // all contiguous and 16-byte aligned. q / qkv / out stay bf16 / fp16. Attention: the limits,

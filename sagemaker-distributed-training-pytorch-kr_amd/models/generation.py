@@ -19,6 +19,13 @@ kernel and no Python code of a step reads a length on the host, so with the stat
 of the 16-bit row the default cache would have held, written by the prefill store and by the
 quantising append, and read by csrc/kernels/decode_attn_mx.hip. The prefill's own attention still
 runs on the 16-bit K / V through flash attention.
+
+Speculative decoding (``generate(draft_model=...)``, greedy): a round lets the draft model propose
+``k = num_draft_tokens`` tokens in k + 1 single-token steps and the target check them all in ONE
+multi-token step (``GPTModel.forward_extend``, csrc/kernels/decode_attn_multi.hip: its linears see
+B (k + 1) rows of the same weight stream). ``speculative_accept`` keeps the longest prefix the
+target agrees with plus the target's own next token, so the output is the plain greedy output.
+A whole round stays on the device and can be captured in one graph.
 """
 from __future__ import annotations
 
@@ -94,10 +101,11 @@ class KVCache:
         self.k[attn.layer_number][:, :L].copy_(k)
         self.v[attn.layer_number][:, :L].copy_(v)
 
-    def advance(self):
-        """Start a decode step: the new token goes to row ``pos = lens`` and is one more key."""
+    def advance(self, n: int = 1):
+        """Start a decode step of ``n`` new tokens per sequence: they go to rows ``pos = lens`` ..
+        ``pos + n - 1`` and are ``n`` more keys."""
         self.pos.copy_(self.lens)
-        self.lens.add_(1)
+        self.lens.add_(n)
 
 
 def _refuse(model, input_ids, attention_mask, max_new_tokens, cache, kv_cache_format=None):
@@ -200,7 +208,8 @@ def generate(model, input_ids, attention_mask=None, max_new_tokens: int = 32, do
              temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, eos_token_id: Optional[int] = None,
              pad_token_id: int = 0, generator: Optional[torch.Generator] = None, use_graph: bool = False,
              cache: Optional[KVCache] = None, weight_format: Optional[str] = None,
-             kv_cache_format: Optional[str] = None):
+             kv_cache_format: Optional[str] = None, draft_model=None, num_draft_tokens: int = 4,
+             stats: Optional[dict] = None):
     """Greedy or sampled continuation of the right-padded prompts ``input_ids`` [B, Lmax]
     (``attention_mask`` marks the real tokens; None: every row is Lmax long) with a KV cache.
 
@@ -222,7 +231,31 @@ def generate(model, input_ids, attention_mask=None, max_new_tokens: int = 32, do
     ``kv_cache_format``: None (a cache in the model dtype) or "mxfp8": K and V are stored as MXFP8,
     the MX quantisation of the 16-bit rows, at 51.6 % of the bytes (head dimension 64 or 128,
     heads / kv heads in 1, 2, 4, 8; bf16 and fp16 models). A passed ``cache`` keeps its own format;
-    naming a different one here raises. Independent of ``weight_format`` and ``use_graph``."""
+    naming a different one here raises. Independent of ``weight_format`` and ``use_graph``.
+
+    ``draft_model``: a second model with the same vocabulary (``model`` itself is allowed: the
+    self-draft upper bound) turns on greedy speculative decoding with ``num_draft_tokens`` = k
+    drafted tokens per round, 1 <= k <= ``SF.DECODE_MULTI_MAX_T`` - 1. The tokens are those of the
+    plain greedy call. Positions up to Lmax + max_new_tokens + k - 1 are touched (rejected drafts),
+    so both models' ``max_position_embeddings`` and a passed ``cache`` must hold Lmax +
+    max_new_tokens + k. ``weight_format`` applies to the target only; sampling and
+    ``kv_cache_format`` are refused. ``use_graph=True`` captures one whole round. ``stats``, if a
+    dict, receives ``rounds``, ``drafted`` and ``accepted`` (drafted tokens the target agreed with),
+    both counted over the rows that were still generating."""
+    if draft_model is not None:
+        _refuse_speculative(model, draft_model, input_ids, attention_mask, max_new_tokens, cache, kv_cache_format,
+                            do_sample, num_draft_tokens)
+        state = _decode_weights(model, weight_format)
+        modes = (model.training, draft_model.training)
+        model.eval()
+        draft_model.eval()
+        try:
+            return _generate_speculative(model, draft_model, input_ids, attention_mask, int(max_new_tokens),
+                                         int(num_draft_tokens), eos_token_id, int(pad_token_id), use_graph, cache,
+                                         state, stats)
+        finally:
+            draft_model.train(modes[1])
+            model.train(modes[0])
     _refuse(model, input_ids, attention_mask, max_new_tokens, cache, kv_cache_format)
     state = _decode_weights(model, weight_format)
     if do_sample and temperature <= 0:
@@ -284,3 +317,168 @@ def _generate(model, input_ids, attention_mask, max_new, do_sample, temperature,
     if captured is not None and captured.note.startswith("capture failed"):
         raise RuntimeError(f"generate(use_graph=True): the decode step could not be captured ({captured.note})")
     return seq
+
+
+# ------------------------------------------------------------------------------------------------
+# Greedy speculative decoding
+
+
+def _refuse_speculative(model, draft, input_ids, attention_mask, max_new_tokens, cache, kv_cache_format, do_sample,
+                        k):
+    """Every refusal of ``generate(draft_model=...)``, naming the cause, before anything is allocated."""
+    if do_sample:
+        raise NotImplementedError("generate(draft_model=...): verification is greedy; do_sample=True is not supported "
+                                  "with a draft model")
+    if kv_cache_format is not None or (cache is not None and cache.format is not None):
+        raise NotImplementedError("generate(draft_model=...): kv_cache_format is not supported with a draft model "
+                                  "(the multi-token verify step reads a 16-bit cache)")
+    max_t = SF.DECODE_MULTI_MAX_T
+    if isinstance(k, bool) or int(k) != k or not 1 <= k <= max_t - 1:
+        raise ValueError(f"generate(draft_model=...): num_draft_tokens must be in 1 .. {max_t - 1} (the verify step "
+                         f"takes up to {max_t} tokens), got {k!r}")
+    _refuse(model, input_ids, attention_mask, max_new_tokens, None, None)
+    try:
+        _refuse(draft, input_ids, attention_mask, max_new_tokens, None, None)
+    except (ValueError, NotImplementedError, RuntimeError) as e:
+        raise type(e)(f"generate(draft_model=...): the draft model is refused: {e}") from e
+    vt = int(model.loss_vocab_size or model.cfg.padded_vocab_size)
+    vd = int(draft.loss_vocab_size or draft.cfg.padded_vocab_size)
+    if vt != vd:
+        raise ValueError(f"generate(draft_model=...): the draft model's vocabulary ({vd}) differs from the target's "
+                         f"({vt})")
+    B, L = input_ids.shape
+    total = L + max_new_tokens + k
+    for who, m in (("the target", model), ("the draft model", draft)):
+        if total > m.cfg.max_position_embeddings:
+            raise ValueError(f"generate(draft_model=...): prompt length {L} + max_new_tokens {max_new_tokens} + "
+                             f"num_draft_tokens {k} = {total} exceeds max_position_embeddings "
+                             f"{m.cfg.max_position_embeddings} of {who} (rejected drafts touch those positions)")
+    if cache is not None and (cache.batch != B or total > cache.capacity):
+        raise ValueError(f"generate(draft_model=...): prompt length {L} + max_new_tokens {max_new_tokens} + "
+                         f"num_draft_tokens {k} = {total} for batch {B} exceeds the KV cache (batch {cache.batch}, "
+                         f"capacity {cache.capacity})")
+
+
+def speculative_accept(draft, target_argmax, remaining, finished, eos, pad):
+    """The accept step of one round, per row, on the device (no host read).
+
+    ``draft`` [B, k]: the proposed d1 .. dk; ``target_argmax`` [B, k + 1]: the target's greedy
+    tokens p0 .. pk after x0, d1 .. dk; ``remaining`` [B]: tokens the row may still emit;
+    ``finished`` [B] bool. n = the longest prefix with d_i == p_(i-1) (a cumulative product). The
+    row emits d1 .. dn, p_n, which are p0 .. pn, cut at ``remaining`` and after the first ``eos``
+    (None: no EOS); a finished row emits nothing.
+
+    Returns (tokens [B, k + 1]: the emitted run, then ``pad``; count [B]: its length; finished [B]:
+    the old flag or an emitted EOS; n [B]: the accepted drafts before any cut)."""
+    k = draft.shape[1]
+    match = (draft == target_argmax[:, :k]).long()
+    n = match.cumprod(dim=1).sum(dim=1)                                         # [B], 0 .. k
+    idx = torch.arange(k + 1, device=draft.device)[None, :]
+    count = torch.minimum(n + 1, remaining.long().clamp(min=0))
+    count = torch.where(finished, torch.zeros_like(count), count)
+    done = finished
+    if eos is not None:
+        hit = (target_argmax == eos) & (idx < count[:, None])
+        first = torch.where(hit, idx, torch.full_like(idx, k + 1)).amin(dim=1)  # k + 1: none
+        count = torch.minimum(count, first + 1)
+        done = finished | hit.any(dim=1)
+    tokens = torch.where(idx < count[:, None], target_argmax, torch.full_like(target_argmax, pad))
+    return tokens, count, done, n
+
+
+class SpeculativeState:
+    """What the rounds of one speculative ``generate`` call update in place (all on the device):
+    ``seq`` [B, L + max_new + 1] (the last column takes the writes of tokens that are not emitted),
+    ``plen`` / ``nout`` / ``remaining`` int64 [B], ``finished`` bool [B], ``counters`` int64 [3]
+    (rounds, drafted, accepted) and the two caches."""
+
+    def __init__(self, model, draft, input_ids, attention_mask, max_new, k, eos, pad, cache, dstate):
+        cfg, dev = model.cfg, input_ids.device
+        B, L = input_ids.shape
+        self.model, self.draft, self.k, self.eos, self.pad, self.dstate = model, draft, k, eos, pad, dstate
+        self.vocab = int(model.loss_vocab_size or cfg.padded_vocab_size)
+        self.plen = (torch.full((B,), L, dtype=torch.int64, device=dev) if attention_mask is None
+                     else attention_mask.to(dev).long().sum(dim=1))
+        cap = L + max_new + k
+        self.cache = cache if cache is not None else KVCache(cfg, B, cap, cfg.params_dtype, dev)
+        # a self-draft still keeps a cache of its own: the draft steps run ahead of the target
+        self.dcache = KVCache(draft.cfg, B, cap, draft.cfg.params_dtype, dev)
+        self.seq = torch.full((B, L + max_new + 1), pad, dtype=input_ids.dtype, device=dev)
+        keep = torch.arange(L, device=dev)[None, :] < self.plen[:, None]
+        self.seq[:, :L] = torch.where(keep, input_ids, self.seq[:, :L])
+        self.finished = torch.zeros(B, dtype=torch.bool, device=dev)
+        self.counters = torch.zeros(3, dtype=torch.int64, device=dev)
+        # prefill of both models; the target's logits give the first token x0
+        with tp.decode_weights(dstate):
+            logits = model.forward_prefill(input_ids, self.plen, self.cache)
+        self.cache.lens.copy_(self.plen)
+        draft.forward_prefill(input_ids, self.plen, self.dcache)
+        self.dcache.lens.copy_(self.plen)
+        x0 = logits[:, :self.vocab].argmax(dim=-1)
+        self.seq.scatter_(1, self.plen.unsqueeze(1), x0.unsqueeze(1).to(self.seq.dtype))
+        if eos is not None:
+            self.finished.logical_or_(x0 == eos)
+        self.nout = torch.ones(B, dtype=torch.int64, device=dev)
+        self.remaining = torch.full((B,), max_new - 1, dtype=torch.int64, device=dev)
+        self.x0 = x0
+
+    def round(self, x0):
+        """One round from the last emitted token ``x0`` [B] (in neither cache yet): k + 1 draft
+        steps, one verify step, the accept step and every state update. Returns the new x0. Nothing
+        here reads the device."""
+        k, V = self.k, self.vocab
+        cache, dcache = self.cache, self.dcache
+        base = cache.lens.clone()
+        tok, drafts = x0, []
+        for i in range(k + 1):          # the last step only fills the draft's cache
+            dcache.advance()
+            lg = self.draft.forward_decode(tok, dcache)
+            if i < k:
+                tok = lg[:, :V].argmax(dim=-1)
+                drafts.append(tok)
+        d = torch.stack(drafts, dim=1)                                           # [B, k]
+        cache.advance(k + 1)
+        with tp.decode_weights(self.dstate):
+            logits = self.model.forward_extend(torch.cat([x0.unsqueeze(1), d], dim=1), cache)
+        p = logits[..., :V].argmax(dim=-1)                                       # [B, k + 1]
+        active = ~self.finished & (self.remaining > 0)
+        toks, count, done, n = speculative_accept(d, p, self.remaining, self.finished, self.eos, self.pad)
+        idx = torch.arange(k + 1, device=x0.device)[None, :]
+        col = torch.where(idx < count[:, None], (self.plen + self.nout)[:, None] + idx,
+                          torch.full_like(idx, self.seq.shape[1] - 1))
+        self.seq.scatter_(1, col, toks.to(self.seq.dtype))
+        last = toks.gather(1, (count - 1).clamp(min=0).unsqueeze(1)).squeeze(1)
+        x0 = torch.where(count > 0, last, x0)
+        self.nout.add_(count)
+        self.remaining.sub_(count)
+        self.finished.copy_(done)
+        new_lens = (base.long() + count).to(torch.int32)
+        cache.lens.copy_(new_lens)
+        dcache.lens.copy_(new_lens)
+        self.counters.add_(torch.stack([torch.ones_like(n[0]), (active.long() * k).sum(), (active.long() * n).sum()]))
+        return x0
+
+    def all_done(self):
+        """The one flag the host may read per round."""
+        return bool((self.finished | (self.remaining <= 0)).all())
+
+
+def _generate_speculative(model, draft, input_ids, attention_mask, max_new, k, eos, pad, use_graph, cache, dstate,
+                          stats):
+    st = SpeculativeState(model, draft, input_ids, attention_mask, max_new, k, eos, pad, cache, dstate)
+    step, captured = st.round, None
+    if use_graph and input_ids.device.type == "cuda":
+        from ..train.graphs import CapturedStep
+        step = captured = CapturedStep(st.round, warmup=1)     # round 1 eager, round 2 captured
+    x0 = st.x0
+    # a round emits at least one token per unfinished row and at most k + 1
+    for r in range(max_new - 1):
+        if (eos is not None or r * (k + 1) >= max_new - 1) and st.all_done():
+            break
+        x0 = step(x0)
+    if captured is not None and captured.note.startswith("capture failed"):
+        raise RuntimeError(f"generate(use_graph=True): the speculative round could not be captured ({captured.note})")
+    if stats is not None:
+        rounds, drafted, accepted = (int(v) for v in st.counters.tolist())
+        stats.update(rounds=rounds, drafted=drafted, accepted=accepted)
+    return st.seq[:, :-1].contiguous()

@@ -184,6 +184,17 @@ class GPTModel(nn.Module):
         h = self.decoder.forward_decode(x, cache)
         return self.lm_logits(h).squeeze(0)
 
+    def forward_extend(self, tokens, cache):
+        """T new tokens per sequence, ``tokens`` [b, T], at positions ``cache.pos + t`` against the
+        cache (advanced by ``cache.advance(T)``): the logits after every one of them, [b, T, V].
+        Token t sees the cached keys, the new tokens before it and itself. Learned positions take
+        ``cache.pos + t`` through the ``position_ids`` path."""
+        T = tokens.shape[1]
+        pos = cache.pos.long().unsqueeze(1) + torch.arange(T, device=tokens.device).unsqueeze(0)       # [b, T]
+        x = self._embed(tokens, pos)                                                 # [T, b, h]
+        h = self.decoder.forward_extend(x, cache)
+        return self.lm_logits(h).transpose(0, 1)
+
     def forward(self, tokens, position_ids=None, attention_mask=None, labels=None, loss_mask=None,
                 doc_start=None):
         """Returns per-token losses [b, s] when ``labels`` are given, else the logits. ``loss_mask``

@@ -429,8 +429,12 @@ class HFCausalLM(nn.Module):
         ``eos_token_id=None`` to generate ``max_new_tokens`` whatever is emitted.
         ``weight_format="native" | "mxfp8" | "mxfp4"`` streams the layers' weights through the
         decode GEMM kernel (see ``generate``); the default leaves the linears as they are.
-        ``kv_cache_format="mxfp8"`` keeps the K/V cache as MXFP8; the default is the model dtype."""
+        ``kv_cache_format="mxfp8"`` keeps the K/V cache as MXFP8; the default is the model dtype.
+        ``draft_model`` (an ``HFCausalLM`` or a ``GPTModel``), ``num_draft_tokens`` and ``stats``:
+        greedy speculative decoding with the same output tokens (see ``generate``)."""
         from .generation import generate
+        if isinstance(kw.get("draft_model"), HFCausalLM):
+            kw["draft_model"] = kw["draft_model"].model
         eos = self.hf_config.get("eos_token_id")
         kw.setdefault("eos_token_id", eos)
         pad = self.hf_config.get("pad_token_id")

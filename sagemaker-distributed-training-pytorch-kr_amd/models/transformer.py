@@ -514,6 +514,24 @@ class ParallelAttention(nn.Module):
         ctx = SF.decode_attention(q, k, v, cache.lens, 1.0 / math.sqrt(self.hd), max_len=cache.max_len)
         return self.proj(ctx.view(1, b, self.nh * self.hd))
 
+    def forward_extend(self, x, cache, layer: int):
+        """T new tokens per sequence, x [T, b, h], against a 16-bit ``cache`` whose ``pos`` / ``lens``
+        were advanced by T (``KVCache.advance(T)``): QKV linear over the T b rows, RoPE at
+        ``cache.pos + t`` and the append of the T K / V rows, attention of query t over keys
+        0 .. lens - T + t (decode_attn_multi.hip), projection. The sequence-first projection output
+        goes to the append kernel as a transposed view, without a copy. Returns what ``forward``
+        returns, [T, b, h]."""
+        if cache.format is not None:
+            raise NotImplementedError(f"forward_extend: the multi-token decode step reads a 16-bit K/V cache; this "
+                                      f"cache's format is {cache.format!r}")
+        qkv = self.qkv(x)                                        # [T, b, (nh + 2 nkv) d]
+        T, b = qkv.shape[0], qkv.shape[1]
+        k, v = cache.k[layer], cache.v[layer]
+        q = SF.decode_rope_append_multi(qkv.transpose(0, 1), k, v, cache.pos, self.nh, self.nkv, self.hd,
+                                        rope=self.rope)         # [b, T, nh, d]
+        ctx = SF.decode_attention_multi(q, k, v, cache.lens, 1.0 / math.sqrt(self.hd), max_len=cache.max_len)
+        return self.proj(ctx.transpose(0, 1).reshape(T, b, self.nh * self.hd))
+
     def _groups_ok(self, qkv) -> bool:
         g = _PACK.get("groups")
         W = qkv.shape[-1]
@@ -844,6 +862,21 @@ class ParallelTransformerLayer(nn.Module):
         m, mb = self.mlp(ln2)
         return m, mb, residual
 
+    def forward_extend(self, x, xbias, residual, cache, layer: int):
+        """``forward_decode`` for T new tokens per sequence, x [T, b, h]
+        (``ParallelAttention.forward_extend``)."""
+        training = self.training
+        p = self.cfg.hidden_dropout
+        ln1, residual = self.input_norm.fused(x, xbias, residual, p, training)
+        if self.post_ln_residual:
+            residual = ln1
+        a, ab = self.attention.forward_extend(ln1, cache, layer)
+        ln2, residual = self.post_attention_norm.fused(a, ab, residual, p, training)
+        if self.post_ln_residual:
+            residual = ln2
+        m, mb = self.mlp(ln2)
+        return m, mb, residual
+
     def forward_phases(self, st):
         """``forward`` cut at its four sequence-parallel exchanges for the sub-batch interleave
         (``ParallelTransformer._forward_subbatch``): each phase ends right after it STARTS an
@@ -975,6 +1008,14 @@ class ParallelTransformer(nn.Module):
         xbias = residual = None
         for i, layer in enumerate(self.layers):
             x, xbias, residual = layer.forward_decode(x, xbias, residual, cache, i)
+        return self.final_norm.fused(x, xbias, residual, self.cfg.hidden_dropout, self.training)[0]
+
+    def forward_extend(self, x, cache):
+        """``forward_decode`` for T new tokens per sequence, x [T, b, h]: the normalised output
+        [T, b, h]."""
+        xbias = residual = None
+        for i, layer in enumerate(self.layers):
+            x, xbias, residual = layer.forward_extend(x, xbias, residual, cache, i)
         return self.final_norm.fused(x, xbias, residual, self.cfg.hidden_dropout, self.training)[0]
 
     def forward(self, x, xbias=None, residual=None, doc_start=None):

@@ -929,6 +929,142 @@ def decode_rope_append(qkv, k_cache, v_cache, pos, nh, nkv, hd, rope=None):
 
 
 # --------------------------------------------------------------------------------------------
+# Multi-token decode step (csrc/kernels/decode_attn_multi.hip): T new tokens per sequence in one
+# pass, the verify step of speculative decoding. q is [B, T, nh, D]; ``lens`` counts the keys with
+# all T new tokens appended and query t sees keys 0 .. lens[b] - T + t (the old keys, the new tokens
+# before it, itself). T = 1 is ``decode_attention``'s meaning.
+
+DECODE_MULTI_MAX_T = 8      # smdt_decode_attn_multi_max_t(): T * (nh / nkv) <= 64 query rows per kv head
+
+
+def decode_attention_multi_supported(q, k_cache, v_cache=None) -> bool:
+    """The operands decode_attn_multi.hip takes (smdt_decode_attn_multi_supported): q [B, T, nh, D]
+    with 1 <= T <= ``DECODE_MULTI_MAX_T`` and otherwise ``decode_attention_supported``'s set."""
+    if q.dim() != 4 or not 1 <= q.shape[1] <= DECODE_MULTI_MAX_T or q.shape[1] * q.shape[2] > 65535:
+        return False
+    return decode_attention_supported(q[:, 0], k_cache, v_cache)
+
+
+def _multi_limits(lens, T):
+    """[B, T]: the number of keys query t of sequence b sees, lens[b] - T + t + 1 (not below 0)."""
+    return (lens.long()[:, None] - T + 1 + torch.arange(T, device=lens.device)[None, :]).clamp_(min=0)
+
+
+def decode_attention_multi_ref(q, k_cache, v_cache, lens, scale, max_len=None, emulate: bool = False):
+    """Torch twin of ``decode_attention_multi``. Default: ``decode_attention_ref`` of every query t
+    over its own lens[b] - T + t + 1 keys (fp32 math, float64 for float64 operands, one rounding at
+    the output; the bits of ``decode_attention_ref`` at T = 1); a query that sees no key returns
+    zeros. Keys at or beyond a query's limit are selected out before any arithmetic.
+
+    ``emulate=True`` places the kernel's rounding points instead: per chunk of ``DECODE_CHUNK`` keys
+    the probabilities exp(s - chunk maximum) are rounded to q's dtype before the P V product
+    (their sum l stays unrounded fp32), the product accumulates in fp32, the chunks are combined in
+    fp32 as the combine kernel does, and the output is rounded once."""
+    B, T, nh, D = q.shape
+    lim = _multi_limits(lens, T)
+    if not emulate:
+        out = torch.empty_like(q)
+        for t in range(T):
+            o = decode_attention_ref(q[:, t].contiguous(), k_cache, v_cache, lim[:, t], scale)
+            out[:, t] = torch.where((lim[:, t] > 0)[:, None, None], o, torch.zeros((), dtype=q.dtype, device=q.device))
+        return out
+    cap, nkv = k_cache.shape[1], k_cache.shape[2]
+    if nh % nkv:
+        raise ValueError(f"decode_attention_multi: {nh} query heads are not a multiple of {nkv} kv heads")
+    C = DECODE_CHUNK
+    nc = (cap + C - 1) // C
+    f32 = torch.float32
+    valid = torch.arange(cap, device=q.device)[None, None, :] < lim[:, :, None]             # [B, T, cap]
+    used = valid.any(dim=1)                                                                  # [B, cap]
+    zero = torch.zeros((), dtype=f32, device=q.device)
+    kk = torch.where(used[:, :, None, None], k_cache.to(f32), zero)
+    vv = torch.where(used[:, :, None, None], v_cache.to(f32), zero)
+    qg = q.to(f32).reshape(B, T, nkv, nh // nkv, D)
+    s = torch.einsum("btkgd,bckd->btkgc", qg, kk) * scale
+    s = s.masked_fill(~valid[:, :, None, None, :], float("-inf"))
+    pad = nc * C - cap
+    if pad:
+        s = torch.nn.functional.pad(s, (0, pad), value=float("-inf"))
+        vv = torch.nn.functional.pad(vv, (0, 0, 0, 0, 0, pad))
+    s = s.view(B, T, nkv, nh // nkv, nc, C)
+    m = s.amax(dim=-1)                                                                       # [B, T, k, g, nc]
+    p = torch.where(s == float("-inf"), zero, torch.exp(s - m.unsqueeze(-1).clamp(min=-3.0e38)))
+    l = p.sum(dim=-1)
+    acc = torch.einsum("btkgnc,bnckd->btkgnd", p.to(q.dtype).to(f32), vv.view(B, nc, C, nkv, D))
+    has = l > 0
+    M = torch.where(has, m, torch.full_like(m, float("-inf"))).amax(dim=-1, keepdim=True)
+    w = torch.where(has, torch.exp(m - M.clamp(min=-3.0e38)), zero)
+    num = (w.unsqueeze(-1) * acc).sum(dim=-2)
+    den = (w * l).sum(dim=-1, keepdim=True)
+    o = torch.where(den > 0, num / den.clamp(min=1e-38), zero)
+    return o.reshape(B, T, nh, D).to(q.dtype)
+
+
+def decode_attention_multi(q, k_cache, v_cache, lens, scale, max_len=None):
+    """Attention of T new queries per sequence, q [B, T, nh, D], against the caches [B, cap, nkv, D]
+    that already hold the T new tokens' keys: ``lens`` (int32 [B] on q's device) counts the keys
+    with all T appended and query t sees keys 0 .. lens[b] - T + t. Returns [B, T, nh, D]; a query
+    that sees no key returns zeros. ``max_len`` (host int <= cap, default cap) only bounds the
+    kernel's grid. GPU operands run decode_attn_multi.hip (scores and P V on the 16x16x32 MFMA) or
+    raise (``decode_attention_multi_supported``); CPU operands run the torch twin."""
+    if q.dim() != 4:
+        raise ValueError(f"decode_attention_multi: q must be [B, T, nh, D], got {tuple(q.shape)}")
+    if not _ext.use_kernels(q, k_cache, v_cache):
+        if q.shape[1] < 1:
+            raise ValueError("decode_attention_multi: T must be at least 1")
+        return decode_attention_multi_ref(q, k_cache, v_cache, lens, scale, max_len)
+    if not decode_attention_multi_supported(q, k_cache, v_cache):
+        raise RuntimeError(f"decode_attention_multi on the GPU needs bf16 / fp16 q [B, T, nh, D] with 1 <= T <= "
+                           f"{DECODE_MULTI_MAX_T} and 16-bit caches [B, cap, nkv, D] of q's dtype (not an MXFP8 cache), "
+                           f"D in (64, 128) and nh / nkv in (1, 2, 4, 8); got q {tuple(q.shape)} {q.dtype}, k_cache "
+                           f"{tuple(k_cache.shape)} {k_cache.dtype}, v_cache {tuple(v_cache.shape)} {v_cache.dtype}")
+    cap = k_cache.shape[1]
+    max_len = cap if max_len is None else int(max_len)
+    if not 0 < max_len <= cap:
+        raise ValueError(f"decode_attention_multi: max_len {max_len} must be in 1 .. the capacity {cap}")
+    return _ext.ext().decode_attn_multi(q.contiguous(), k_cache, v_cache, lens, float(scale), max_len)
+
+
+def decode_rope_append_multi_ref(qkv, k_cache, v_cache, pos, nh, nkv, hd, rope=None):
+    """Torch twin of ``decode_rope_append_multi``: T calls of ``decode_rope_append_ref``, token t at
+    position pos[b] + t."""
+    T = qkv.shape[1]
+    return torch.stack([decode_rope_append_ref(qkv[:, t], k_cache, v_cache, pos + t, nh, nkv, hd, rope)
+                        for t in range(T)], dim=1)
+
+
+def decode_rope_append_multi(qkv, k_cache, v_cache, pos, nh, nkv, hd, rope=None):
+    """T new tokens per sequence: ``qkv`` [B, T, (nh + 2 nkv) hd]. Token t of sequence b is rotated
+    at position pos[b] + t (``pos`` int32 [B], device) and its k / v are written into cache row
+    pos[b] + t; q [B, T, nh, hd] is returned. The bytes are those of T calls of
+    ``decode_rope_append``. The kernel takes the batch and token strides as they are (rows of W
+    contiguous elements, strides multiples of 8 elements), so the model passes its sequence-first
+    [T, B, W] projection as ``qkv.transpose(0, 1)`` and no copy is made; anything else is copied
+    here. GPU operands run the kernel or raise; CPU operands run the torch twin."""
+    if qkv.dim() != 3 or qkv.shape[2] != (nh + 2 * nkv) * hd:
+        raise ValueError(f"decode_rope_append_multi: qkv {tuple(qkv.shape)} is not [B, T, (nh + 2 nkv) hd] = "
+                         f"[B, T, {(nh + 2 * nkv) * hd}]")
+    if not 1 <= qkv.shape[1] <= DECODE_MULTI_MAX_T:
+        raise ValueError(f"decode_rope_append_multi: T = {qkv.shape[1]} is outside 1 .. {DECODE_MULTI_MAX_T}")
+    if tuple(k_cache.shape[2:]) != (nkv, hd) or k_cache.shape != v_cache.shape or k_cache.shape[0] != qkv.shape[0]:
+        raise ValueError(f"decode_rope_append_multi: caches {tuple(k_cache.shape)} / {tuple(v_cache.shape)} are not "
+                         f"[B, cap, {nkv}, {hd}]")
+    if not _ext.use_kernels(qkv, k_cache, v_cache):
+        return decode_rope_append_multi_ref(qkv, k_cache, v_cache, pos, nh, nkv, hd, rope)
+    if qkv.dtype not in (torch.bfloat16, torch.float16) or k_cache.dtype != qkv.dtype or v_cache.dtype != qkv.dtype \
+            or hd % 8 or (rope is not None and rope[2] % 16):
+        raise RuntimeError(f"decode_rope_append_multi on the GPU needs bf16 / fp16 qkv and caches of one dtype, hd % 8 "
+                           f"== 0 and a rotary dim % 16 == 0; got {qkv.dtype} / {k_cache.dtype} / {v_cache.dtype}, "
+                           f"hd {hd}")
+    if qkv.stride(2) != 1 or qkv.stride(0) % 8 or qkv.stride(1) % 8 or qkv.data_ptr() % 16:
+        qkv = qkv.contiguous()
+    if rope is None:
+        return _ext.ext().decode_rope_append_multi(qkv, k_cache, v_cache, pos, nh)
+    cos, sin, rot = rope
+    return _ext.ext().decode_rope_append_multi(qkv, k_cache, v_cache, pos, nh, cos, sin, int(rot))
+
+
+# --------------------------------------------------------------------------------------------
 # MXFP8 K/V cache (csrc/kernels/decode_attn_mx.hip, generate(kv_cache_format="mxfp8")). K and V of
 # a layer are each stored as q [B, cap, nkv, D] float8_e4m3fn and s [B, cap, nkv, D / 32] uint8
 # (E8M0, bias 127): a (sequence, position, kv head) row of D elements is D / 32 MX blocks and its
