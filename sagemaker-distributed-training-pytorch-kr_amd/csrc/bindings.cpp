@@ -996,6 +996,8 @@ std::vector<Tensor> window_attn_bwd(Tensor qkv, Tensor table, Tensor lse, Tensor
 // q [B, nh, D], caches [B, cap, nkv, D], lens int32 [B] on the device (valid keys per sequence, the
 // new token included); max_len <= cap bounds the grid (0: cap). Everything the kernel does not
 // take is refused here, before any launch.
+static bool aligned16(const Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0; }
+
 static void dec_check_cache(const Tensor& k_cache, const Tensor& v_cache, const Tensor& like, const char* what) {
   need_contig(k_cache, "k_cache");
   need_contig(v_cache, "v_cache");
@@ -1018,6 +1020,20 @@ static const int* dec_index(const Tensor& t, const Tensor& like, const char* wha
 
 int64_t decode_attn_chunk() { return smdt_decode_attn_chunk(); }
 
+// What an attention op allocates: the checked max_len (0: cap) and the split-KV workspaces of its
+// `heads` partial rows per sequence (nh, or T nh for the multi-token step).
+struct DecWork {
+  int64_t max_len;
+  Tensor ws_ml, ws_acc;
+};
+static DecWork dec_work(const Tensor& q, int64_t cap, int64_t max_len, int64_t heads, int64_t D, const char* what) {
+  if (max_len <= 0) max_len = cap;
+  TORCH_CHECK(max_len <= cap, what, ": max_len ", max_len, " exceeds the cache capacity ", cap);
+  const int64_t C = smdt_decode_attn_chunk(), nchunks = (max_len + C - 1) / C;
+  auto f32 = q.options().dtype(at::kFloat);
+  return {max_len, torch::empty({q.size(0), heads, nchunks, 2}, f32), torch::empty({q.size(0), heads, nchunks, D}, f32)};
+}
+
 bool decode_attn_supported(int64_t dtype, int64_t D, int64_t nh, int64_t nkv) {
   return nh < (1 << 20) && nkv < (1 << 20) && D < (1 << 20) &&
          smdt_decode_attn_supported((int)dtype, (int)D, (int)nh, (int)nkv) != 0;
@@ -1032,18 +1048,12 @@ Tensor decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor lens, double
   TORCH_CHECK(decode_attn_supported(dcode(q), D, nh, nkv),
               "decode_attn: unsupported (needs D in {64, 128} and nh / nkv in {1, 2, 4, 8}): D ", D, ", nh ", nh,
               ", nkv ", nkv);
-  if (max_len <= 0) max_len = cap;
-  TORCH_CHECK(max_len <= cap, "decode_attn: max_len ", max_len, " exceeds the cache capacity ", cap);
+  const DecWork w = dec_work(q, cap, max_len, nh, D, "decode_attn");
   const int* lp = dec_index(lens, q, "decode_attn");
-  const int64_t C = smdt_decode_attn_chunk();
-  const int64_t nchunks = (max_len + C - 1) / C;
-  auto f32 = q.options().dtype(at::kFloat);
-  auto ws_ml = torch::empty({B, nh, nchunks, 2}, f32);
-  auto ws_acc = torch::empty({B, nh, nchunks, D}, f32);
   auto out = torch::empty_like(q);
   check(smdt_decode_attn(dcode(q), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), lp,
-                         ws_ml.data_ptr<float>(), ws_acc.data_ptr<float>(), out.data_ptr(), (int)B, (int)nh,
-                         (int)nkv, (int)D, (int)cap, (int)max_len, (float)scale, cur_stream()),
+                         w.ws_ml.data_ptr<float>(), w.ws_acc.data_ptr<float>(), out.data_ptr(), (int)B, (int)nh,
+                         (int)nkv, (int)D, (int)cap, (int)w.max_len, (float)scale, cur_stream()),
         "decode_attn");
   return out;
 }
@@ -1075,23 +1085,50 @@ static RopeTables dec_rope_tables(const OptT& cos_t, const OptT& sin_t, int64_t 
   return rt;
 }
 
-// qkv [B, (nh + 2 nkv) D] -> q [B, nh, D]; k / v written into row pos[b] of the caches. cos / sin
-// (fp32 [max_pos, rot / 2]) and rot > 0 rotate q and k; without them the op is a copy.
+// The qkv row width of an append op: (nh + 2 nkv) D with D % 8 == 0.
+static void dec_check_qkv(const Tensor& qkv, int64_t nh, int64_t nkv, int64_t D, const char* what) {
+  const int64_t W = qkv.size(-1);
+  TORCH_CHECK(nh > 0 && nh < (1 << 20) && D % 8 == 0 && D < (1 << 20) && W == (nh + 2 * nkv) * D, what,
+              ": qkv width ", W, " is not (nh + 2 nkv) D with D % 8 == 0");
+}
+
+// The 16-bit append of both decode steps (one kernel, decode_attn_multi.hip). cos / sin (fp32
+// [max_pos, rot / 2]) and rot > 0 rotate q and k; without them the op is a copy.
+//   qkv [B, (nh + 2 nkv) D], contiguous: one new token per sequence, rotated at pos[b] and written
+//     into cache row pos[b]; -> q [B, nh, D] (`decode_rope_append` in the messages).
+//   qkv [B, T, (nh + 2 nkv) D]: any batch / token strides (multiples of 8 elements) over contiguous
+//     rows, so the model's sequence-first [T, B, W] is passed as a transposed view without a copy.
+//     Token t of sequence b is rotated at pos[b] + t and appended to that cache row; -> q [B, T, nh,
+//     D] (`decode_rope_append_multi`).
 Tensor decode_rope_append(Tensor qkv, Tensor k_cache, Tensor v_cache, Tensor pos, int64_t nh, OptT cos_t,
                           OptT sin_t, int64_t rot) {
-  need_contig(qkv, "qkv");
-  TORCH_CHECK(qkv.dim() == 2, "decode_rope_append: qkv must be [B, (nh + 2 nkv) D]");
-  dec_check_cache(k_cache, v_cache, qkv, "decode_rope_append");
-  const int64_t B = qkv.size(0), cap = k_cache.size(1), nkv = k_cache.size(2), D = k_cache.size(3);
-  TORCH_CHECK(nh > 0 && nh < (1 << 20) && D % 8 == 0 && D < (1 << 20) && qkv.size(1) == (nh + 2 * nkv) * D,
-              "decode_rope_append: qkv width ", qkv.size(1), " is not (nh + 2 nkv) D with D % 8 == 0");
-  const int* pp = dec_index(pos, qkv, "decode_rope_append");
-  const RopeTables rt = dec_rope_tables(cos_t, sin_t, rot, D, qkv, "decode_rope_append");
-  auto q = torch::empty({B, nh, D}, qkv.options());
-  check(smdt_decode_rope_append(dcode(qkv), qkv.data_ptr(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-                                pp, (int)B, (int)nh, (int)nkv, (int)D, (int)cap, (int)rot, rt.cos, rt.sin,
-                                (int)rt.max_pos, cur_stream()),
-        "decode_rope_append");
+  const bool multi = qkv.dim() == 3;
+  const char* what = multi ? "decode_rope_append_multi" : "decode_rope_append";
+  if (multi) {
+    TORCH_CHECK(qkv.is_cuda(), "decode_rope_append_multi: qkv must be a GPU [B, T, (nh + 2 nkv) D]");
+  } else {
+    need_contig(qkv, "qkv");
+    TORCH_CHECK(qkv.dim() == 2, "decode_rope_append: qkv must be [B, (nh + 2 nkv) D]");
+  }
+  dec_check_cache(k_cache, v_cache, qkv, what);
+  const int64_t B = qkv.size(0), T = multi ? qkv.size(1) : 1, cap = k_cache.size(1), nkv = k_cache.size(2),
+                D = k_cache.size(3);
+  if (multi)
+    TORCH_CHECK(T >= 1 && T <= smdt_decode_attn_multi_max_t(), "decode_rope_append_multi: T ", T, " is outside 1 .. ",
+                smdt_decode_attn_multi_max_t());
+  dec_check_qkv(qkv, nh, nkv, D, what);
+  if (multi)
+    TORCH_CHECK(qkv.stride(2) == 1 && qkv.stride(0) % 8 == 0 && qkv.stride(1) % 8 == 0 && qkv.stride(0) >= 0 &&
+                    qkv.stride(1) >= 0 && aligned16(qkv),
+                "decode_rope_append_multi: qkv rows must be contiguous and 16-byte aligned (strides ", qkv.strides(), ")");
+  const int* pp = dec_index(pos, qkv, what);
+  const RopeTables rt = dec_rope_tables(cos_t, sin_t, rot, D, qkv, what);
+  auto q = multi ? torch::empty({B, T, nh, D}, qkv.options()) : torch::empty({B, nh, D}, qkv.options());
+  check(smdt_decode_rope_append_multi(dcode(qkv), qkv.data_ptr(), multi ? qkv.stride(0) : qkv.size(1),
+                                      multi ? qkv.stride(1) : 0, q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                                      pp, (int)B, (int)T, (int)nh, (int)nkv, (int)D, (int)cap, (int)rot, rt.cos, rt.sin,
+                                      (int)rt.max_pos, cur_stream()),
+        what);
   return q;
 }
 
@@ -1115,54 +1152,20 @@ Tensor decode_attn_multi(Tensor q, Tensor k_cache, Tensor v_cache, Tensor lens, 
   TORCH_CHECK(decode_attn_multi_supported(dcode(q), D, nh, nkv, T) && T * nh <= 65535,
               "decode_attn_multi: unsupported (needs D in {64, 128}, nh / nkv in {1, 2, 4, 8} and 1 <= T <= ",
               smdt_decode_attn_multi_max_t(), "): D ", D, ", nh ", nh, ", nkv ", nkv, ", T ", T);
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(k_cache.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(v_cache.data_ptr()) % 16 == 0,
+  TORCH_CHECK(aligned16(q) && aligned16(k_cache) && aligned16(v_cache),
               "decode_attn_multi: q and the caches must be 16-byte aligned");
-  if (max_len <= 0) max_len = cap;
-  TORCH_CHECK(max_len <= cap, "decode_attn_multi: max_len ", max_len, " exceeds the cache capacity ", cap);
+  const DecWork w = dec_work(q, cap, max_len, T * nh, D, "decode_attn_multi");
   const int* lp = dec_index(lens, q, "decode_attn_multi");
-  const int64_t C = smdt_decode_attn_chunk();
-  const int64_t nchunks = (max_len + C - 1) / C;
-  auto f32 = q.options().dtype(at::kFloat);
-  auto ws_ml = torch::empty({B, T * nh, nchunks, 2}, f32);
-  auto ws_acc = torch::empty({B, T * nh, nchunks, D}, f32);
   auto out = torch::empty_like(q);
   check(smdt_decode_attn_multi(dcode(q), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), lp,
-                               ws_ml.data_ptr<float>(), ws_acc.data_ptr<float>(), out.data_ptr(), (int)B, (int)T,
-                               (int)nh, (int)nkv, (int)D, (int)cap, (int)max_len, (float)scale, cur_stream()),
+                               w.ws_ml.data_ptr<float>(), w.ws_acc.data_ptr<float>(), out.data_ptr(), (int)B, (int)T,
+                               (int)nh, (int)nkv, (int)D, (int)cap, (int)w.max_len, (float)scale, cur_stream()),
         "decode_attn_multi");
   return out;
 }
 
-// qkv [B, T, (nh + 2 nkv) D]: any batch / token strides (multiples of 8 elements) over contiguous
-// rows, so the model's sequence-first [T, B, W] is passed as a transposed view without a copy.
-// Token t of sequence b is rotated at pos[b] + t and appended to that cache row; -> q [B, T, nh, D].
-Tensor decode_rope_append_multi(Tensor qkv, Tensor k_cache, Tensor v_cache, Tensor pos, int64_t nh, OptT cos_t,
-                                OptT sin_t, int64_t rot) {
-  TORCH_CHECK(qkv.is_cuda() && qkv.dim() == 3, "decode_rope_append_multi: qkv must be a GPU [B, T, (nh + 2 nkv) D]");
-  dec_check_cache(k_cache, v_cache, qkv, "decode_rope_append_multi");
-  const int64_t B = qkv.size(0), T = qkv.size(1), cap = k_cache.size(1), nkv = k_cache.size(2), D = k_cache.size(3);
-  TORCH_CHECK(T >= 1 && T <= smdt_decode_attn_multi_max_t(), "decode_rope_append_multi: T ", T, " is outside 1 .. ",
-              smdt_decode_attn_multi_max_t());
-  TORCH_CHECK(nh > 0 && nh < (1 << 20) && D % 8 == 0 && D < (1 << 20) && qkv.size(2) == (nh + 2 * nkv) * D,
-              "decode_rope_append_multi: qkv width ", qkv.size(2), " is not (nh + 2 nkv) D with D % 8 == 0");
-  TORCH_CHECK(qkv.stride(2) == 1 && qkv.stride(0) % 8 == 0 && qkv.stride(1) % 8 == 0 && qkv.stride(0) >= 0 &&
-                  qkv.stride(1) >= 0 && reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0,
-              "decode_rope_append_multi: qkv rows must be contiguous and 16-byte aligned (strides ", qkv.strides(), ")");
-  const int* pp = dec_index(pos, qkv, "decode_rope_append_multi");
-  const RopeTables rt = dec_rope_tables(cos_t, sin_t, rot, D, qkv, "decode_rope_append_multi");
-  auto q = torch::empty({B, T, nh, D}, qkv.options());
-  check(smdt_decode_rope_append_multi(dcode(qkv), qkv.data_ptr(), qkv.stride(0), qkv.stride(1), q.data_ptr(),
-                                      k_cache.data_ptr(), v_cache.data_ptr(), pp, (int)B, (int)T, (int)nh, (int)nkv,
-                                      (int)D, (int)cap, (int)rot, rt.cos, rt.sin, (int)rt.max_pos, cur_stream()),
-        "decode_rope_append_multi");
-  return q;
-}
-
 // ------------------------------------------------------------------ MXFP8 K/V cache (decode_attn_mx.hip)
 // kq / vq [B, cap, nkv, D] E4M3, ksc / vsc [B, cap, nkv, D / 32] uint8 E8M0; q / qkv stay 16-bit.
-static bool aligned16(const Tensor& t);
 static void dec_check_cache_mx(const Tensor& kq, const Tensor& ks, const Tensor& vq, const Tensor& vs,
                                const Tensor& like, const char* what) {
   TORCH_CHECK(like.scalar_type() == at::kBFloat16 || like.scalar_type() == at::kHalf, what,
@@ -1194,18 +1197,12 @@ Tensor decode_attn_mx(Tensor q, Tensor kq, Tensor ks, Tensor vq, Tensor vs, Tens
               "decode_attn_mx: unsupported (needs D in {64, 128} and nh / nkv in {1, 2, 4, 8}): D ", D, ", nh ", nh,
               ", nkv ", nkv);
   TORCH_CHECK(aligned16(q), "decode_attn_mx: q must be 16-byte aligned");
-  if (max_len <= 0) max_len = cap;
-  TORCH_CHECK(max_len <= cap, "decode_attn_mx: max_len ", max_len, " exceeds the cache capacity ", cap);
+  const DecWork w = dec_work(q, cap, max_len, nh, D, "decode_attn_mx");
   const int* lp = dec_index(lens, q, "decode_attn_mx");
-  const int64_t C = smdt_decode_attn_chunk();
-  const int64_t nchunks = (max_len + C - 1) / C;
-  auto f32 = q.options().dtype(at::kFloat);
-  auto ws_ml = torch::empty({B, nh, nchunks, 2}, f32);
-  auto ws_acc = torch::empty({B, nh, nchunks, D}, f32);
   auto out = torch::empty_like(q);
   check(smdt_decode_attn_mx(dcode(q), q.data_ptr(), kq.data_ptr(), ks.data_ptr(), vq.data_ptr(), vs.data_ptr(), lp,
-                            ws_ml.data_ptr<float>(), ws_acc.data_ptr<float>(), out.data_ptr(), (int)B, (int)nh,
-                            (int)nkv, (int)D, (int)cap, (int)max_len, (float)scale, cur_stream()),
+                            w.ws_ml.data_ptr<float>(), w.ws_acc.data_ptr<float>(), out.data_ptr(), (int)B, (int)nh,
+                            (int)nkv, (int)D, (int)cap, (int)w.max_len, (float)scale, cur_stream()),
         "decode_attn_mx");
   return out;
 }
@@ -1216,8 +1213,7 @@ Tensor decode_rope_append_mx(Tensor qkv, Tensor kq, Tensor ks, Tensor vq, Tensor
   TORCH_CHECK(qkv.dim() == 2, "decode_rope_append_mx: qkv must be [B, (nh + 2 nkv) D]");
   dec_check_cache_mx(kq, ks, vq, vs, qkv, "decode_rope_append_mx");
   const int64_t B = qkv.size(0), cap = kq.size(1), nkv = kq.size(2), D = kq.size(3);
-  TORCH_CHECK(nh > 0 && nh < (1 << 20) && D < (1 << 20) && qkv.size(1) == (nh + 2 * nkv) * D,
-              "decode_rope_append_mx: qkv width ", qkv.size(1), " is not (nh + 2 nkv) D");
+  dec_check_qkv(qkv, nh, nkv, D, "decode_rope_append_mx");
   TORCH_CHECK(nkv * D <= 8192, "decode_rope_append_mx: nkv * D = ", nkv * D, " exceeds 8192 (the kernel stages the "
               "token's k and v rows in LDS)");
   TORCH_CHECK(aligned16(qkv), "decode_rope_append_mx: qkv must be 16-byte aligned");
@@ -1253,8 +1249,6 @@ std::vector<int64_t> decode_linear_plan(int64_t fmt, int64_t N, int64_t K) {
   smdt_decode_linear_plan((int)fmt, N, K, &s, &sl);
   return {s, sl};
 }
-
-static bool aligned16(const Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0; }
 
 Tensor decode_linear(Tensor x, Tensor w, OptT scales, OptT bias, int64_t fmt, OptT workspace, OptT out_) {
   need_contig(x, "x");
@@ -1701,8 +1695,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         arg("T"));
   m.def("decode_attn_multi", &decode_attn_multi, arg("q"), arg("k_cache"), arg("v_cache"), arg("lens"), arg("scale"),
         arg("max_len") = 0);
-  m.def("decode_rope_append_multi", &decode_rope_append_multi, arg("qkv"), arg("k_cache"), arg("v_cache"), arg("pos"),
-        arg("nh"), arg("cos") = pybind11::none(), arg("sin") = pybind11::none(), arg("rot") = 0);
   m.def("decode_attn_mx", &decode_attn_mx, arg("q"), arg("kq"), arg("ks"), arg("vq"), arg("vs"), arg("lens"),
         arg("scale"), arg("max_len") = 0);
   m.def("decode_rope_append_mx", &decode_rope_append_mx, arg("qkv"), arg("kq"), arg("ks"), arg("vq"), arg("vs"),

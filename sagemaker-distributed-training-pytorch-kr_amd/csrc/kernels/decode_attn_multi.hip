@@ -1,16 +1,17 @@
 // A decode step with T new tokens per sequence for gfx950 (speculative verification: the target
 // model checks k drafted tokens and the last emitted one, T = k + 1, in one pass over its weights).
 //
-//   smdt_decode_rope_append_multi  RoPE on the T new tokens' q / k and the append of their k / v
-//                                  into cache rows pos[b] .. pos[b] + T - 1
+//   smdt_decode_rope_append_multi  RoPE on the T new tokens' q / k (bitwise rope.hip's) and the
+//                                  append of their k / v into cache rows pos[b] .. pos[b] + T - 1;
+//                                  T = 1 is the single-token decode step's append
 //   smdt_decode_attn_multi         split-KV attention of q [B, T, nh, D] against k / v
 //                                  [B, cap, nkv, D]; query t sees keys 0 .. lens[b] - T + t
 //
-// As in decode_attn.hip no length is read on the host (`lens` / `pos` are device int32 [B]), there
-// are no atomics and the result is bitwise repeatable.
+// decode_common.h states the guarantees these keep (lengths stay on the device, nothing beyond
+// lens[b] is loaded, masking by selection, fixed order, no atomics).
 //
-// Attention. The grid is decode_attn.hip's: one 256-thread workgroup per (key chunk of 256, kv
-// head, sequence). It serves all R = T G query rows of its kv head (G = nh / nkv; row r = t G + g),
+// Attention. The grid is the single-query kernel's: one 256-thread workgroup per (key chunk of 256,
+// kv head, sequence). It serves all R = T G query rows of its kv head (G = nh / nkv; row r = t G + g),
 // so every cache byte is still read once. With R rows the score and P V products are matrix
 // products and run on v_mfma_f32_16x16x32 (lane l: c = l & 15, qd = l >> 4; A[row c][k = 8 qd + j],
 // B[k = 8 qd + j][col c], D[row 4 qd + reg][col c]); the rows are padded to RT = ceil(R / 16) tiles
@@ -37,15 +38,14 @@
 // Partials go to decode_attn.hip's workspace with nh' = T nh heads per sequence and head t nh + h;
 // smdt_decode_attn_combine finishes them (a row with no visible key in a chunk has l = 0 there and
 // is skipped by selection; a query with no visible key at all returns zeros).
-#include "common.h"
+#include "decode_common.h"
 #include "launchers.h"
 #include "mfma_tile.h"
 
 namespace smdt {
 
-constexpr int kMtChunk = 256;     // == smdt_decode_attn_chunk(), checked at launch
-constexpr int kMtThreads = 256;
-constexpr int kMtMaxT = 8;        // R = T G <= 64: four 16-row tiles
+constexpr int kDecMultiMaxT = 8;        // R = T G <= 64: four 16-row tiles
+static_assert(kDecChunk == 256 && kDecThreads == 256, "four waves of 64 keys: the tiling below is written for 256");
 
 __device__ __forceinline__ f32x4 mt_mma(bf16x8 a, bf16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
@@ -55,7 +55,7 @@ __device__ __forceinline__ f32x4 mt_mma(mt::f16x8 a, mt::f16x8 b, f32x4 c) {
 }
 
 template <typename E, int D, int RT>
-__global__ __launch_bounds__(kMtThreads) void decode_attn_multi_kernel(
+__global__ __launch_bounds__(kDecThreads) void decode_attn_multi_kernel(
     const E* __restrict__ q, const E* __restrict__ kc, const E* __restrict__ vc, const int* __restrict__ lens,
     float* __restrict__ ws_ml, float* __restrict__ ws_acc, int cap, int nkv, int G, int Tn, float scale) {
   using V8 = mt::v8_t<E>;
@@ -70,20 +70,15 @@ __global__ __launch_bounds__(kMtThreads) void decode_attn_multi_kernel(
   const int nchunks = gridDim.x, nh = nkv * G, R = Tn * G;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int c = lane & 15, qd = lane >> 4;
-  int len = lens[b];
-  len = len < 0 ? 0 : (len > cap ? cap : len);
-  const int k0 = chunk * kMtChunk;
+  const int len = dec_clamp_len(lens[b], cap);
+  const int k0 = chunk * kDecChunk;
   // workspace index of query row r = t G + g: head t nh + kvh G + g of nh' = T nh
   auto part = [&](int r) -> int64_t {
     const int t = r / G, g = r - t * G;
-    return ((int64_t)b * Tn * nh + (int64_t)t * nh + kvh * G + g) * nchunks + chunk;
+    return dec_part((int64_t)b * Tn * nh + (int64_t)t * nh + kvh * G + g, nchunks, chunk);
   };
-  if (k0 >= len) {      // no key of this sequence in the chunk: partials the combine skips
-    if (tid < R) {
-      const int64_t p = part(tid);
-      ws_ml[p * 2] = -INFINITY;
-      ws_ml[p * 2 + 1] = 0.f;
-    }
+  if (k0 >= len) {
+    if (tid < R) dec_store_empty(ws_ml, part(tid));
     return;
   }
   __shared__ __attribute__((aligned(16))) char smem[kStage > kRed ? kStage : kRed];
@@ -242,60 +237,25 @@ __global__ __launch_bounds__(kMtThreads) void decode_attn_multi_kernel(
   if (tid < R) {        // red_l was written before the product's barriers
     const float m = fmaxf(fmaxf(red_m[0][tid], red_m[1][tid]), fmaxf(red_m[2][tid], red_m[3][tid]));
     const float l = ((red_l[0][tid] + red_l[1][tid]) + red_l[2][tid]) + red_l[3][tid];
-    const int64_t p = part(tid);
-    ws_ml[p * 2] = m;
-    ws_ml[p * 2 + 1] = l;
+    dec_store_ml(ws_ml, part(tid), m, l);
   }
 }
 
-// decode_attn.hip's decode_rope_append_kernel (its arithmetic, statement for statement, so the
-// bytes equal T calls of it) with one workgroup per (token t, sequence b): the token's row is at
+// The 16-bit RoPE-and-append kernel, one workgroup per (token t, sequence b): the token's row is at
 // qkv + b stride_b + t stride_t, its position is pos[b] + t, q goes to q_out [B, T, nh, D] and k /
-// v to cache row pos[b] + t. A position outside [0, cap) or the table writes nothing.
+// v to cache row pos[b] + t (dec_rope_token). A position outside [0, cap) or the table writes
+// nothing. One new token per sequence is T = 1 with stride_b = (nh + 2 nkv) D.
 template <typename T>
-__global__ __launch_bounds__(256) void decode_rope_append_multi_kernel(
+__global__ __launch_bounds__(256) void decode_rope_append_kernel(
     const T* __restrict__ qkv, int64_t stride_b, int64_t stride_t, T* __restrict__ q_out, T* __restrict__ kc,
     T* __restrict__ vc, const int* __restrict__ pos_t, int nh, int nkv, int D, int cap, int rot,
     const float* __restrict__ cos_t, const float* __restrict__ sin_t, int max_pos, float sign) {
   const int t = blockIdx.x, b = blockIdx.y, Tn = gridDim.x;
   const int64_t pos = (int64_t)pos_t[b] + t;
-  if (pos < 0 || pos >= cap || (rot > 0 && pos >= max_pos)) return;
-  const int half = rot / 2;
-  const int groups = half / 8;              // rotated 8-pair groups per head
-  const int tail = (D - rot) / 8;           // unrotated 16-byte pieces per head
-  const T* src = qkv + (int64_t)b * stride_b + (int64_t)t * stride_t;
-  T* qd = q_out + ((int64_t)b * Tn + t) * nh * D;
-  T* kd = kc + ((int64_t)b * cap + pos) * nkv * D;
-  T* vd = vc + ((int64_t)b * cap + pos) * nkv * D;
-  const float* ct = cos_t + pos * half;
-  const float* stb = sin_t + pos * half;
-  for (int i = threadIdx.x; i < (nh + nkv) * groups; i += 256) {
-    const int h = i / groups, gidx = i - h * groups;
-    const T* base = src + (int64_t)h * D + gidx * 8;
-    T* dst = (h < nh ? qd + (int64_t)h * D : kd + (int64_t)(h - nh) * D) + gidx * 8;
-    float a[8], bb[8], c[8], s[8];
-    load_vec<T, 8>(base, a);
-    load_vec<T, 8>(base + half, bb);
-    load_vec<float, 8>(ct + gidx * 8, c);
-    load_vec<float, 8>(stb + gidx * 8, s);
-    float oa[8], ob[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float sn = sign * s[j];
-      oa[j] = a[j] * c[j] - bb[j] * sn;
-      ob[j] = bb[j] * c[j] + a[j] * sn;
-    }
-    store_vec<T, 8>(dst, oa);
-    store_vec<T, 8>(dst + half, ob);
-  }
-  for (int i = threadIdx.x; i < (nh + nkv) * tail; i += 256) {
-    const int h = i / tail, o = rot + (i - h * tail) * 8;
-    T* dst = (h < nh ? qd + (int64_t)h * D : kd + (int64_t)(h - nh) * D) + o;
-    *reinterpret_cast<u16x8*>(dst) = *reinterpret_cast<const u16x8*>(src + (int64_t)h * D + o);
-  }
-  const T* vs = src + (int64_t)(nh + nkv) * D;
-  for (int i = threadIdx.x; i < nkv * D / 8; i += 256)
-    *reinterpret_cast<u16x8*>(vd + i * 8) = *reinterpret_cast<const u16x8*>(vs + i * 8);
+  if (!dec_pos_ok(pos, cap, rot, max_pos)) return;
+  const int64_t row = ((int64_t)b * cap + pos) * nkv * D;
+  dec_rope_token(qkv + (int64_t)b * stride_b + (int64_t)t * stride_t, q_out + ((int64_t)b * Tn + t) * nh * D, kc + row,
+                 vc + row, pos, nh, nkv, D, rot, cos_t, sin_t, sign);
 }
 
 template <typename E, int D>
@@ -305,7 +265,7 @@ hipError_t decode_attn_multi_launch(const void* q, const void* kc, const void* v
   const dim3 grid((unsigned)nchunks, (unsigned)nkv, (unsigned)B);
   const int G = nh / nkv;
 #define SMDT_DEC_MT(RT)                                                                                     \
-  hipLaunchKernelGGL((decode_attn_multi_kernel<E, D, RT>), grid, dim3(kMtThreads), 0, st, (const E*)q,      \
+  hipLaunchKernelGGL((decode_attn_multi_kernel<E, D, RT>), grid, dim3(kDecThreads), 0, st, (const E*)q,     \
                      (const E*)kc, (const E*)vc, lens, ws_ml, ws_acc, cap, nkv, G, Tn, scale)
   switch ((Tn * G + 15) / 16) {
     case 1: SMDT_DEC_MT(1); break;
@@ -322,28 +282,23 @@ hipError_t decode_attn_multi_launch(const void* q, const void* kc, const void* v
 
 using namespace smdt;
 
-extern "C" int smdt_decode_attn_multi_max_t() { return kMtMaxT; }
+extern "C" int smdt_decode_attn_multi_max_t() { return kDecMultiMaxT; }
 
 extern "C" int smdt_decode_attn_multi_supported(int dtype, int D, int nh, int nkv, int T) {
-  return smdt_decode_attn_supported(dtype, D, nh, nkv) && T >= 1 && T <= kMtMaxT;
+  return smdt_decode_attn_supported(dtype, D, nh, nkv) && T >= 1 && T <= kDecMultiMaxT;
 }
 
 extern "C" hipError_t smdt_decode_attn_multi(int dtype, const void* q, const void* k_cache, const void* v_cache,
                                              const int* lens, float* ws_ml, float* ws_acc, void* out, int B, int T,
                                              int nh, int nkv, int D, int cap, int max_len, float scale,
                                              hipStream_t st) {
-  if (!smdt_decode_attn_multi_supported(dtype, D, nh, nkv, T) || smdt_decode_attn_chunk() != kMtChunk || B <= 0 ||
-      B > 65535 || nkv > 65535 || (int64_t)T * nh > 65535 || cap <= 0 || max_len <= 0 || max_len > cap)
+  const int nchunks = dec_nchunks(B, nkv, cap, max_len);
+  if (!smdt_decode_attn_multi_supported(dtype, D, nh, nkv, T) || (int64_t)T * nh > 65535 || nchunks == 0)
     return hipErrorInvalidValue;
-  const int nchunks = (max_len + kMtChunk - 1) / kMtChunk;
-  hipError_t e;
-  if (dtype == 1) {
-    if (D == 64) e = decode_attn_multi_launch<bf16, 64>(q, k_cache, v_cache, lens, ws_ml, ws_acc, B, T, nh, nkv, cap, nchunks, scale, st);
-    else e = decode_attn_multi_launch<bf16, 128>(q, k_cache, v_cache, lens, ws_ml, ws_acc, B, T, nh, nkv, cap, nchunks, scale, st);
-  } else {
-    if (D == 64) e = decode_attn_multi_launch<f16, 64>(q, k_cache, v_cache, lens, ws_ml, ws_acc, B, T, nh, nkv, cap, nchunks, scale, st);
-    else e = decode_attn_multi_launch<f16, 128>(q, k_cache, v_cache, lens, ws_ml, ws_acc, B, T, nh, nkv, cap, nchunks, scale, st);
-  }
+  const hipError_t e = dec_dispatch(dtype, D, [&](auto tag, auto d) {
+    return decode_attn_multi_launch<typename decltype(tag)::type, decltype(d)::value>(
+        q, k_cache, v_cache, lens, ws_ml, ws_acc, B, T, nh, nkv, cap, nchunks, scale, st);
+  });
   if (e != hipSuccess) return e;
   return smdt_decode_attn_combine(dtype, ws_ml, ws_acc, lens, out, B, T * nh, D, cap, nchunks, st);
 }
@@ -353,18 +308,14 @@ extern "C" hipError_t smdt_decode_rope_append_multi(int dtype, const void* qkv, 
                                                     int T, int nh, int nkv, int D, int cap, int rot,
                                                     const float* cos_t, const float* sin_t, int max_pos,
                                                     hipStream_t st) {
-  if ((dtype != 1 && dtype != 2) || B <= 0 || B > 65535 || T <= 0 || T > kMtMaxT || D % 8 || rot % 16 || rot < 0 ||
-      rot > D || cap <= 0 || stride_b % 8 || stride_t % 8 ||
-      (rot > 0 && (cos_t == nullptr || sin_t == nullptr || max_pos <= 0)))
+  if (B <= 0 || B > 65535 || T <= 0 || T > kDecMultiMaxT || D % 8 || rot % 16 || rot < 0 || rot > D || cap <= 0 ||
+      stride_b % 8 || stride_t % 8 || (rot > 0 && (cos_t == nullptr || sin_t == nullptr || max_pos <= 0)))
     return hipErrorInvalidValue;
-  const dim3 grid((unsigned)T, (unsigned)B);
-  if (dtype == 1)
-    hipLaunchKernelGGL(decode_rope_append_multi_kernel<bf16>, grid, dim3(256), 0, st, (const bf16*)qkv, stride_b,
-                       stride_t, (bf16*)q_out, (bf16*)k_cache, (bf16*)v_cache, pos, nh, nkv, D, cap, rot, cos_t, sin_t,
+  return dec_dispatch(dtype, [&](auto tag) {
+    using E = typename decltype(tag)::type;
+    hipLaunchKernelGGL(decode_rope_append_kernel<E>, dim3((unsigned)T, (unsigned)B), dim3(256), 0, st, (const E*)qkv,
+                       stride_b, stride_t, (E*)q_out, (E*)k_cache, (E*)v_cache, pos, nh, nkv, D, cap, rot, cos_t, sin_t,
                        max_pos, 1.f);
-  else
-    hipLaunchKernelGGL(decode_rope_append_multi_kernel<f16>, grid, dim3(256), 0, st, (const f16*)qkv, stride_b,
-                       stride_t, (f16*)q_out, (f16*)k_cache, (f16*)v_cache, pos, nh, nkv, D, cap, rot, cos_t, sin_t,
-                       max_pos, 1.f);
-  return hipGetLastError();
+    return hipGetLastError();
+  });
 }

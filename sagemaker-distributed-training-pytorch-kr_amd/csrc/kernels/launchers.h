@@ -150,7 +150,8 @@ hipError_t smdt_flash_bwd_sums(int dtype, const void* q, const void* k, const vo
                                float scale, int causal, float dropout_p, uint64_t seed, uint64_t offset,
                                const int* doc_start, const int* doc_end, float* colpart, hipStream_t st);
 
-// decode_attn.hip: incremental decoding. smdt_decode_attn: out [B, nh, D] = attention of one query
+// decode_attn.hip: incremental decoding (decode_common.h holds what the three decode files share,
+// kernels and guarantees). smdt_decode_attn: out [B, nh, D] = attention of one query
 // per sequence, q [B, nh, D], against k_cache / v_cache [B, cap, nkv, D] (contiguous, q's dtype:
 // bf16 / fp16), keys 0 .. lens[b] - 1 (device int32 [B]); max_len <= cap only bounds the grid.
 // Two launches, no atomics. Workspaces for nchunks = ceil(max_len / smdt_decode_attn_chunk()):
@@ -161,12 +162,6 @@ int smdt_decode_attn_supported(int dtype, int D, int nh, int nkv);
 hipError_t smdt_decode_attn(int dtype, const void* q, const void* k_cache, const void* v_cache, const int* lens,
                             float* ws_ml, float* ws_acc, void* out, int B, int nh, int nkv, int D, int cap,
                             int max_len, float scale, hipStream_t st);
-// qkv [B, (nh + 2 nkv) D] of one new token per sequence: q / k rotated at pos[b] (device int32 [B])
-// over their first rot elements (rope.hip's arithmetic bit for bit; rot == 0: no RoPE, tables
-// unused), q -> q_out [B, nh, D], k / v -> row pos[b] of the caches. cos / sin fp32 [max_pos, rot / 2].
-hipError_t smdt_decode_rope_append(int dtype, const void* qkv, void* q_out, void* k_cache, void* v_cache,
-                                   const int* pos, int B, int nh, int nkv, int D, int cap, int rot,
-                                   const float* cos_t, const float* sin_t, int max_pos, hipStream_t st);
 // The second launch of smdt_decode_attn alone, over partials in its workspace layout.
 hipError_t smdt_decode_attn_combine(int dtype, const float* ws_ml, const float* ws_acc, const int* lens, void* out,
                                     int B, int nh, int D, int cap, int nchunks, hipStream_t st);
@@ -184,10 +179,12 @@ int smdt_decode_attn_multi_supported(int dtype, int D, int nh, int nkv, int T);
 hipError_t smdt_decode_attn_multi(int dtype, const void* q, const void* k_cache, const void* v_cache,
                                   const int* lens, float* ws_ml, float* ws_acc, void* out, int B, int T, int nh,
                                   int nkv, int D, int cap, int max_len, float scale, hipStream_t st);
-// qkv: token t of sequence b at qkv + b * stride_b + t * stride_t (elements; rows of (nh + 2 nkv) D
-// contiguous elements, so both [B, T, W] and the model's [T, B, W] are taken without a copy). Token
-// t is rotated at pos[b] + t and appended to cache row pos[b] + t; q -> q_out [B, T, nh, D]. The
-// arithmetic of smdt_decode_rope_append, so the bytes equal T calls of it.
+// The 16-bit RoPE-and-append, for one new token per sequence (T = 1, stride_b = (nh + 2 nkv) D) and
+// for T of them. qkv: token t of sequence b at qkv + b * stride_b + t * stride_t (elements; rows of
+// (nh + 2 nkv) D contiguous elements, so both [B, T, W] and the model's [T, B, W] are taken without
+// a copy). Token t's q / k are rotated at pos[b] + t (device int32 [B]) over their first rot
+// elements (rope.hip's arithmetic bit for bit; rot == 0: no RoPE, tables unused; cos / sin fp32
+// [max_pos, rot / 2]); q -> q_out [B, T, nh, D], k / v -> cache row pos[b] + t.
 hipError_t smdt_decode_rope_append_multi(int dtype, const void* qkv, int64_t stride_b, int64_t stride_t,
                                          void* q_out, void* k_cache, void* v_cache, const int* pos, int B, int T,
                                          int nh, int nkv, int D, int cap, int rot, const float* cos_t,

@@ -820,11 +820,49 @@ def apply_rope(x, cos, sin, pos_div: int, pos_mod: int, rot: Optional[int] = Non
 
 
 # --------------------------------------------------------------------------------------------
-# Incremental decoding (csrc/kernels/decode_attn.hip): one new token per sequence against a K/V
-# cache [B, cap, nkv, D]. Lengths and positions are device int32 [B] tensors and are never read on
-# the host, so a decode step has static shapes and can be captured in a graph.
+# Incremental decoding (csrc/kernels/decode_attn.hip; decode_common.h holds what it shares with
+# the MXFP8 and multi-token files below): one new token per sequence against a K/V cache [B, cap,
+# nkv, D]. Lengths and positions are device int32 [B] tensors and are never read on the host, so a
+# decode step has static shapes and can be captured in a graph.
 
 DECODE_CHUNK = 256      # keys per workgroup of the split-KV kernel (smdt_decode_attn_chunk)
+
+
+def _decode_max_len(name, max_len, cap):
+    """The grid bound an attention wrapper hands its kernel: ``max_len`` (None: the capacity), in 1 .. cap."""
+    max_len = cap if max_len is None else int(max_len)
+    if not 0 < max_len <= cap:
+        raise ValueError(f"{name}: max_len {max_len} must be in 1 .. the capacity {cap}")
+    return max_len
+
+
+def _decode_check_qkv(name, qkv, nh, nkv, hd, lead="B"):
+    """qkv is [B, W] (``lead`` "B") or [B, T, W] ("B, T") with W = (nh + 2 nkv) hd."""
+    W = (nh + 2 * nkv) * hd
+    if qkv.dim() != lead.count(",") + 2 or qkv.shape[-1] != W:
+        raise ValueError(f"{name}: qkv {tuple(qkv.shape)} is not [{lead}, (nh + 2 nkv) hd] = [{lead}, {W}]")
+
+
+def _decode_check_caches(name, qkv, k_cache, v_cache, nkv, hd):
+    if tuple(k_cache.shape[2:]) != (nkv, hd) or k_cache.shape != v_cache.shape or k_cache.shape[0] != qkv.shape[0]:
+        raise ValueError(f"{name}: caches {tuple(k_cache.shape)} / {tuple(v_cache.shape)} are not "
+                         f"[B, cap, {nkv}, {hd}]")
+
+
+def _decode_check_append_gpu(name, qkv, k_cache, v_cache, hd, rope):
+    """What the 16-bit append kernel takes of GPU operands."""
+    if qkv.dtype not in (torch.bfloat16, torch.float16) or k_cache.dtype != qkv.dtype or v_cache.dtype != qkv.dtype \
+            or hd % 8 or (rope is not None and rope[2] % 16):
+        raise RuntimeError(f"{name} on the GPU needs bf16 / fp16 qkv and caches of one dtype, hd % 8 == 0 "
+                           f"and a rotary dim % 16 == 0; got {qkv.dtype} / {k_cache.dtype} / {v_cache.dtype}, hd {hd}")
+
+
+def _rope_args(rope):
+    """The append bindings' trailing arguments: (cos, sin, rot) of the model's tables, nothing without RoPE."""
+    if rope is None:
+        return ()
+    cos, sin, rot = rope
+    return cos, sin, int(rot)
 
 
 def decode_attention_supported(q, k_cache, v_cache=None) -> bool:
@@ -874,10 +912,7 @@ def decode_attention(q, k_cache, v_cache, lens, scale, max_len=None):
                            f"of one dtype, D in (64, 128) and nh / nkv in (1, 2, 4, 8); got q {tuple(q.shape)} "
                            f"{q.dtype}, k_cache {tuple(k_cache.shape)} {k_cache.dtype}, v_cache "
                            f"{tuple(v_cache.shape)} {v_cache.dtype}")
-    cap = k_cache.shape[1]
-    max_len = cap if max_len is None else int(max_len)
-    if not 0 < max_len <= cap:
-        raise ValueError(f"decode_attention: max_len {max_len} must be in 1 .. the capacity {cap}")
+    max_len = _decode_max_len("decode_attention", max_len, k_cache.shape[1])
     return _ext.ext().decode_attn(q.contiguous(), k_cache, v_cache, lens, float(scale), max_len)
 
 
@@ -910,22 +945,12 @@ def decode_rope_append(qkv, k_cache, v_cache, pos, nh, nkv, hd, rope=None):
     caches [B, cap, nkv, hd] and q [B, nh, hd] is returned. The rotation is bit for bit what the
     ``rope_`` kernel writes for the same row at the same position. GPU operands run the kernel or
     raise; CPU operands run the torch twin."""
-    if qkv.dim() != 2 or qkv.shape[1] != (nh + 2 * nkv) * hd:
-        raise ValueError(f"decode_rope_append: qkv {tuple(qkv.shape)} is not [B, (nh + 2 nkv) hd] = "
-                         f"[B, {(nh + 2 * nkv) * hd}]")
-    if tuple(k_cache.shape[2:]) != (nkv, hd) or k_cache.shape != v_cache.shape or k_cache.shape[0] != qkv.shape[0]:
-        raise ValueError(f"decode_rope_append: caches {tuple(k_cache.shape)} / {tuple(v_cache.shape)} are not "
-                         f"[B, cap, {nkv}, {hd}]")
+    _decode_check_qkv("decode_rope_append", qkv, nh, nkv, hd)
+    _decode_check_caches("decode_rope_append", qkv, k_cache, v_cache, nkv, hd)
     if not _ext.use_kernels(qkv, k_cache, v_cache):
         return decode_rope_append_ref(qkv, k_cache, v_cache, pos, nh, nkv, hd, rope)
-    if qkv.dtype not in (torch.bfloat16, torch.float16) or k_cache.dtype != qkv.dtype or v_cache.dtype != qkv.dtype \
-            or hd % 8 or (rope is not None and rope[2] % 16):
-        raise RuntimeError(f"decode_rope_append on the GPU needs bf16 / fp16 qkv and caches of one dtype, hd % 8 == 0 "
-                           f"and a rotary dim % 16 == 0; got {qkv.dtype} / {k_cache.dtype} / {v_cache.dtype}, hd {hd}")
-    if rope is None:
-        return _ext.ext().decode_rope_append(qkv.contiguous(), k_cache, v_cache, pos, nh)
-    cos, sin, rot = rope
-    return _ext.ext().decode_rope_append(qkv.contiguous(), k_cache, v_cache, pos, nh, cos, sin, int(rot))
+    _decode_check_append_gpu("decode_rope_append", qkv, k_cache, v_cache, hd, rope)
+    return _ext.ext().decode_rope_append(qkv.contiguous(), k_cache, v_cache, pos, nh, *_rope_args(rope))
 
 
 # --------------------------------------------------------------------------------------------
@@ -1018,10 +1043,7 @@ def decode_attention_multi(q, k_cache, v_cache, lens, scale, max_len=None):
                            f"{DECODE_MULTI_MAX_T} and 16-bit caches [B, cap, nkv, D] of q's dtype (not an MXFP8 cache), "
                            f"D in (64, 128) and nh / nkv in (1, 2, 4, 8); got q {tuple(q.shape)} {q.dtype}, k_cache "
                            f"{tuple(k_cache.shape)} {k_cache.dtype}, v_cache {tuple(v_cache.shape)} {v_cache.dtype}")
-    cap = k_cache.shape[1]
-    max_len = cap if max_len is None else int(max_len)
-    if not 0 < max_len <= cap:
-        raise ValueError(f"decode_attention_multi: max_len {max_len} must be in 1 .. the capacity {cap}")
+    max_len = _decode_max_len("decode_attention_multi", max_len, k_cache.shape[1])
     return _ext.ext().decode_attn_multi(q.contiguous(), k_cache, v_cache, lens, float(scale), max_len)
 
 
@@ -1041,27 +1063,16 @@ def decode_rope_append_multi(qkv, k_cache, v_cache, pos, nh, nkv, hd, rope=None)
     contiguous elements, strides multiples of 8 elements), so the model passes its sequence-first
     [T, B, W] projection as ``qkv.transpose(0, 1)`` and no copy is made; anything else is copied
     here. GPU operands run the kernel or raise; CPU operands run the torch twin."""
-    if qkv.dim() != 3 or qkv.shape[2] != (nh + 2 * nkv) * hd:
-        raise ValueError(f"decode_rope_append_multi: qkv {tuple(qkv.shape)} is not [B, T, (nh + 2 nkv) hd] = "
-                         f"[B, T, {(nh + 2 * nkv) * hd}]")
+    _decode_check_qkv("decode_rope_append_multi", qkv, nh, nkv, hd, lead="B, T")
     if not 1 <= qkv.shape[1] <= DECODE_MULTI_MAX_T:
         raise ValueError(f"decode_rope_append_multi: T = {qkv.shape[1]} is outside 1 .. {DECODE_MULTI_MAX_T}")
-    if tuple(k_cache.shape[2:]) != (nkv, hd) or k_cache.shape != v_cache.shape or k_cache.shape[0] != qkv.shape[0]:
-        raise ValueError(f"decode_rope_append_multi: caches {tuple(k_cache.shape)} / {tuple(v_cache.shape)} are not "
-                         f"[B, cap, {nkv}, {hd}]")
+    _decode_check_caches("decode_rope_append_multi", qkv, k_cache, v_cache, nkv, hd)
     if not _ext.use_kernels(qkv, k_cache, v_cache):
         return decode_rope_append_multi_ref(qkv, k_cache, v_cache, pos, nh, nkv, hd, rope)
-    if qkv.dtype not in (torch.bfloat16, torch.float16) or k_cache.dtype != qkv.dtype or v_cache.dtype != qkv.dtype \
-            or hd % 8 or (rope is not None and rope[2] % 16):
-        raise RuntimeError(f"decode_rope_append_multi on the GPU needs bf16 / fp16 qkv and caches of one dtype, hd % 8 "
-                           f"== 0 and a rotary dim % 16 == 0; got {qkv.dtype} / {k_cache.dtype} / {v_cache.dtype}, "
-                           f"hd {hd}")
+    _decode_check_append_gpu("decode_rope_append_multi", qkv, k_cache, v_cache, hd, rope)
     if qkv.stride(2) != 1 or qkv.stride(0) % 8 or qkv.stride(1) % 8 or qkv.data_ptr() % 16:
         qkv = qkv.contiguous()
-    if rope is None:
-        return _ext.ext().decode_rope_append_multi(qkv, k_cache, v_cache, pos, nh)
-    cos, sin, rot = rope
-    return _ext.ext().decode_rope_append_multi(qkv, k_cache, v_cache, pos, nh, cos, sin, int(rot))
+    return _ext.ext().decode_rope_append(qkv, k_cache, v_cache, pos, nh, *_rope_args(rope))     # 3-D: the T-token form
 
 
 # --------------------------------------------------------------------------------------------
@@ -1144,10 +1155,7 @@ def decode_attention_mx(q, kq, ks, vq, vs, lens, scale, max_len=None):
         raise RuntimeError(f"decode_attention_mx on the GPU needs bf16 / fp16 q [B, nh, D], an MXFP8 cache "
                            f"[B, cap, nkv, D], D in (64, 128) and nh / nkv in (1, 2, 4, 8); got q {tuple(q.shape)} "
                            f"{q.dtype}, cache {tuple(kq.shape)}")
-    cap = kq.shape[1]
-    max_len = cap if max_len is None else int(max_len)
-    if not 0 < max_len <= cap:
-        raise ValueError(f"decode_attention_mx: max_len {max_len} must be in 1 .. the capacity {cap}")
+    max_len = _decode_max_len("decode_attention_mx", max_len, kq.shape[1])
     return _ext.ext().decode_attn_mx(q.contiguous(), kq, ks, vq, vs, lens, float(scale), max_len)
 
 
@@ -1169,9 +1177,7 @@ def decode_rope_append_mx(qkv, kq, ks, vq, vs, pos, nh, nkv, hd, rope=None):
     32-block (``mx_quantize_ref``) and written, elements and scale bytes, into row pos[b]. A position
     outside the cache writes nothing. GPU operands run decode_attn_mx.hip or raise; CPU operands
     run the torch twin."""
-    if qkv.dim() != 2 or qkv.shape[1] != (nh + 2 * nkv) * hd:
-        raise ValueError(f"decode_rope_append_mx: qkv {tuple(qkv.shape)} is not [B, (nh + 2 nkv) hd] = "
-                         f"[B, {(nh + 2 * nkv) * hd}]")
+    _decode_check_qkv("decode_rope_append_mx", qkv, nh, nkv, hd)
     B, cap, ckv, D = _kv_mx_shapes(kq, ks, vq, vs, "decode_rope_append_mx")
     if (ckv, D) != (nkv, hd) or B != qkv.shape[0]:
         raise ValueError(f"decode_rope_append_mx: the cache {tuple(kq.shape)} is not [{qkv.shape[0]}, cap, {nkv}, {hd}]")
@@ -1183,10 +1189,7 @@ def decode_rope_append_mx(qkv, kq, ks, vq, vs, pos, nh, nkv, hd, rope=None):
     if nkv * hd > _KV_MX_MAX_ROW:
         raise RuntimeError(f"decode_rope_append_mx: nkv * hd = {nkv * hd} exceeds {_KV_MX_MAX_ROW}, the k / v row the "
                            "kernel stages in LDS")
-    if rope is None:
-        return _ext.ext().decode_rope_append_mx(qkv.contiguous(), kq, ks, vq, vs, pos, nh)
-    cos, sin, rot = rope
-    return _ext.ext().decode_rope_append_mx(qkv.contiguous(), kq, ks, vq, vs, pos, nh, cos, sin, int(rot))
+    return _ext.ext().decode_rope_append_mx(qkv.contiguous(), kq, ks, vq, vs, pos, nh, *_rope_args(rope))
 
 
 def kv_store_mx_ref(k, v, kq, ks, vq, vs):

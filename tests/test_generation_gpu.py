@@ -141,6 +141,26 @@ def test_decode_rope_append_bitwise(dtype, nh, nkv, D, rot):
     assert torch.equal(kc, k0) and torch.equal(vc, v0)
 
 
+@pytest.mark.parametrize("dtype", DTYPES, ids=["bf16", "fp16"])
+def test_decode_rope_append_of_a_slice(dtype):
+    """A [B, W] slice with a non-zero, 16-byte aligned storage offset gives the bytes of its
+    contiguous clone: one token is the strided T-token kernel at T = 1, stride W."""
+    nh, nkv, D, rot, B, cap = 4, 2, 64, 64, 4, 40
+    g = _gen(9)
+    big = torch.randn(B + 2, (nh + 2 * nkv) * D, device="cuda", generator=g).to(dtype)
+    part = big[1:1 + B]
+    assert part.storage_offset() > 0 and part.data_ptr() % 16 == 0 and part.is_contiguous()
+    pos = torch.tensor([0, cap - 1, 17, 5], dtype=torch.int32, device="cuda")
+    rope = (*SF.rope_tables(cap, rot, device="cuda"), rot)
+    kc = torch.randn(B, cap, nkv, D, device="cuda", generator=g).to(dtype)
+    vc = torch.randn(B, cap, nkv, D, device="cuda", generator=g).to(dtype)
+    k1, v1 = kc.clone(), vc.clone()
+    want = SF.decode_rope_append(part.clone(), k1, v1, pos, nh, nkv, D, rope=rope)
+    got = SF.decode_rope_append(part, kc, vc, pos, nh, nkv, D, rope=rope)
+    assert got.shape == (B, nh, D) and torch.equal(got, want)
+    assert torch.equal(kc, k1) and torch.equal(vc, v1)
+
+
 def test_refused_shapes_raise():
     def ops(nh, nkv, D, dtype):
         q = torch.zeros(2, nh, D, device="cuda", dtype=dtype)

@@ -3,8 +3,8 @@
 The attention kernel is judged row by row as ``_numerics.flash_excess`` judges flash attention: its
 error against float64 of the same 16-bit inputs may be at most 2 x the error, in the same row, of
 the torch twin that places the kernel's rounding points (``decode_attention_multi_ref(emulate=
-True)``), plus one ulp of the type at the row's maximum. The append kernel is compared bit for bit
-with T calls of the single-token one. End to end, speculative tokens must equal the plain greedy
+True)``), plus one ulp of the type at the row's maximum. The append is compared bit for bit with T
+single-token calls and, as both run one kernel, with the ``rope_`` kernel. End to end, speculative tokens must equal the plain greedy
 ones unless the fp32 model itself cannot separate the two tokens at the first difference."""
 import math
 
@@ -127,7 +127,9 @@ def test_query_without_keys_returns_zeros():
 @pytest.mark.parametrize("dtype", DTYPES, ids=["bf16", "fp16"])
 def test_decode_rope_append_multi_bitwise(dtype, seq_first, nh, nkv, D, rot):
     """The bytes of T calls of ``decode_rope_append`` (q and both caches), from a [B, T, W] tensor
-    and from the model's sequence-first [T, B, W] as a transposed view."""
+    and from the model's sequence-first [T, B, W] as a transposed view. Both sides run one kernel,
+    so the transposed case is anchored independently as well: q / k of every token against the
+    ``rope_`` kernel at position pos[b] + t, v against the source rows."""
     B, T, cap = 4, 5, 40
     g = _gen(7)
     W = (nh + 2 * nkv) * D
@@ -149,6 +151,21 @@ def test_decode_rope_append_multi_bitwise(dtype, seq_first, nh, nkv, D, rot):
     got = SF.decode_rope_append_multi(qkv, kc, vc, pos, nh, nkv, D, rope=rope)
     assert got.shape == (B, T, nh, D) and torch.equal(got, want)
     assert torch.equal(kc, k1) and torch.equal(vc, v1)
+    if not seq_first:
+        return
+    want_qk = qkv[:, :, :(nh + nkv) * D].reshape(B, T, nh + nkv, D).clone()
+    if rot is not None:
+        for b in range(B):           # the rope_ kernel on a [cap] sequence holding token t's row at pos[b] + t
+            x = torch.zeros(cap, nh + nkv, D, device="cuda", dtype=dtype)
+            x[int(pos[b]):int(pos[b]) + T] = want_qk[b]
+            _ext.ext().rope_(x, cos, sin, rot, 1, cap, False)
+            want_qk[b] = x[int(pos[b]):int(pos[b]) + T]
+    want_v = qkv[:, :, (nh + nkv) * D:].reshape(B, T, nkv, D)
+    assert torch.equal(got, want_qk[:, :, :nh])
+    for b in range(B):
+        p = int(pos[b])
+        assert torch.equal(kc[b, p:p + T], want_qk[b, :, nh:])
+        assert torch.equal(vc[b, p:p + T], want_v[b])
 
 
 def test_refused_shapes_raise():
