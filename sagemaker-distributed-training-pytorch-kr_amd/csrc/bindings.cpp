@@ -726,14 +726,33 @@ std::vector<Tensor> gemm_tn_grouped(Tensor a, Tensor btab, int64_t n, Tensor til
 }
 
 // ------------------------------------------------------------------ weight gradient (MFMA)
+// The operand checks the wgrad bindings share, in the order every one of them makes them (the FP8
+// binding raises for a misplaced dequantisation factor between the two): an fp32 contiguous device
+// target, 2-D contiguous operands of a permitted type (dy one of dy_a / dy_b; x of x_type, or of
+// dy's type when x_type is Undefined), on the target's device when `same_device` (the single launch
+// never asked) ...
+static bool wgrad_operands_ok(const Tensor& mg, const Tensor& dy, const Tensor& x, at::ScalarType dy_a,
+                              at::ScalarType dy_b, at::ScalarType x_type, bool same_device) {
+  if (!mg.is_cuda() || mg.scalar_type() != at::kFloat || !mg.is_contiguous()) return false;
+  if (dy.dim() != 2 || x.dim() != 2 || !dy.is_contiguous() || !x.is_contiguous()) return false;
+  if ((dy.scalar_type() != dy_a && dy.scalar_type() != dy_b) ||
+      x.scalar_type() != (x_type == at::ScalarType::Undefined ? dy.scalar_type() : x_type))
+    return false;
+  return !same_device || (dy.get_device() == mg.get_device() && x.get_device() == mg.get_device());
+}
+// ... and dy [M, N], x [M, K], a target of N K elements, a shape the kernel takes.
+static bool wgrad_shape_ok(const Tensor& mg, const Tensor& dy, const Tensor& x,
+                           int (*supported)(int64_t, int64_t, int64_t)) {
+  const int64_t M = dy.size(0), N = dy.size(1), K = x.size(1);
+  return x.size(0) == M && mg.numel() == N * K && supported(M, N, K);
+}
+
 // main_grad[N, K] (fp32) += dy[M, N]^T . x[M, K]; returns false when the shape is unsupported.
 bool wgrad_mfma(Tensor main_grad, Tensor dy, Tensor x, int64_t max_splits) {
-  if (!main_grad.is_cuda() || main_grad.scalar_type() != at::kFloat || !main_grad.is_contiguous()) return false;
-  if (dy.dim() != 2 || x.dim() != 2 || !dy.is_contiguous() || !x.is_contiguous()) return false;
-  if ((dy.scalar_type() != at::kBFloat16 && dy.scalar_type() != at::kHalf) || x.scalar_type() != dy.scalar_type())
+  if (!wgrad_operands_ok(main_grad, dy, x, at::kBFloat16, at::kHalf, at::ScalarType::Undefined, false) ||
+      !wgrad_shape_ok(main_grad, dy, x, smdt_wgrad_supported))
     return false;
   const int64_t M = dy.size(0), N = dy.size(1), K = x.size(1);
-  if (x.size(0) != M || main_grad.numel() != N * K || !smdt_wgrad_supported(M, N, K)) return false;
   check(smdt_wgrad_accumulate_t(dcode(dy), dy.data_ptr(), x.data_ptr(), main_grad.data_ptr<float>(), M, N, K, (int)max_splits,
                               cur_stream()),
         "wgrad_mfma");
@@ -759,14 +778,10 @@ bool wgrad_grouped(std::vector<Tensor> main_grads, std::vector<Tensor> dys, std:
   std::vector<SmdtWgradProblem> probs(n);
   for (size_t i = 0; i < n; ++i) {
     const Tensor &mg = main_grads[i], &dy = dys[i], &x = xs[i];
-    if (!mg.is_cuda() || mg.scalar_type() != at::kFloat || !mg.is_contiguous()) return false;
-    if (dy.dim() != 2 || x.dim() != 2 || !dy.is_contiguous() || !x.is_contiguous()) return false;
-    if ((dy.scalar_type() != at::kBFloat16 && dy.scalar_type() != at::kHalf) || x.scalar_type() != dy.scalar_type() ||
-        dy.scalar_type() != dys[0].scalar_type())
+    if (!wgrad_operands_ok(mg, dy, x, at::kBFloat16, at::kHalf, at::ScalarType::Undefined, true) ||
+        dy.scalar_type() != dys[0].scalar_type() || !wgrad_shape_ok(mg, dy, x, smdt_wgrad_supported))
       return false;
-    if (dy.get_device() != mg.get_device() || x.get_device() != mg.get_device()) return false;
     const int64_t M = dy.size(0), N = dy.size(1), K = x.size(1);
-    if (x.size(0) != M || mg.numel() != N * K || !smdt_wgrad_supported(M, N, K)) return false;
     float* bg = nullptr;
     if (!biases.empty() && biases[i].numel() > 0) {
       const Tensor& bt = biases[i];
@@ -807,18 +822,15 @@ bool wgrad_fp8_grouped(std::vector<Tensor> main_grads, std::vector<Tensor> dys, 
   std::vector<SmdtWgradFp8Problem> probs(n);
   for (size_t i = 0; i < n; ++i) {
     const Tensor &mg = main_grads[i], &dy = dys[i], &x = xs[i], &idy = inv_dys[i], &ix = inv_xs[i];
-    if (!mg.is_cuda() || mg.scalar_type() != at::kFloat || !mg.is_contiguous()) return false;
-    if (dy.dim() != 2 || x.dim() != 2 || !dy.is_contiguous() || !x.is_contiguous()) return false;
-    if ((dy.scalar_type() != at::kFloat8_e5m2 && dy.scalar_type() != at::kFloat8_e4m3fn) ||
-        x.scalar_type() != at::kFloat8_e4m3fn || dy.scalar_type() != dys[0].scalar_type())
+    if (!wgrad_operands_ok(mg, dy, x, at::kFloat8_e5m2, at::kFloat8_e4m3fn, at::kFloat8_e4m3fn, true) ||
+        dy.scalar_type() != dys[0].scalar_type())
       return false;
-    if (dy.get_device() != mg.get_device() || x.get_device() != mg.get_device()) return false;
     for (const Tensor* t : {&idy, &ix})
       TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->numel() == 1 &&
                       t->get_device() == mg.get_device(),
                   "wgrad_fp8_grouped: a dequantisation factor must be one fp32 value on the target's device");
+    if (!wgrad_shape_ok(mg, dy, x, smdt_wgrad_fp8_supported)) return false;
     const int64_t M = dy.size(0), N = dy.size(1), K = x.size(1);
-    if (x.size(0) != M || mg.numel() != N * K || !smdt_wgrad_fp8_supported(M, N, K)) return false;
     for (size_t j = 0; j < i; ++j) {    // overlapping targets would race
       const char *a0 = (const char*)mg.data_ptr(), *b0 = (const char*)main_grads[j].data_ptr();
       if (a0 < b0 + main_grads[j].numel() * 4 && b0 < a0 + mg.numel() * 4) return false;

@@ -267,6 +267,25 @@ __device__ __forceinline__ void colsum_block(const float* __restrict__ part, int
   }
 }
 
+// ---------------------------------------------------------------------------
+// Helpers of the kernels that stream operands global -> LDS by DMA (global_load_lds /
+// buffer_load ... lds) and run persistent or XCD-ordered grids.
+using lds_void = __attribute__((address_space(3))) void;
+
+// s_waitcnt with vmcnt = n and the other counters left alone (gfx9 encoding).
+template <int n>
+__device__ __forceinline__ void wait_vm() {
+  static_assert(n >= 0 && n < 64, "vmcnt range");
+  __builtin_amdgcn_s_waitcnt((n & 15) | ((n >> 4) << 14) | (7 << 4) | (15 << 8));
+}
+
+// XCD-aware bijective remap: hardware dispatches block b to XCD b % 8 (blocks b and b + 8 share
+// an XCD); give each XCD a contiguous range of work items.
+__device__ __forceinline__ int xcd_remap(int orig, int nblocks) {
+  const int xcd = orig & 7, q = nblocks >> 3, rem = nblocks & 7;
+  return (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (orig >> 3);
+}
+
 // Number of blocks for a grid-stride memory-bound kernel (Guideline 11:
 // cap at ~8 blocks per CU over 256 CUs).
 inline int stream_grid(int64_t work_items, int per_block) {

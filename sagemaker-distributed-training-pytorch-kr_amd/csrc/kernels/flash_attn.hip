@@ -247,14 +247,6 @@ __device__ __forceinline__ f2s pexp2(float x0, float x1, float c, float b0, floa
   return {fexp2(fmaf(x0, c, -b0)), fexp2(fmaf(x1, c, -b1))};
 }
 
-// s_waitcnt with vmcnt = n and the other counters left alone (gfx9 encoding).
-template <int n>
-__device__ __forceinline__ void wait_vm() {
-  static_assert(n >= 0 && n < 64, "vmcnt range");
-  __builtin_amdgcn_s_waitcnt((n & 15) | ((n >> 4) << 14) | (7 << 4) | (15 << 8));
-}
-using lds_void = __attribute__((address_space(3))) void;
-
 // LDS-DMA of `bytes` per lane from a wave-uniform global base + a 32-bit per-lane byte offset,
 // as buffer_load ... lds: the base lives in an SGPR buffer resource, the lane part in ONE VGPR
 // (global_load_lds needs a 64-bit VGPR address per piece, kept live across the loop).

@@ -44,7 +44,6 @@ constexpr int kSc = kT * 4;              // 512 B: one operand's scale dwords of
 constexpr int kSlot = 2 * kOp + 2 * kSc; // [A | B | sa | sb]
 constexpr int kGl = kOp / 1024 / 4;      // 1-KB DMA wave-instructions per wave per operand (4)
 
-using lds_void = __attribute__((address_space(3))) void;
 using i32x4 = __attribute__((ext_vector_type(4))) int;
 using i32x8 = __attribute__((ext_vector_type(8))) int;
 using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
@@ -62,16 +61,6 @@ struct Args {
   int tiles;
   int nt;         // K / 128
 };
-
-// s_waitcnt vmcnt(0), other counters untouched (gfx9 encoding)
-__device__ __forceinline__ void wait_vm0() { __builtin_amdgcn_s_waitcnt((7 << 4) | (15 << 8)); }
-
-// XCD-aware bijective remap: blocks b and b + 8 share an XCD (round-robin dispatch); give each
-// XCD a contiguous range.
-__device__ __forceinline__ int xcd_remap(int orig, int nblocks) {
-  const int xcd = orig & 7, q = nblocks >> 3, rem = nblocks & 7;
-  return (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (orig >> 3);
-}
 
 template <class E>
 __device__ __forceinline__ u32x2 pack4(float a, float b, float c, float d) {
@@ -159,7 +148,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_mx_kernel(const Args g) {
     for (int kt = 0; kt < g.nt; ++kt) {
       // stage kt has landed (nothing else of this wave is in flight), in every wave after the
       // barrier; every wave has also finished stage kt - 1, whose slot the next DMA overwrites
-      wait_vm0();
+      wait_vm<0>();
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);

@@ -68,7 +68,6 @@ constexpr int kEpiB = 32 * 128;          // per-wave epilogue staging: 2 x 16 ro
 
 enum { EPI_NONE = 0, EPI_BIAS = 1, EPI_BIAS_GELU = 2, EPI_DGELU = 3 };
 
-using lds_void = __attribute__((address_space(3))) void;
 using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
@@ -84,12 +83,7 @@ __device__ __forceinline__ f32x4 mma(f16x8 a, f16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 }
 
-// s_waitcnt vmcnt(n), other counters untouched (gfx9 encoding; n <= 63)
-template <int n>
-__device__ __forceinline__ void wait_vm() {
-  static_assert(n >= 0 && n < 64, "vmcnt range");
-  __builtin_amdgcn_s_waitcnt((n & 15) | ((n >> 4) << 14) | (7 << 4) | (15 << 8));
-}
+// one of three counted waits (common.h wait_vm), chosen at run time
 template <int a, int b, int c>
 __device__ __forceinline__ void wait_vm_sel(int sel) {
   if (sel == 0) wait_vm<a>();
@@ -110,13 +104,6 @@ __device__ __forceinline__ void unpack4(u32x2 w, float (&o)[4]) {
   v4 v = __builtin_bit_cast(v4, w);
 #pragma unroll
   for (int i = 0; i < 4; ++i) o[i] = (float)v[i];
-}
-
-// XCD-aware bijective remap: blocks b and b + 8 share an XCD (round-robin dispatch); give each
-// XCD a contiguous range.
-__device__ __forceinline__ int xcd_remap(int orig, int nblocks) {
-  const int xcd = orig & 7, q = nblocks >> 3, rem = nblocks & 7;
-  return (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (orig >> 3);
 }
 
 struct Args {

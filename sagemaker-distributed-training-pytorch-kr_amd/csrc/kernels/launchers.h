@@ -274,8 +274,6 @@ hipError_t smdt_moe_route(int dtype, const void* logits, int64_t T, int64_t E, f
 int smdt_wgrad_supported(int64_t M, int64_t N, int64_t K);
 hipError_t smdt_wgrad_accumulate_t(int dtype, const void* dy, const void* x, float* main_grad, int64_t M,
                                    int64_t N, int64_t K, int max_splits, hipStream_t st);
-hipError_t smdt_wgrad_accumulate(const void* dy, const void* x, float* main_grad, int64_t M, int64_t N,
-                                 int64_t K, int max_splits, hipStream_t st);
 struct SmdtWgradProblem {
   const void* dy;      // [M, N] bf16
   const void* x;       // [M, K] bf16
@@ -289,11 +287,9 @@ struct SmdtWgradProblem {
   const int* mrange;
   int expert;
 };
-// Many independent wgrad accumulations in one launch per 32 (no split-K, no atomics). The
-// main_grad targets of one call must not overlap.
-hipError_t smdt_wgrad_grouped(const SmdtWgradProblem* probs, int n, hipStream_t st);
-hipError_t smdt_wgrad_grouped_t(int dtype, const SmdtWgradProblem* probs, int n, hipStream_t st);
-// the same with the tail split sized for `cus` concurrently usable CUs (0: 256, the whole chip)
+// Many independent wgrad accumulations in one launch per 32 (no split-K; only the tiles past the
+// last full round add with atomics). The main_grad targets of one call must not overlap. The tail
+// split is sized for `cus` concurrently usable CUs (0: 256, the whole chip).
 hipError_t smdt_wgrad_grouped_cus(int dtype, const SmdtWgradProblem* probs, int n, int cus, hipStream_t st);
 
 // wgrad_fp8.hip: main_grad[N, K] (fp32) (+)= (*inv_dy * *inv_x) * dy[M, N]^T . x[M, K] on FP8 bytes

@@ -731,3 +731,47 @@ def assert_flash_close(got, emu, ref, dtype, names=("o", "lse", "dq", "dk", "dv"
         if not ratio <= 1.0:
             fails.append(f"{n}: error {ek:.4g} vs emulation {ee:.4g}, {ratio:.3g}x the bound")
     assert not fails, f"{what}: " + "; ".join(fails)
+
+
+# ---------------------------------------------------------------------- weight gradient, exact data
+#
+# Operands on which every sum of the weight-gradient kernels is exact, so a kernel is compared bit
+# for bit whatever its summation order (split-K and tail pieces add with atomics).
+
+def wgrad_exact_case(g, M, N, K, dy_dtype, x_dtype=None):
+    """dY [M, N] and x [M, K] from {0, +-0.5, +-1, +-2} (exact in bf16, fp16, E5M2 and E4M3), a
+    target [N, K] and a bias target [N] of small integers."""
+    vals = torch.tensor([0.0, 0.5, -0.5, 1.0, -1.0, 2.0, -2.0])
+    a = vals[torch.randint(0, 7, (M, N), generator=g)].to(dy_dtype)
+    b = vals[torch.randint(0, 7, (M, K), generator=g)].to(x_dtype or dy_dtype)
+    mg = torch.randint(-8, 9, (N, K), generator=g).float()
+    bg = torch.randint(-8, 9, (N,), generator=g).float()
+    return a, b, mg, bg
+
+
+def wgrad_exact_twin(mg, a, b, overwrite, inv_dy=None, inv_x=None):
+    """The twin on the CPU, with the check that makes it an exact reference: its fp32 result equals
+    the float64 one, so no sum of these inputs rounds (every product is a multiple of 1/4 no larger
+    than 4, every partial sum a multiple of 1/4 below 2^22 for M <= 2^18, the two dequantisation
+    factors of the FP8 form are powers of two and the target holds small integers: any order,
+    atomics included, is exact). ``inv_dy`` / ``inv_x`` (one-element tensors) select the FP8 twin."""
+    assert a.shape[0] <= 2 ** 18
+    if inv_dy is None:
+        prod = a.float().t().matmul(b.float())
+        out = prod if overwrite else mg + prod
+        r64 = a.double().t() @ b.double()
+    else:
+        from smdt_amd.ops import functional as SF
+        out = SF.fp8_wgrad_ref(mg.clone(), a, b, inv_dy, inv_x, overwrite)
+        r64 = (a.double() * inv_dy.double()).t() @ (b.double() * inv_x.double())
+    if not overwrite:
+        r64 = r64 + mg.double()
+    assert torch.equal(out.double(), r64)
+    return out
+
+
+def wgrad_exact_bias_twin(bg, a):
+    """start + column sums of dY, exact for the same reason."""
+    out = bg + a.float().sum(0)
+    assert torch.equal(out.double(), bg.double() + a.double().sum(0))
+    return out

@@ -6,6 +6,8 @@ import warnings
 import pytest
 import torch
 
+from _numerics import wgrad_exact_case, wgrad_exact_twin
+
 pytestmark = pytest.mark.gpu
 
 S = 64                                   # the kernel's stage: rows of m per LDS stage
@@ -19,25 +21,12 @@ def _ext():
 
 def _exact_case(g, M, N, K, fmt):
     """Operands from {0, +-0.5, +-1, +-2} (exact in E5M2 and E4M3), a target of small integers."""
-    vals = torch.tensor([0.0, 0.5, -0.5, 1.0, -1.0, 2.0, -2.0])
-    a = vals[torch.randint(0, 7, (M, N), generator=g)].to(FMT[fmt])
-    b = vals[torch.randint(0, 7, (M, K), generator=g)].to(FMT["e4m3"])
-    mg = torch.randint(-8, 9, (N, K), generator=g).float()
-    return a, b, mg
+    return wgrad_exact_case(g, M, N, K, FMT[fmt], FMT["e4m3"])[:3]
 
 
 def _twin(mg, a, b, inv_dy, inv_x, overwrite):
-    """The twin on the CPU, with the check that makes it an exact reference: its fp32 result
-    equals the float64 one, so no sum of these inputs rounds (every product is a multiple of 1/4
-    no larger than 4, every partial sum a multiple of 1/4 below 2^22 for M <= 2^18, the two factors
-    are powers of two and the target holds small integers: any order, atomics included, is exact)."""
-    from smdt_amd.ops import functional as SF
-    out = SF.fp8_wgrad_ref(mg.clone(), a, b, inv_dy, inv_x, overwrite)
-    r64 = (a.double() * inv_dy.double()).t() @ (b.double() * inv_x.double())
-    if not overwrite:
-        r64 = r64 + mg.double()
-    assert torch.equal(out.double(), r64)
-    return out
+    """The twin on the CPU (SF.fp8_wgrad_ref), checked against float64: see wgrad_exact_twin."""
+    return wgrad_exact_twin(mg, a, b, overwrite, inv_dy, inv_x)
 
 
 INV_DY, INV_X = 0.5, 4.0
