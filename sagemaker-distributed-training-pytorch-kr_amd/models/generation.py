@@ -35,6 +35,7 @@ import torch
 
 from ..ops import functional as SF
 from ..parallel import state as ps
+from ..parallel import decode_weights as dw
 from ..parallel import tensor_parallel as tp
 from . import transformer as _T
 from .transformer import TransformerConfig
@@ -149,7 +150,7 @@ def _refuse(model, input_ids, attention_mask, max_new_tokens, cache, kv_cache_fo
 
 
 def _decode_weights(model, weight_format):
-    """The ``tp.DecodeWeights`` of a ``generate(weight_format=...)`` call (None for None): every
+    """The ``dw.DecodeWeights`` of a ``generate(weight_format=...)`` call (None for None): every
     refusal raises here, the quantised copies are made (or found in the cache) and the kernel's
     workspace and the dequantisation scratch are allocated, all before the first decode step."""
     if weight_format is None:
@@ -170,7 +171,7 @@ def _decode_weights(model, weight_format):
                                    "training linear); weight formats are for models with plain 16-bit linears")
             linears.append((name, mod.weight, False))
     linears.append(("the LM head", head, True))
-    state = tp.DecodeWeights(weight_format, head_weight=head)
+    state = dw.DecodeWeights(weight_format, head_weight=head)
     state.prepare(linears)
     return state
 
@@ -263,7 +264,7 @@ def generate(model, input_ids, attention_mask=None, max_new_tokens: int = 32, do
     was_training = model.training
     model.eval()
     try:
-        with tp.decode_weights(state):
+        with dw.decode_weights(state):
             return _generate(model, input_ids, attention_mask, int(max_new_tokens), do_sample, float(temperature),
                              int(top_k), float(top_p), eos_token_id, int(pad_token_id), generator, use_graph, cache,
                              kv_cache_format)
@@ -409,7 +410,7 @@ class SpeculativeState:
         self.finished = torch.zeros(B, dtype=torch.bool, device=dev)
         self.counters = torch.zeros(3, dtype=torch.int64, device=dev)
         # prefill of both models; the target's logits give the first token x0
-        with tp.decode_weights(dstate):
+        with dw.decode_weights(dstate):
             logits = model.forward_prefill(input_ids, self.plen, self.cache)
         self.cache.lens.copy_(self.plen)
         draft.forward_prefill(input_ids, self.plen, self.dcache)
@@ -438,7 +439,7 @@ class SpeculativeState:
                 drafts.append(tok)
         d = torch.stack(drafts, dim=1)                                           # [B, k]
         cache.advance(k + 1)
-        with tp.decode_weights(self.dstate):
+        with dw.decode_weights(self.dstate):
             logits = self.model.forward_extend(torch.cat([x0.unsqueeze(1), d], dim=1), cache)
         p = logits[..., :V].argmax(dim=-1)                                       # [B, k + 1]
         active = ~self.finished & (self.remaining > 0)

@@ -18,6 +18,7 @@ import torch.nn as nn
 
 from ..ops import functional as SF
 from ..parallel import state as ps
+from ..parallel import lm_head
 from ..parallel import tensor_parallel as tp
 from .transformer import ParallelTransformer, TransformerConfig
 
@@ -221,11 +222,11 @@ class GPTModel(nn.Module):
         st = ps.get_state()
         if labels is not None:
             w = self.output_weight if self.output_weight is not None else self.embedding.weight
-            if tp.lm_head_ce_ok(out, w, st.tp):
+            if lm_head.lm_head_ce_ok(out, w, st.tp):
                 # LM-head GEMM + CE as one op: no backward pass over the [tokens, vocab] logits
                 vs = int(self.loss_vocab_size or 0)
                 vvalid = vs if 0 < vs < w.shape[0] else 0
-                loss = tp.LMHeadCrossEntropy.apply(out, w, labels.transpose(0, 1), -100, vvalid)
+                loss = lm_head.LMHeadCrossEntropy.apply(out, w, labels.transpose(0, 1), -100, vvalid)
                 return loss.transpose(0, 1).contiguous()             # [b, s]
             if self.parallel_output and tp.vp_lm_head_ce_ok(out, w, st.tp):
                 # vocab-parallel LM head + CE as one op: one pass over this rank's logit slice

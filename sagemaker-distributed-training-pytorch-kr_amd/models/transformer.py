@@ -27,6 +27,9 @@ import torch.nn.functional as F
 from ..ops import _ext
 from ..ops import functional as SF
 from ..parallel import state as ps
+from ..parallel import decode_weights as dw
+from ..parallel import fp8_linear
+from ..parallel import moe_experts
 from ..parallel import tensor_parallel as tp
 from ..parallel.random import checkpoint as rng_checkpoint, get_rng
 
@@ -81,7 +84,7 @@ class TransformerConfig:
     recompute_num_layers: Optional[int] = None
     distribute_saved_activations: bool = False   # full recompute: saved layer inputs split across TP
     # FP8 linears with delayed scaling (--fp8-e4m3 / --fp8-hybrid): QKV, proj, fc1, fc2 of every
-    # layer run their forward and input-gradient GEMMs on FP8 operands (tp.FP8State)
+    # layer run their forward and input-gradient GEMMs on FP8 operands (fp8_linear.FP8State)
     fp8: Optional[str] = None                    # None | "e4m3" | "hybrid" (dY in E5M2)
     fp8_wgrad: bool = False                      # --fp8-wgrad: the weight-gradient GEMM on FP8 operands too
     fp8_margin: int = 0
@@ -466,7 +469,7 @@ class ParallelAttention(nn.Module):
         16-bit linear) and a shape the kernels take as it is."""
         lin = self.qkv
         if (_PACK["idx"] is not None or self.rope is not None or not self.cfg.use_flash_attn
-                or ps.get_state().cp != 1 or lin._fp8 is not None or tp.decode_quantised() or lin.sequence_parallel
+                or ps.get_state().cp != 1 or lin._fp8 is not None or dw.decode_quantised() or lin.sequence_parallel
                 or lin.gather_output
                 or lin.skip_bias_add or not torch.is_grad_enabled() or x.dim() != 3
                 or lin.bias is None or lin.weight.dtype != x.dtype or lin.bias.dtype != x.dtype):
@@ -656,7 +659,7 @@ class ParallelMLP(nn.Module):
         act = self.cfg.activation
         # FP8 linears take the unfused route: FP8 GEMM, then the bias-activation kernel
         # (nor under a quantised generation weight format: the fused forms would read the 16-bit weights)
-        fused = act == "gelu" and self.cfg.bias_gelu_fusion and not self.cfg.fp8 and not tp.decode_quantised()
+        fused = act == "gelu" and self.cfg.bias_gelu_fusion and not self.cfg.fp8 and not dw.decode_quantised()
         if fused:
             # the fused forms read fc1 / fc2 weights without calling fc1(x) / fc2(x)
             _gather_wait(self.fc1, x)
@@ -762,7 +765,7 @@ class SwitchMLP(nn.Module):
         return kern
 
     def _forward_grouped(self, x):
-        """--moe-grouped-gemm: device routing + grouped expert GEMMs (``tp.GroupedSwitchExperts``):
+        """--moe-grouped-gemm: device routing + grouped expert GEMMs (``moe_experts.GroupedSwitchExperts``):
         no host sync and no launch shape that depends on the routing."""
         s, b, h = x.shape
         flat = x.reshape(s * b, h)
@@ -781,7 +784,7 @@ class SwitchMLP(nn.Module):
             if self._tabs is None or self._tabs[0] != key:      # built once per layer
                 self._tabs = (key, (SF.moe_pointer_tables(w1, b1), SF.moe_pointer_tables(w2, b2)))
             tabs = self._tabs[1]
-        out = tp.GroupedSwitchExperts.apply(flat, top_p, route, tabs, len(ex), *w1, *b1, *w2, *b2)
+        out = moe_experts.GroupedSwitchExperts.apply(flat, top_p, route, tabs, len(ex), *w1, *b1, *w2, *b2)
         return out.view(s, b, h), None
 
     def forward(self, x):
@@ -922,12 +925,12 @@ class ParallelTransformer(nn.Module):
             # dict of a 16-bit model keeps its keys
             lins = [m for l in self.layers for m in (l.attention.qkv, l.attention.proj, l.mlp.fc1, l.mlp.fc2)]
             if cfg.fp8_recipe == "mxfp8":      # stateless: no module, no buffer, nothing in the state dict
-                tp.attach_mxfp8(lins, tp.MXFP8Recipe(cfg.fp8))
+                fp8_linear.attach_mxfp8(lins, fp8_linear.MXFP8Recipe(cfg.fp8))
                 return
-            self.fp8_state = tp.FP8State(len(lins), cfg.fp8, cfg.fp8_margin, cfg.fp8_interval,
-                                         cfg.fp8_amax_history_len, cfg.fp8_amax_compute_algo, device,
-                                         fp8_wgrad=cfg.fp8_wgrad)
-            tp.attach_fp8(lins, self.fp8_state)
+            self.fp8_state = fp8_linear.FP8State(len(lins), cfg.fp8, cfg.fp8_margin, cfg.fp8_interval,
+                                                 cfg.fp8_amax_history_len, cfg.fp8_amax_compute_algo, device,
+                                                 fp8_wgrad=cfg.fp8_wgrad)
+            fp8_linear.attach_fp8(lins, self.fp8_state)
 
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
                               error_msgs):

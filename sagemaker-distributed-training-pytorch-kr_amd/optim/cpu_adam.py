@@ -18,7 +18,8 @@ from typing import Optional
 import torch
 import torch.distributed as dist
 
-from ..parallel import tensor_parallel as _tp
+from ..parallel import dense as _dense
+from ..parallel import fp8_linear as _fp8
 from .optimizer import MixedPrecisionAdam
 
 
@@ -73,7 +74,7 @@ class CPUOffloadAdam(MixedPrecisionAdam):
         if lr is not None:
             self.lr = lr
         self.param_groups[0]["lr"] = self.lr
-        _tp.params_changed()
+        _dense.params_changed()
         ddp = self.ddp
         ddp.wait_param_gather()
         g = ddp.grad_data
@@ -130,7 +131,7 @@ class CPUOffloadAdam(MixedPrecisionAdam):
                                       non_blocking=cuda)
         if self.zero:
             ddp.all_gather_params()
-        _tp.fp8_after_optimizer_step(self.ddp.module)
+        _fp8.fp8_after_optimizer_step(self.ddp.module)
         return self.grad_norm
 
     def state_dict(self):

@@ -32,7 +32,8 @@ from ..comm import stats as _cs
 from ..ops import _ext
 from ..parallel import state as ps
 from ..parallel.distributed import DistributedDataParallel
-from ..parallel import tensor_parallel as _tp
+from ..parallel import dense as _dense
+from ..parallel import fp8_linear as _fp8
 
 
 class DynamicLossScaler:
@@ -211,7 +212,7 @@ class MixedPrecisionAdam:
             self._step_t += 1                            # device step count: replays advance it
             self._hyp[1:2].copy_(1.0 - torch.pow(self.beta1, self._step_t))
             self._hyp[2:3].copy_(1.0 - torch.pow(self.beta2, self._step_t))
-        _tp.params_changed()
+        _dense.params_changed()
         ddp = self.ddp
         if hasattr(ddp, "wait_param_gather"):
             ddp.wait_param_gather()          # (also the previous step's overlapped updates)
@@ -258,7 +259,7 @@ class MixedPrecisionAdam:
             self._step_overlapped(g, mul, t)
             if self.scaler is not None:
                 self.scaler.update(self.found_inf)
-            _tp.fp8_after_optimizer_step(self.ddp.module)
+            _fp8.fp8_after_optimizer_step(self.ddp.module)
             return self.grad_norm
         for (s, e, key), mo in zip(self.pieces, self.master_off):
             if e <= s:
@@ -268,7 +269,7 @@ class MixedPrecisionAdam:
             self.scaler.update(self.found_inf)
         if self.zero:
             ddp.all_gather_params()
-        _tp.fp8_after_optimizer_step(self.ddp.module)
+        _fp8.fp8_after_optimizer_step(self.ddp.module)
         return self.grad_norm
 
     _overlappable = True     # the per-bucket update may run on the overlapped side stream
@@ -348,7 +349,7 @@ class MixedPrecisionAdam:
     def repair_params(self):
         """Model-dtype parameters <- fp32 masters for this rank's pieces, then (ZeRO) re-gather the
         full buffer: undoes NaN-filled parameter gathers after a collective timed out."""
-        _tp.params_changed()
+        _dense.params_changed()
         ddp = self.ddp
         if hasattr(ddp, "wait_param_gather"):
             ddp.wait_param_gather()
@@ -362,7 +363,7 @@ class MixedPrecisionAdam:
     @torch.no_grad()
     def reload_model_params(self):
         """Refresh the fp32 masters from the model buffer (after loading weights only)."""
-        _tp.params_changed()
+        _dense.params_changed()
         self.ddp.wait_param_gather()
         for (s, e, _), mo in zip(self.pieces, self.master_off):
             self.master[mo:mo + (e - s)].copy_(self.ddp.param_data[s:e].float())
@@ -384,7 +385,7 @@ class MixedPrecisionAdam:
 
     def load_state_dict(self, d):
         self.ddp.wait_param_gather()
-        _tp.params_changed()
+        _dense.params_changed()
         self.step_count = int(d["step"])
         if self.capturable:
             self._step_t.fill_(self.step_count)

@@ -431,7 +431,7 @@ class DistributedDataParallel(nn.Module):
                 fr.discard(id(p))
                 v.zero_()
             elif id(p) in self._claimed:
-                from .tensor_parallel import flush_deferred_wgrad
+                from .dense import flush_deferred_wgrad
                 flush_deferred_wgrad()
                 self._claimed.clear()          # everything queued has been issued
         return v
@@ -597,7 +597,7 @@ class DistributedDataParallel(nn.Module):
         only after all of ITS gradients were accumulated."""
         enabled = bool(enabled)
         if enabled and not self.sync_enabled:
-            from .tensor_parallel import DEFERRED_WGRAD, flush_deferred_wgrad
+            from .dense import DEFERRED_WGRAD, flush_deferred_wgrad
             if not DEFERRED_WGRAD.hold:   # (a held accumulation window drains in its last pass)
                 flush_deferred_wgrad()
             self._reset_pending()
@@ -613,7 +613,7 @@ class DistributedDataParallel(nn.Module):
             self.set_sync_enabled(prev)
 
     def start_grad_sync(self):
-        from .tensor_parallel import flush_deferred_wgrad
+        from .dense import flush_deferred_wgrad
         flush_deferred_wgrad()          # queued weight-gradient GEMMs mark their params ready
         for b in self.buckets:
             if not b.launched:
@@ -625,7 +625,7 @@ class DistributedDataParallel(nn.Module):
         check_pending_adds("finish_grad_sync")   # a deferred RS summand no consumer added
         self.wait_param_gather()  # params a forward never touched
         if self.zero_stage >= 2:
-            from .tensor_parallel import flush_deferred_wgrad
+            from .dense import flush_deferred_wgrad
             flush_deferred_wgrad()
             for b in self.buckets:
                 if b.index in self._staging:

@@ -522,7 +522,7 @@ def validate_args(args, defaults=None):
     if args.ffn_hidden_size is None:
         args.ffn_hidden_size = 4 * args.hidden_size if not args.swiglu else int(8 * args.hidden_size / 3)
     if getattr(args, "moe_grouped_gemm", False):
-        # the grouped Switch path (tp.GroupedSwitchExperts): what it cannot run is refused here
+        # the grouped Switch path (moe_experts.GroupedSwitchExperts): what it cannot run is refused here
         if not args.num_experts:
             raise ValueError("--moe-grouped-gemm needs --num-experts")
         if requested_tp > 1:

@@ -61,7 +61,8 @@ def forward_backward_no_pipelining(forward_step_func: Callable, data_iterator, m
     stage time has the schedule's W grouping instead of the opportunistic per-collective flushes
     of a plain backward.
     """
-    from ..parallel.tensor_parallel import DEFERRED_WGRAD, W_FILL, accumulation_window_ok, forward_fill
+    from ..parallel.dense import DEFERRED_WGRAD
+    from ..parallel.tensor_parallel import W_FILL, accumulation_window_ok, forward_fill
     models = model if isinstance(model, list) else [model]
     m = models[0]
     gate = _SyncGate(models)
@@ -315,7 +316,8 @@ def forward_backward_pipelining_without_interleaving(forward_step_func: Callable
                                                      forward_only: bool = False, grad_scale=None, schedule=None, **_):
     """1F1B, optionally with the split (zero-bubble) backward of ``set_pipeline_schedule``.
     ``tensor_shape`` is the [s(/tp), b, h] activation exchanged between stages."""
-    from ..parallel.tensor_parallel import DEFERRED_WGRAD, W_FILL, forward_fill
+    from ..parallel.dense import DEFERRED_WGRAD
+    from ..parallel.tensor_parallel import W_FILL, forward_fill
     models = model if isinstance(model, list) else [model]
     m = models[0]
     _enter_schedule(m)

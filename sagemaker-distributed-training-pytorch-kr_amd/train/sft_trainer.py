@@ -364,7 +364,7 @@ class Trainer:
         finally:
             # a run stopped inside an accumulation window must not leave held weight gradients
             # (and their dY / X) queued, or the queue in hold mode, for the next user
-            from ..parallel.tensor_parallel import reset_wgrad_window
+            from ..parallel.dense import reset_wgrad_window
             reset_wgrad_window()
         total_loss += tr_loss
         if self.world > 1:

@@ -39,6 +39,7 @@ from ..models.gpt import allreduce_word_embedding_grads, gpt_flops_per_token
 from ..optim.lr_scheduler import OptimizerParamScheduler
 from ..optim.optimizer import ConstantLossScaler, DynamicLossScaler, MixedPrecisionAdam, MixedPrecisionSGD
 from ..parallel import state as ps
+from ..parallel import dense
 from ..parallel import tensor_parallel as tp
 from ..parallel.distributed import DistributedDataParallel
 from ..parallel.random import model_parallel_seed
@@ -142,7 +143,7 @@ def get_model(model_provider_func, args):
 def setup_model_and_optimizer(model_provider_func, args):
     # --no-gradient-accumulation-fusion: weight gradients are computed, then added to main_grad
     # (instead of the MFMA wgrad kernels accumulating straight into the fp32 buffer)
-    tp._FUSED_WGRAD = bool(getattr(args, "gradient_accumulation_fusion", True)) and tp._FUSED_WGRAD
+    dense._FUSED_WGRAD = bool(getattr(args, "gradient_accumulation_fusion", True)) and dense._FUSED_WGRAD
     ddp = get_model(model_provider_func, args)
     scaler = None
     if args.fp16:

@@ -229,7 +229,7 @@ class ZeroEngine:
         whole accumulation window (the GA micro-batches fused into one batch, each weighted 1/GA):
         no 1/GA scaling, and this backward is the window's synchronising pass."""
         if window:
-            from ..parallel.tensor_parallel import DEFERRED_WGRAD
+            from ..parallel.dense import DEFERRED_WGRAD
             DEFERRED_WGRAD.hold = False
             self.micro_steps = (self.micro_steps // self.ga) * self.ga + self.ga - 1
             if self.optimizer.scaler is not None:
@@ -242,8 +242,8 @@ class ZeroEngine:
         boundary = self.is_gradient_accumulation_boundary()
         if self._hold_wgrad():
             # the window's weight-gradient GEMMs meet in the deferred queue and run once over all
-            # of its tokens in the boundary pass (parallel/tensor_parallel.DeferredWgrad.hold)
-            from ..parallel.tensor_parallel import DEFERRED_WGRAD
+            # of its tokens in the boundary pass (parallel/dense.DeferredWgrad.hold)
+            from ..parallel.dense import DEFERRED_WGRAD
             DEFERRED_WGRAD.hold = not boundary
         ctx = nullcontext() if boundary else self.ddp.no_sync()
         with ctx:

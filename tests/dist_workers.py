@@ -325,7 +325,7 @@ def zero_sft_worker(rank, world, stage, ga, steps, offload=False, offload_param=
             if stage == 3 and with_mem and k == steps * ga * world:     # before the last micro-batch
                 # stand-in dgrad W^T entries (the cache only fills on GPU): a bucket freed by
                 # the partitioner must drop its parameters' entries
-                from smdt_amd.parallel import tensor_parallel as _tpm
+                from smdt_amd.parallel import dense as _tpm
                 for p in m.parameters():
                     _tpm._WT_CACHE[id(p)] = (None, torch.empty(1))
             loss, _ = m(ids, labels=lab)
@@ -334,7 +334,7 @@ def zero_sft_worker(rank, world, stage, ga, steps, offload=False, offload_param=
     eng.wait_for_params()
     wt_left = None
     if stage == 3 and with_mem:
-        from smdt_amd.parallel import tensor_parallel as _tpm
+        from smdt_amd.parallel import dense as _tpm
         part = eng.partitioner
         wt_left = sum(1 for b in eng.ddp.buckets if not part.persistent[b.index]
                       for p in b.params if id(p) in _tpm._WT_CACHE)
@@ -701,6 +701,7 @@ def tp_overlap_order_worker(rank, world):
     import torch.distributed as dist
     from smdt_amd.comm import init_distributed
     from smdt_amd.parallel import state as ps
+    from smdt_amd.parallel import dense
     from smdt_amd.parallel import tensor_parallel as T
     init_distributed("gloo")
     ps.initialize_model_parallel(world, 1)
@@ -723,7 +724,7 @@ def tp_overlap_order_worker(rank, world):
     def wgrad(weight, g2, t2):
         events.append("wgrad")
         return real_wgrad(weight, g2, t2)
-    T._exchange, T._wgrad = exchange, wgrad
+    T._exchange, T._wgrad, dense._wgrad = exchange, wgrad, wgrad     # _wgrad: each module that calls it
     g = torch.Generator().manual_seed(5)
     S, B, H, O = 8, 2, 16, 32
     xs = torch.randn(S, B, H, generator=g, dtype=torch.float64)

@@ -169,10 +169,11 @@ def _biases(model):
 def _step(model, ddp, toks, monkeypatch, producer, zero=True):
     """One forward + backward; returns (qkv db, fc1 db, {bias numel: dY}, {bias numel: bias pushed
     with the wgrad}) with dY the 16-bit output gradients the wgrad queue received."""
+    from smdt_amd.parallel import dense
     from smdt_amd.parallel import tensor_parallel as tp
     monkeypatch.setattr(tp, "_BIAS_FROM_PRODUCER", producer)
     # FusedGeLUMLP is taken only where its GEMMs have a tile per CU; let this 8-tile layer take it
-    monkeypatch.setattr(tp, "_NUM_CUS", [1])
+    monkeypatch.setattr(dense, "_NUM_CUS", [1])
     dys, with_bias = {}, {}
     push = tp.DEFERRED_WGRAD.push
 

@@ -654,7 +654,7 @@ def test_empty_unused_memory_level_and_grad_accum_fusion_flags(monkeypatch):
     eval iterations), 2 also after the optimizer step; ``--no-gradient-accumulation-fusion`` turns
     the MFMA wgrad-into-main_grad path off; ``--use-cpu-initialization`` reaches the config."""
     import argparse
-    from smdt_amd.parallel import tensor_parallel as tp
+    from smdt_amd.parallel import dense
     from smdt_amd.train import arguments as A
     from smdt_amd.train import training as T
     calls = []
@@ -676,7 +676,7 @@ def test_empty_unused_memory_level_and_grad_accum_fusion_flags(monkeypatch):
     assert a.gradient_accumulation_fusion is False and a.empty_unused_memory_level == 2
     a.padded_vocab_size = 128
     assert A.core_transformer_config_from_args(a).use_cpu_initialization is True
-    monkeypatch.setattr(tp, "_FUSED_WGRAD", True)
+    monkeypatch.setattr(dense, "_FUSED_WGRAD", True)
     class _Stop(Exception):
         pass
 
@@ -684,4 +684,4 @@ def test_empty_unused_memory_level_and_grad_accum_fusion_flags(monkeypatch):
         raise _Stop                 # only the flag handling before the model build is under test
     with pytest.raises(_Stop):
         T.setup_model_and_optimizer(provider, a)
-    assert tp._FUSED_WGRAD is False
+    assert dense._FUSED_WGRAD is False

@@ -11,6 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from smdt_amd.ops import functional as SF
+from smdt_amd.parallel import decode_weights as dw
 from smdt_amd.parallel import tensor_parallel as tp
 
 FP4 = [0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0]
@@ -226,15 +227,15 @@ def test_cache_follows_the_weights_and_stays_out_of_the_state_dict(fmt):
     ids, mask = _ragged_prompt()
     kw = dict(max_new_tokens=8, eos_token_id=None)
     before = {k: v.clone() for k, v in model.state_dict().items()}
-    tp._DECODE_WQ.clear()
+    dw._DECODE_WQ.clear()
     generate(model, ids, mask, **kw)
     generate(model, ids, mask, weight_format="native", **kw)
-    assert not tp._DECODE_WQ                                                     # None / native never make a copy
+    assert not dw._DECODE_WQ                                                     # None / native never make a copy
     first = generate(model, ids, mask, weight_format=fmt, **kw)
-    assert len(tp._DECODE_WQ) == 8
-    held = {k: v[1][0] for k, v in tp._DECODE_WQ.items()}
+    assert len(dw._DECODE_WQ) == 8
+    held = {k: v[1][0] for k, v in dw._DECODE_WQ.items()}
     generate(model, ids, mask, weight_format=fmt, **kw)
-    assert all(tp._DECODE_WQ[k][1][0] is q for k, q in held.items())            # reused, not re-made
+    assert all(dw._DECODE_WQ[k][1][0] is q for k, q in held.items())            # reused, not re-made
     after = model.state_dict()
     assert list(after) == list(before) and all(torch.equal(after[k], before[k]) for k in before)
     assert not any("decode" in n or "quant" in n for n, _ in model.named_buffers())
@@ -243,21 +244,21 @@ def test_cache_follows_the_weights_and_stays_out_of_the_state_dict(fmt):
         lin.weight.mul_(2)                                                       # an in-place edit: _version moves
     second = generate(model, ids, mask, weight_format=fmt, **kw)
     assert torch.equal(second, generate(_oracle(model, fmt), ids, mask, **kw))
-    assert tp._DECODE_WQ[id(lin.weight)][1][0] is not held[id(lin.weight)]
+    assert dw._DECODE_WQ[id(lin.weight)][1][0] is not held[id(lin.weight)]
     tp.params_changed()                                                          # an optimizer step: every copy goes
-    assert not tp._DECODE_WQ
+    assert not dw._DECODE_WQ
     generate(model, ids, mask, weight_format=fmt, **kw)
-    assert all(tp._DECODE_WQ[k][1][0] is not q for k, q in held.items())
+    assert all(dw._DECODE_WQ[k][1][0] is not q for k, q in held.items())
     other = [f for f in QUANT if f != fmt][0]                                    # one copy per weight, not one per format
     generate(model, ids, mask, weight_format=other, **kw)
-    assert len(tp._DECODE_WQ) == 8 and all(v[0][-1] == other for v in tp._DECODE_WQ.values())
+    assert len(dw._DECODE_WQ) == 8 and all(v[0][-1] == other for v in dw._DECODE_WQ.values())
     tp.drop_cached_weight_t([lin.weight])
-    assert id(lin.weight) not in tp._DECODE_WQ and len(tp._DECODE_WQ) == 7
+    assert id(lin.weight) not in dw._DECODE_WQ and len(dw._DECODE_WQ) == 7
     del lin, held
     del model                                                                    # a deleted model takes its copies along
     import gc
     gc.collect()
-    assert not tp._DECODE_WQ
+    assert not dw._DECODE_WQ
     assert first.shape == second.shape
 
 
@@ -296,4 +297,4 @@ def test_refusals():
         bad.decoder.layers[0].attention.proj.weight[0, 0] = float("inf")
     with pytest.raises(ValueError, match="layers.0.attention.proj.*NaN or Inf"):
         generate(bad, ids, mask, weight_format="mxfp4", **kw)
-    assert tp._DECODE["state"] is None                                           # every raise left the context
+    assert dw._DECODE["state"] is None                                           # every raise left the context

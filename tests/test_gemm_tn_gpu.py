@@ -112,12 +112,13 @@ def test_gpt_step_on_gemm_tn_matches_fp32_reference(monkeypatch, mode):
     test_model_gpu, whose gradients check every parameter). The fused paths must actually run:
     their calls are counted."""
     import test_model_gpu as T
+    from smdt_amd.parallel import dense
     from smdt_amd.parallel import tensor_parallel as tp
     monkeypatch.setattr(tp, "_FUSED_BIAS_GELU", True)
     monkeypatch.setattr(tp, "_fills_chip", lambda rows, n: True)   # test shapes: a few tiles only
     if mode == "all_linears":
-        monkeypatch.setattr(tp, "_GEMM_TN", "1")
-        monkeypatch.setattr(tp, "_GEMM_TN_SHAPES", None)
+        monkeypatch.setattr(dense, "_GEMM_TN", "1")
+        monkeypatch.setattr(dense, "_GEMM_TN_SHAPES", None)
     calls = {"fc1": 0, "mlp": 0}
     orig_fc1, orig_mlp = tp.linear_bias_gelu, tp.FusedGeLUMLP.forward
 

@@ -203,6 +203,7 @@ def test_mxfp8_linear_against_independent_reference(fmt, dtype):
 
 
 def test_mx_weight_forms_are_cached_per_optimizer_step():
+    from smdt_amd.parallel import fp8_linear
     from smdt_amd.parallel import tensor_parallel as tp
     w = torch.nn.Parameter(torch.randn(128, 128).bfloat16())
     a = tp.mx_weight_q(w)
@@ -214,7 +215,7 @@ def test_mx_weight_forms_are_cached_per_optimizer_step():
         w.mul_(2)                                      # an in-autograd write bumps the version
     assert tp.mx_weight_q(w)[0] is not b[0]
     tp.drop_cached_weight_t([w])
-    assert id(w) not in tp._MX_WQ
+    assert id(w) not in fp8_linear._MX_WQ
 
 
 def _no_saturation(t):

@@ -183,11 +183,12 @@ def test_interleaved_pipeline_matches_single_rank(nmb, p2p):
 def test_deferred_wgrad_queue_semantics(monkeypatch):
     """DeferredWgrad (CPU fallback): ready only at flush, duplicate target flushes first (order kept),
     threshold flush, and an in-place write into a queued operand is caught."""
+    from smdt_amd.parallel import dense
     from smdt_amd.parallel import tensor_parallel as tp
     q = tp.DeferredWgrad()
     q.allow_cpu = True
     q.flush_tiles = 3
-    monkeypatch.setattr(tp, "DEFERRED_WGRAD", q)
+    monkeypatch.setattr(dense, "DEFERRED_WGRAD", q)
     torch.manual_seed(0)
     ready = []
 
@@ -299,11 +300,12 @@ def test_deferred_wgrad_accumulation_window_merges(monkeypatch):
     the window, every weight's micro-batch GEMMs merge into ONE product over the concatenated
     tokens with ONE readiness report in the boundary pass, and the result equals the per-micro-
     batch sum."""
+    from smdt_amd.parallel import dense
     from smdt_amd.parallel import tensor_parallel as tp
     q = tp.DeferredWgrad()
     q.allow_cpu = True
     q.flush_tiles = 1                 # would flush after every push outside a window
-    monkeypatch.setattr(tp, "DEFERRED_WGRAD", q)
+    monkeypatch.setattr(dense, "DEFERRED_WGRAD", q)
     torch.manual_seed(1)
     ready = []
     w = torch.nn.Parameter(torch.randn(1024, 64))
@@ -330,10 +332,11 @@ def test_accumulation_window_gate(monkeypatch):
     profiles/r3_l4l/), SMDT_WGRAD_MERGE_ACCUM forcing either way, and the structural vetoes
     (ZeRO-3 partitioner, stage 2 without its in-place single-rank store, queue disabled)."""
     from types import SimpleNamespace as NS
+    from smdt_amd.parallel import dense
     from smdt_amd.parallel import tensor_parallel as tp
     q = tp.DeferredWgrad()
     monkeypatch.setattr(q, "enabled", True, raising=False)
-    monkeypatch.setattr(tp, "DEFERRED_WGRAD", q)
+    monkeypatch.setattr(dense, "DEFERRED_WGRAD", q)
     monkeypatch.delenv("SMDT_WGRAD_MERGE_ACCUM", raising=False)
     plain = NS(zero_stage=1)
     assert tp.accumulation_window_ok([plain]) is True

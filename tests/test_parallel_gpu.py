@@ -2,6 +2,7 @@
 import pytest
 import torch
 
+from smdt_amd.parallel import dense
 from smdt_amd.parallel import tensor_parallel as tp
 
 pytestmark = pytest.mark.gpu
@@ -9,7 +10,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize("fused", [True, False])
 def test_wgrad_accumulates_into_fp32_main_grad(fused, monkeypatch):
-    monkeypatch.setattr(tp, "_FUSED_WGRAD", fused)
+    monkeypatch.setattr(dense, "_FUSED_WGRAD", fused)
     torch.manual_seed(0)
     out_f, in_f, tokens = 384, 256, 1000
     w = torch.nn.Parameter(torch.randn(out_f, in_f, device="cuda", dtype=torch.bfloat16))
