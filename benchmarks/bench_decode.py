@@ -36,6 +36,11 @@ the plain decode step, with the break-even number of accepted drafts per round t
 two times; and a self-draft ``generate`` on OPT-125m for the accounting. Random-init pairs accept
 almost nothing, so no tokens/s gain of a real pair is measured here.
 
+``--prefill``: the chunked / prefix-cached prefill. ``prefill_attention`` (prefill_attn.hip) against
+SDPA on the same cache with an explicit mask at a few (B, prefix, T) points, with the workgroup
+count of each; and the time to the first token and peak memory of ``generate`` with
+``prefill_chunk`` and with a ``cached_prefix`` of 7 / 8 of the prompt against the plain prefill.
+
 One JSON line per measurement. Needs a GPU: there is no CPU fallback for a timing.
 """
 import argparse
@@ -494,12 +499,91 @@ def bench_spec_model(emit, quick=False):
               "acceptance": stats["accepted"] / max(stats["drafted"], 1)})
 
 
+def bench_prefill_kernel(emit, quick=False):
+    """``prefill_attention`` against SDPA on the same cache with an explicit mask (and the K / V head
+    expansion SDPA needs under GQA), at (B, prefix, T) points: a whole prompt, a chunk on a prefix,
+    and a short chunk on a long prefix at batch 1 (few workgroups: the case the kernel does not
+    split). FLOPs are the 4 D (keys seen) per query and head the algorithm needs."""
+    from smdt_amd.ops import functional as SF
+    dev = torch.device("cuda", 0)
+    points = ((2, 0, 256), (1, 896, 128)) if quick else ((4, 0, 2048), (4, 3584, 512), (4, 4064, 32), (1, 8064, 128))
+    for name, (nh, nkv, D) in GEOMETRIES.items():
+        for B, P, T in points:
+            S, rep, scale = P + T, nh // nkv, 1.0 / math.sqrt(D)
+            k = torch.empty(B, S, nkv, D, device=dev, dtype=torch.bfloat16).normal_()
+            v = torch.empty(B, S, nkv, D, device=dev, dtype=torch.bfloat16).normal_()
+            q = torch.empty(B, T, nh, D, device=dev, dtype=torch.bfloat16).normal_()
+            pos = torch.full((B,), P, dtype=torch.int32, device=dev)
+            lens = torch.full((B,), S, dtype=torch.int32, device=dev)
+            mask = torch.arange(S, device=dev)[None, :] <= (P + torch.arange(T, device=dev))[:, None]
+
+            def kernel():
+                return SF.prefill_attention(q, k, v, pos, lens, scale)
+
+            def sdpa():
+                kk, vv = k.transpose(1, 2), v.transpose(1, 2)
+                if rep > 1:
+                    kk, vv = kk.repeat_interleave(rep, dim=1), vv.repeat_interleave(rep, dim=1)
+                return F.scaled_dot_product_attention(q.transpose(1, 2), kk, vv, attn_mask=mask, scale=scale)
+
+            diff = (kernel().float() - sdpa().transpose(1, 2).float()).abs().max().item()
+            flops = 4.0 * D * B * nh * sum(P + t + 1 for t in range(T))
+            reps = max(3, min(100, int(0.2 / max(flops / 2e14, 2e-5))))
+            t = _alternate({"kernel": kernel, "sdpa": sdpa}, reps)
+            emit({"bench": "prefill_attention", "geometry": name, "B": B, "prefix": P, "T": T,
+                  "workgroups": -(-T * rep // 128) * nkv * B, "kernel_us": t["kernel"] * 1e6, "sdpa_us": t["sdpa"] * 1e6,
+                  "sdpa_over_kernel": t["sdpa"] / t["kernel"], "kernel_TFLOPs": flops / t["kernel"] / 1e12,
+                  "max_abs_diff_vs_sdpa": diff, "reps": reps})
+            del k, v, q, mask
+            torch.cuda.empty_cache()
+
+
+def bench_prefill_e2e(emit, quick=False):
+    """Time to the first token (a 1-token ``generate`` call, host clock around a synchronise) and
+    the peak of ``torch.cuda.max_memory_allocated`` above the resident model for the plain prefill
+    (both arguments unset: the parent's path, the baseline), ``prefill_chunk`` and a
+    ``cached_prefix`` that covers 7 / 8 of the prompt (the cache filled by an untimed plain call)."""
+    from smdt_amd.models import generation as G
+    from smdt_amd.models.hf import HFCausalLM
+    dev = torch.device("cuda", 0)
+    name = "facebook/opt-125m" if quick else "llama-7b"
+    m = HFCausalLM.from_pretrained(name, params_dtype=torch.bfloat16, device=dev).eval()
+    for B, L, chunk in ((2, 256, 64),) if quick else ((1, 1920, 512), (8, 1920, 512)):
+        ids = torch.randint(3, 30000, (B, L), device=dev)
+        cache = G.KVCache(m.model.cfg, B, L + 1, torch.bfloat16, dev)
+        m.generate(ids, max_new_tokens=1, eos_token_id=None, cache=cache)
+        arms = {"plain": {}, "prefill_chunk": dict(prefill_chunk=chunk), "cached_prefix": dict(cached_prefix=L * 7 // 8)}
+        base = torch.cuda.memory_allocated()
+
+        def run(kw):
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            t0 = time.perf_counter()
+            out = m.generate(ids, max_new_tokens=1, eos_token_id=None, cache=cache, **kw)
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0, torch.cuda.max_memory_allocated() - base, out
+        res, names = {n: [] for n in arms}, list(arms)
+        for r in range(5):               # round 0 warms every shape up; the arms alternate in order
+            for n in (names if r % 2 == 0 else names[::-1]):
+                res[n].append(run(arms[n]))
+        for n in names:
+            emit({"bench": "prefill_e2e", "model": name, "B": B, "prompt": L, "arm": n, **arms[n],
+                  "first_token_ms": min(x[0] for x in res[n][1:]) * 1e3,
+                  "first_token_ms_max": max(x[0] for x in res[n][1:]) * 1e3,
+                  "peak_extra_MiB": max(x[1] for x in res[n][1:]) / 2 ** 20,
+                  "token_equals_plain": bool(torch.equal(res[n][-1][2], res["plain"][-1][2]))})
+        del cache
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--kernel", action="store_true")
     ap.add_argument("--e2e", action="store_true")
     ap.add_argument("--linear", action="store_true", help="decode_linear against F.linear per shape and M")
     ap.add_argument("--speculative", action="store_true", help="the multi-token step and speculative generate")
+    ap.add_argument("--prefill", action="store_true", help="prefill_attention against SDPA, and the time to the first "
+                    "token / peak memory of generate(prefill_chunk / cached_prefix) against the plain prefill")
     ap.add_argument("--weight-format", default=None,
                     help="with --e2e: comma-separated weight formats to run beside the parent path")
     ap.add_argument("--kv-format", default=None, help="with --kernel: decode_attention_mx against decode_attention; "
@@ -524,6 +608,12 @@ def main():
 
     both = not (args.kernel or args.e2e or args.linear)
     with torch.no_grad():
+        if args.prefill:
+            if args.kernel or both:
+                bench_prefill_kernel(emit, args.quick)
+            if args.e2e or both:
+                bench_prefill_e2e(emit, args.quick)
+            return
         if args.speculative:
             if args.kernel or both:
                 bench_spec_kernel(emit, args.quick)

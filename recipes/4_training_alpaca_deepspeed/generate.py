@@ -2,7 +2,7 @@
 
     python generate.py --model_dir out --instruction "Name three primary colours." \
         [--input "..."] [--max_new_tokens 64] [--temperature 0.7 --top_p 0.9] [--graph]
-        [--weight_format {native,mxfp8,mxfp4}] [--kv_cache_format {mxfp8}]
+        [--weight_format {native,mxfp8,mxfp4}] [--kv_cache_format {mxfp8}] [--prefill_chunk N]
 
 ``--model_dir`` is a directory written by ``train.py`` (config.json + weights + tokenizer). The
 prompt is built from the templates the training data used (``smdt_amd.data.sft.PROMPT_DICT``) and
@@ -12,7 +12,9 @@ offline ``HashWordTokenizer`` hashes words to ids and cannot. ``--weight_format`
 layers' weights through the decode GEMM kernel: ``native`` reads the 16-bit parameters, ``mxfp8`` /
 ``mxfp4`` (bf16 models) a block-scaled copy made once; the LM head stays 16-bit and the 16-bit
 parameters stay in memory. ``--kv_cache_format mxfp8`` keeps the K/V cache as MXFP8 (E4M3 elements,
-one scale byte per 32: 51.6 % of the 16-bit cache; head dimension 64 or 128).
+one scale byte per 32: 51.6 % of the 16-bit cache; head dimension 64 or 128). ``--prefill_chunk N``
+feeds the prompt in pieces of N tokens (the chunked prefill kernel; same tokens, bounded prefill
+memory; not with ``--kv_cache_format`` or a draft model).
 """
 import argparse
 import json
@@ -42,6 +44,8 @@ def main(argv=None):
                     help="how the decode steps read the layers' weights (default: the model's own linears)")
     ap.add_argument("--kv_cache_format", choices=["mxfp8"], default=None,
                     help="how the K/V cache is stored (default: the model dtype)")
+    ap.add_argument("--prefill_chunk", type=int, default=None,
+                    help="feed the prompt in pieces of this many tokens (default: one pass)")
     ap.add_argument("--draft_model_dir", default=None,
                     help="a smaller model with the same vocabulary: greedy speculative decoding (temperature 0)")
     ap.add_argument("--num_draft_tokens", type=int, default=4, help="tokens the draft proposes per round (1 .. 7)")
@@ -72,7 +76,8 @@ def main(argv=None):
     gen = torch.Generator(device=device).manual_seed(args.seed) if sample else None
     out = model.generate(ids, max_new_tokens=new, do_sample=sample, temperature=args.temperature if sample else 1.0,
                          top_p=args.top_p, eos_token_id=eos, generator=gen, use_graph=args.graph,
-                         weight_format=args.weight_format, kv_cache_format=args.kv_cache_format, **spec)
+                         weight_format=args.weight_format, kv_cache_format=args.kv_cache_format,
+                         prefill_chunk=args.prefill_chunk, **spec)
     tokens = out[0, ids.shape[1]:].tolist()
     if eos is not None and eos in tokens:
         tokens = tokens[: tokens.index(eos) + 1]

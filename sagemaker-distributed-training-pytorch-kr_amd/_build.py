@@ -67,7 +67,10 @@ def _run(cmd, verbose):
 # Per-file device-compiler flags (measured choices). flash_attn: the SLP vectorizer packs the
 # softmax f32 math into v_pk_*_f32, which pins register pairs and measured 4 % slower in the
 # backward (profiles/r1_attn_dropout/ab_attention.log).
-KERNEL_FLAGS = {"flash_attn.hip": ["-fno-slp-vectorize"]}
+KERNEL_FLAGS = {"flash_attn.hip": ["-fno-slp-vectorize"],
+                # prefill_attn: its softmax is the same scalar f32 math; packed fp32 ops are kept out
+                # of it altogether (no v_pk_{add,mul,fma}_f32 is generated)
+                "prefill_attn.hip": ["-fno-slp-vectorize", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def kernel_sources():

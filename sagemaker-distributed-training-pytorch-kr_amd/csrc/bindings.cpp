@@ -1176,6 +1176,63 @@ Tensor decode_attn_multi(Tensor q, Tensor k_cache, Tensor v_cache, Tensor lens, 
   return out;
 }
 
+// ------------------------------------------------------------------ chunked prefill (prefill_attn.hip)
+// q [B, T, nh, D] (1 <= T <= cap) against the 16-bit caches that already hold the T new tokens;
+// pos[b] is the cache row of new token 0, lens[b] the valid keys after the append. Returns out
+// [B, T, nh, D]: query t attends keys 0 .. pos[b] + t if that row is < lens[b], else zeros.
+bool prefill_attn_supported(int64_t dtype, int64_t D, int64_t nh, int64_t nkv) {
+  return nh < (1 << 20) && nkv < (1 << 20) && D < (1 << 20) &&
+         smdt_prefill_attn_supported((int)dtype, (int)D, (int)nh, (int)nkv) != 0;
+}
+
+Tensor prefill_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor pos, Tensor lens, double scale) {
+  need_contig(q, "q");
+  TORCH_CHECK(q.dim() == 4, "prefill_attn: q must be [B, T, nh, D]");
+  dec_check_cache(k_cache, v_cache, q, "prefill_attn");
+  const int64_t B = q.size(0), T = q.size(1), nh = q.size(2), D = q.size(3), cap = k_cache.size(1),
+                nkv = k_cache.size(2);
+  TORCH_CHECK(k_cache.size(3) == D, "prefill_attn: head dim of q and the caches differ");
+  TORCH_CHECK(prefill_attn_supported(dcode(q), D, nh, nkv),
+              "prefill_attn: unsupported (needs D in {64, 128} and nh / nkv in {1, 2, 4, 8}): D ", D, ", nh ", nh,
+              ", nkv ", nkv);
+  TORCH_CHECK(T >= 1 && T <= cap, "prefill_attn: T ", T, " is outside 1 .. the cache capacity ", cap);
+  TORCH_CHECK(scale > 0, "prefill_attn: the softmax scale must be positive, got ", scale);
+  TORCH_CHECK(aligned16(q) && aligned16(k_cache) && aligned16(v_cache),
+              "prefill_attn: q and the caches must be 16-byte aligned");
+  const int* pp = dec_index(pos, q, "prefill_attn");
+  const int* lp = dec_index(lens, q, "prefill_attn");
+  auto out = torch::empty_like(q);
+  check(smdt_prefill_attn(dcode(q), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), pp, lp, out.data_ptr(),
+                          (int)B, (int)T, (int)nh, (int)nkv, (int)D, (int)cap, (float)scale, cur_stream()),
+        "prefill_attn");
+  return out;
+}
+
+// qkv [B, T, (nh + 2 nkv) D], any batch / token strides (multiples of 8 elements) over contiguous
+// rows, any T >= 1: decode_rope_append_multi with the guard that a token at or beyond lens[b]
+// writes no cache row (its q row is zeros). -> q [B, T, nh, D].
+Tensor prefill_rope_append(Tensor qkv, Tensor k_cache, Tensor v_cache, Tensor pos, Tensor lens, int64_t nh,
+                           OptT cos_t, OptT sin_t, int64_t rot) {
+  const char* what = "prefill_rope_append";
+  TORCH_CHECK(qkv.is_cuda() && qkv.dim() == 3, what, ": qkv must be a GPU [B, T, (nh + 2 nkv) D]");
+  dec_check_cache(k_cache, v_cache, qkv, what);
+  const int64_t B = qkv.size(0), T = qkv.size(1), cap = k_cache.size(1), nkv = k_cache.size(2), D = k_cache.size(3);
+  TORCH_CHECK(T >= 1 && T < (1LL << 31), what, ": T ", T, " must be at least 1");
+  dec_check_qkv(qkv, nh, nkv, D, what);
+  TORCH_CHECK(qkv.stride(2) == 1 && qkv.stride(0) % 8 == 0 && qkv.stride(1) % 8 == 0 && qkv.stride(0) >= 0 &&
+                  qkv.stride(1) >= 0 && aligned16(qkv),
+              what, ": qkv rows must be contiguous and 16-byte aligned (strides ", qkv.strides(), ")");
+  const int* pp = dec_index(pos, qkv, what);
+  const int* lp = dec_index(lens, qkv, what);
+  const RopeTables rt = dec_rope_tables(cos_t, sin_t, rot, D, qkv, what);
+  auto q = torch::empty({B, T, nh, D}, qkv.options());
+  check(smdt_prefill_rope_append(dcode(qkv), qkv.data_ptr(), qkv.stride(0), qkv.stride(1), q.data_ptr(),
+                                 k_cache.data_ptr(), v_cache.data_ptr(), pp, lp, (int)B, (int)T, (int)nh, (int)nkv,
+                                 (int)D, (int)cap, (int)rot, rt.cos, rt.sin, (int)rt.max_pos, cur_stream()),
+        what);
+  return q;
+}
+
 // ------------------------------------------------------------------ MXFP8 K/V cache (decode_attn_mx.hip)
 // kq / vq [B, cap, nkv, D] E4M3, ksc / vsc [B, cap, nkv, D / 32] uint8 E8M0; q / qkv stay 16-bit.
 static void dec_check_cache_mx(const Tensor& kq, const Tensor& ks, const Tensor& vq, const Tensor& vs,
@@ -1707,7 +1764,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         arg("T"));
   m.def("decode_attn_multi", &decode_attn_multi, arg("q"), arg("k_cache"), arg("v_cache"), arg("lens"), arg("scale"),
         arg("max_len") = 0);
-  m.def("decode_attn_mx", &decode_attn_mx, arg("q"), arg("kq"), arg("ks"), arg("vq"), arg("vs"), arg("lens"),
+  m.def("prefill_attn_supported", &prefill_attn_supported, arg("dtype"), arg("D"), arg("nh"), arg("nkv"));
+  m.def("prefill_attn", &prefill_attn, arg("q"), arg("k_cache"), arg("v_cache"), arg("pos"), arg("lens"), arg("scale"));
+  m.def("prefill_rope_append", &prefill_rope_append, arg("qkv"), arg("k_cache"), arg("v_cache"), arg("pos"),
+        arg("lens"), arg("nh"), arg("cos") = pybind11::none(), arg("sin") = pybind11::none(), arg("rot") = 0);
+  m.def("decode_attn_mx", &decode_attn_mx, arg("q"),arg("kq"), arg("ks"), arg("vq"), arg("vs"), arg("lens"),
         arg("scale"), arg("max_len") = 0);
   m.def("decode_rope_append_mx", &decode_rope_append_mx, arg("qkv"), arg("kq"), arg("ks"), arg("vq"), arg("vs"),
         arg("pos"), arg("nh"), arg("cos") = pybind11::none(), arg("sin") = pybind11::none(), arg("rot") = 0);

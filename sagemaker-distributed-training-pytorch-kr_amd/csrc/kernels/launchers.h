@@ -190,6 +190,26 @@ hipError_t smdt_decode_rope_append_multi(int dtype, const void* qkv, int64_t str
                                          int nh, int nkv, int D, int cap, int rot, const float* cos_t,
                                          const float* sin_t, int max_pos, hipStream_t st);
 
+// prefill_attn.hip: a chunk of T new tokens per sequence (1 <= T <= cap) against the 16-bit caches
+// that already hold a prefix: a one-pass flash forward on v_mfma_f32_32x32x16. smdt_prefill_attn:
+// q / out [B, T, nh, D], caches [B, cap, nkv, D] with the new tokens' k / v appended; pos[b] is the
+// cache row of new token 0 and lens[b] the valid keys after the append (device int32 [B], lens
+// clamped to cap). Query t sits at row r = pos[b] + t: r < lens[b] attends keys 0 .. r, otherwise
+// it is padding and its output row is zeros. scale > 0. Supported: bf16 / fp16, D in {64, 128},
+// nh / nkv in {1, 2, 4, 8}, 16-byte aligned contiguous operands; anything else returns
+// hipErrorInvalidValue unlaunched. No workspace, no atomics.
+int smdt_prefill_attn_supported(int dtype, int D, int nh, int nkv);
+hipError_t smdt_prefill_attn(int dtype, const void* q, const void* k_cache, const void* v_cache, const int* pos,
+                             const int* lens, void* out, int B, int T, int nh, int nkv, int D, int cap, float scale,
+                             hipStream_t st);
+// smdt_decode_rope_append_multi for any T >= 1 with the ragged prefill's guard: token t's k / v go
+// to cache row pos[b] + t only if that row is < lens[b] (the bytes of the decode append at that
+// position); a padding token writes no cache row and leaves its q_out row zeros.
+hipError_t smdt_prefill_rope_append(int dtype, const void* qkv, int64_t stride_b, int64_t stride_t, void* q_out,
+                                    void* k_cache, void* v_cache, const int* pos, const int* lens, int B, int T,
+                                    int nh, int nkv, int D, int cap, int rot, const float* cos_t, const float* sin_t,
+                                    int max_pos, hipStream_t st);
+
 // decode_attn_mx.hip: the same two operations against an MXFP8 cache: kq / vq [B, cap, nkv, D] E4M3
 // bytes, ksc / vsc [B, cap, nkv, D / 32] E8M0 bytes (mx_quant.hip's row form of every 16-bit row),
 // all contiguous and 16-byte aligned. q / qkv / out stay bf16 / fp16. Attention: the limits,

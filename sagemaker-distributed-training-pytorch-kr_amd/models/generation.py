@@ -26,10 +26,16 @@ multi-token step (``GPTModel.forward_extend``, csrc/kernels/decode_attn_multi.hi
 B (k + 1) rows of the same weight stream). ``speculative_accept`` keeps the longest prefix the
 target agrees with plus the target's own next token, so the output is the plain greedy output.
 A whole round stays on the device and can be captured in one graph.
+
+Chunked and prefix-cached prefill (``generate(prefill_chunk=..., cached_prefix=...)``): the prompt
+goes through ``GPTModel.forward_chunk`` in pieces, from row ``cached_prefix[b]`` of a cache that
+already holds the tokens before it (csrc/kernels/prefill_attn.hip: many new queries per sequence
+against a cached prefix, lengths on the device). ``_prefill_pieces`` sets ``pos`` / ``lens`` per
+piece on the device; the piece count comes from host values only.
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import Optional, Sequence, Union
 
 import torch
 
@@ -109,8 +115,10 @@ class KVCache:
         self.lens.add_(n)
 
 
-def _refuse(model, input_ids, attention_mask, max_new_tokens, cache, kv_cache_format=None):
-    """Everything generation does not do raises here, naming the cause."""
+def _refuse(model, input_ids, attention_mask, max_new_tokens, cache, kv_cache_format=None, prefill_chunk=None,
+            cached_prefix=None):
+    """Everything generation does not do raises here, naming the cause. Returns the host list of
+    per-row prefill starts of a ``prefill_chunk`` / ``cached_prefix`` call (None without either)."""
     cfg = model.cfg
     st = ps.get_state()
     if st.tp > 1 or st.pp > 1 or st.cp > 1:
@@ -136,6 +144,10 @@ def _refuse(model, input_ids, attention_mask, max_new_tokens, cache, kv_cache_fo
         if not bool(m[:, 0].all()) or bool((m[:, 1:] & ~m[:, :-1]).any()):
             raise ValueError("generate: prompts must be right-padded (attention_mask rows of ones followed by zeros, "
                              "at least one token per row)")
+    starts = None
+    if prefill_chunk is not None or cached_prefix is not None:
+        plen = [L] * B if attention_mask is None else m.sum(dim=1).tolist()      # the mask is on the host already
+        starts = _refuse_chunked(cfg, input_ids, plen, cache, kv_cache_format, prefill_chunk, cached_prefix)
     total = L + max_new_tokens
     if total > cfg.max_position_embeddings:
         raise ValueError(f"generate: prompt length {L} + max_new_tokens {max_new_tokens} = {total} exceeds "
@@ -147,6 +159,38 @@ def _refuse(model, input_ids, attention_mask, max_new_tokens, cache, kv_cache_fo
     if cache is not None and kv_cache_format is not None and cache.format != kv_cache_format:
         raise ValueError(f"generate: kv_cache_format {kv_cache_format!r} disagrees with the passed cache, whose format "
                          f"is {cache.format!r}")
+    return starts
+
+
+def _refuse_chunked(cfg, input_ids, plen, cache, kv_cache_format, prefill_chunk, cached_prefix):
+    """Every refusal of ``generate(prefill_chunk=..., cached_prefix=...)``, from host values only
+    (``plen``: the prompt lengths as a list). Returns the per-row prefill starts P[b]."""
+    B = input_ids.shape[0]
+    if kv_cache_format is not None or (cache is not None and cache.format is not None):
+        raise NotImplementedError("generate(prefill_chunk / cached_prefix): kv_cache_format is not supported (the "
+                                  "chunked prefill kernel reads a 16-bit cache, not an MXFP8 one)")
+    D, nh, nkv = cfg.kv_channels, cfg.num_attention_heads, cfg.num_query_groups
+    if input_ids.device.type == "cuda" and (D not in (64, 128) or nh % nkv or nh // nkv not in (1, 2, 4, 8)
+                                            or cfg.params_dtype not in (torch.bfloat16, torch.float16)):
+        raise NotImplementedError(f"generate(prefill_chunk / cached_prefix): the chunked prefill kernel takes bf16 / "
+                                  f"fp16 models with a head dimension in (64, 128) and num_attention_heads / "
+                                  f"num_query_groups in (1, 2, 4, 8); got {cfg.params_dtype}, head dimension {D} and "
+                                  f"{nh} / {nkv}")
+    if prefill_chunk is not None and (isinstance(prefill_chunk, bool) or int(prefill_chunk) != prefill_chunk
+                                      or prefill_chunk < 1):
+        raise ValueError(f"generate: prefill_chunk must be a positive int, got {prefill_chunk!r}")
+    if cached_prefix is None:
+        return [0] * B
+    if cache is None:
+        raise ValueError("generate: cached_prefix needs cache=, the KVCache of the earlier call whose rows it names")
+    starts = [int(cached_prefix)] * B if isinstance(cached_prefix, int) else [int(p) for p in cached_prefix]
+    if len(starts) != B:
+        raise ValueError(f"generate: cached_prefix has {len(starts)} entries for a batch of {B}")
+    for b, (p, n) in enumerate(zip(starts, plen)):
+        if not 0 <= p < n:
+            raise ValueError(f"generate: cached_prefix[{b}] = {p} must be in 0 .. prompt length - 1 = {n - 1} (a row "
+                             f"needs at least one new token)")
+    return starts
 
 
 def _decode_weights(model, weight_format):
@@ -210,7 +254,8 @@ def generate(model, input_ids, attention_mask=None, max_new_tokens: int = 32, do
              pad_token_id: int = 0, generator: Optional[torch.Generator] = None, use_graph: bool = False,
              cache: Optional[KVCache] = None, weight_format: Optional[str] = None,
              kv_cache_format: Optional[str] = None, draft_model=None, num_draft_tokens: int = 4,
-             stats: Optional[dict] = None):
+             stats: Optional[dict] = None, prefill_chunk: Optional[int] = None,
+             cached_prefix: Union[None, int, Sequence[int]] = None):
     """Greedy or sampled continuation of the right-padded prompts ``input_ids`` [B, Lmax]
     (``attention_mask`` marks the real tokens; None: every row is Lmax long) with a KV cache.
 
@@ -242,7 +287,21 @@ def generate(model, input_ids, attention_mask=None, max_new_tokens: int = 32, do
     max_new_tokens + k. ``weight_format`` applies to the target only; sampling and
     ``kv_cache_format`` are refused. ``use_graph=True`` captures one whole round. ``stats``, if a
     dict, receives ``rounds``, ``drafted`` and ``accepted`` (drafted tokens the target agreed with),
-    both counted over the rows that were still generating."""
+    both counted over the rows that were still generating.
+
+    ``prefill_chunk``: feed the prompt in pieces of that many tokens per sequence
+    (``GPTModel.forward_chunk``, csrc/kernels/prefill_attn.hip) instead of one pass, which bounds
+    the prefill's activations; ``cached_prefix`` (host int, or one per row; needs ``cache=``): rows
+    0 .. P[b] - 1 of the passed cache already hold the K / V of ``input_ids[b, :P[b]]`` from an
+    earlier call on the same cache, so the prefill starts at P[b], 0 <= P[b] < the row's prompt
+    length. Without ``prefill_chunk`` the remaining tokens go as one piece. ``input_ids`` and the
+    returned ``sequences`` keep their meaning (the whole prompt, then the new tokens): the result
+    is that of the plain call. Both are refused with ``draft_model`` and ``kv_cache_format`` (or an
+    MXFP8 ``cache``) and, on the GPU, for a model outside the kernel's set; ``weight_format`` and
+    ``use_graph`` are allowed."""
+    if draft_model is not None and (prefill_chunk is not None or cached_prefix is not None):
+        raise NotImplementedError("generate(prefill_chunk / cached_prefix): not supported with a draft model "
+                                  "(speculative decoding prefills both models in one pass)")
     if draft_model is not None:
         _refuse_speculative(model, draft_model, input_ids, attention_mask, max_new_tokens, cache, kv_cache_format,
                             do_sample, num_draft_tokens)
@@ -257,7 +316,8 @@ def generate(model, input_ids, attention_mask=None, max_new_tokens: int = 32, do
         finally:
             draft_model.train(modes[1])
             model.train(modes[0])
-    _refuse(model, input_ids, attention_mask, max_new_tokens, cache, kv_cache_format)
+    starts = _refuse(model, input_ids, attention_mask, max_new_tokens, cache, kv_cache_format, prefill_chunk,
+                     cached_prefix)
     state = _decode_weights(model, weight_format)
     if do_sample and temperature <= 0:
         raise ValueError(f"generate: temperature must be positive, got {temperature}")
@@ -267,13 +327,42 @@ def generate(model, input_ids, attention_mask=None, max_new_tokens: int = 32, do
         with dw.decode_weights(state):
             return _generate(model, input_ids, attention_mask, int(max_new_tokens), do_sample, float(temperature),
                              int(top_k), float(top_p), eos_token_id, int(pad_token_id), generator, use_graph, cache,
-                             kv_cache_format)
+                             kv_cache_format, prefill_chunk, starts)
     finally:
         model.train(was_training)
 
 
+def _prefill_pieces(model, input_ids, plen, cache, chunk, starts):
+    """The prefill of ``generate(prefill_chunk=..., cached_prefix=...)``: row b's tokens starts[b]
+    .. plen[b] - 1 go through ``forward_chunk`` in pieces of ``chunk`` tokens (None: one piece).
+    ``starts`` is a host list and the piece count comes from it and Lmax alone; ``plen`` (int64
+    [B]) stays on the device: per piece ``cache.pos`` is the piece's first row and ``cache.lens`` =
+    min(plen, pos + piece), so a short row's padding is never appended, and a row that has no
+    token left in a piece is all padding there. Each row's last real token's hidden state is kept
+    by a select and goes through the LM head once. Returns the next-token logits [B, V]."""
+    B, L = input_ids.shape
+    dev = input_ids.device
+    span = L - min(starts)                      # the most tokens a row may still need
+    chunk = span if chunk is None else min(int(chunk), span)
+    first = torch.tensor(starts, dtype=torch.int64, device=dev)
+    rows = torch.arange(B, device=dev)
+    last = None
+    for done in range(0, span, chunk):
+        T = min(chunk, span - done)
+        p0 = first + done
+        cache.pos.copy_(p0)
+        cache.lens.copy_(torch.minimum(plen, p0 + T))
+        idx = (p0[:, None] + torch.arange(T, device=dev)[None, :]).clamp(max=L - 1)
+        h = model.forward_chunk(input_ids.gather(1, idx), cache)                 # [T, B, h]
+        off = plen - 1 - p0                     # the row's last real token, if this piece holds it
+        here = ((off >= 0) & (off < T))[:, None]
+        pick = h[off.clamp(0, T - 1), rows]
+        last = torch.where(here, pick, pick.new_zeros(()) if last is None else last)
+    return model.lm_logits(last.unsqueeze(0)).squeeze(0)
+
+
 def _generate(model, input_ids, attention_mask, max_new, do_sample, temperature, top_k, top_p, eos, pad, generator,
-              use_graph, cache, kv_cache_format=None):
+              use_graph, cache, kv_cache_format=None, prefill_chunk=None, starts=None):
     cfg = model.cfg
     dev = input_ids.device
     B, L = input_ids.shape
@@ -298,7 +387,10 @@ def _generate(model, input_ids, attention_mask, max_new, do_sample, temperature,
             finished.logical_or_(tok == eos)
         return tok
 
-    logits = model.forward_prefill(input_ids, plen, cache)
+    if starts is None:
+        logits = model.forward_prefill(input_ids, plen, cache)
+    else:
+        logits = _prefill_pieces(model, input_ids, plen, cache, prefill_chunk, starts)
     cache.lens.copy_(plen)
     tok = emit(logits, 0)
 

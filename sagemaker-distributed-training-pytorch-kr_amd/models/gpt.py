@@ -196,6 +196,23 @@ class GPTModel(nn.Module):
         h = self.decoder.forward_extend(x, cache)
         return self.lm_logits(h).transpose(0, 1)
 
+    def forward_chunk(self, tokens, cache):
+        """A piece of the prompts, ``tokens`` [b, T] with any T, against a 16-bit cache that holds
+        what came before: token t of row b sits at position ``cache.pos[b] + t`` and is real if
+        that is below ``cache.lens[b]`` (the valid keys once the piece is appended); the rest is a
+        short row's padding, which is neither appended nor attended. Returns the hidden states
+        [T, b, h]; the caller picks the rows it needs and runs ``lm_logits`` on them (no [b, T, V]
+        logits are formed). Learned positions go through the ``position_ids`` path; a padding
+        token takes the position of its row's last real token, so no position leaves the table."""
+        if cache.format is not None:
+            raise NotImplementedError(f"forward_chunk: the chunked prefill reads a 16-bit K/V cache; this cache's "
+                                      f"format is {cache.format!r}")
+        T = tokens.shape[1]
+        pos = cache.pos.long().unsqueeze(1) + torch.arange(T, device=tokens.device).unsqueeze(0)       # [b, T]
+        pos = torch.minimum(pos, (cache.lens.long() - 1).clamp(min=0).unsqueeze(1))
+        x = self._embed(tokens, pos)                                                 # [T, b, h]
+        return self.decoder.forward_chunk(x, cache)
+
     def forward(self, tokens, position_ids=None, attention_mask=None, labels=None, loss_mask=None,
                 doc_start=None):
         """Returns per-token losses [b, s] when ``labels`` are given, else the logits. ``loss_mask``

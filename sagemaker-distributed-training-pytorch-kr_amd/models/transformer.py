@@ -535,6 +535,24 @@ class ParallelAttention(nn.Module):
         ctx = SF.decode_attention_multi(q, k, v, cache.lens, 1.0 / math.sqrt(self.hd), max_len=cache.max_len)
         return self.proj(ctx.transpose(0, 1).reshape(T, b, self.nh * self.hd))
 
+    def forward_chunk(self, x, cache, layer: int):
+        """A piece of a prompt, x [T, b, h] with any T, against a 16-bit ``cache`` that holds the
+        tokens before it: ``cache.pos`` is the row of the piece's token 0 and ``cache.lens`` the
+        valid keys once the piece is appended, so a token at or beyond ``lens`` is a short row's
+        padding: it is not appended and its context is zeros. QKV linear, RoPE at ``cache.pos + t``
+        and the guarded append, attention of token t over keys 0 .. pos + t (prefill_attn.hip),
+        projection. Returns what ``forward`` returns, [T, b, h]."""
+        if cache.format is not None:
+            raise NotImplementedError(f"forward_chunk: the chunked prefill reads a 16-bit K/V cache; this cache's "
+                                      f"format is {cache.format!r}")
+        qkv = self.qkv(x)                                        # [T, b, (nh + 2 nkv) d]
+        T, b = qkv.shape[0], qkv.shape[1]
+        k, v = cache.k[layer], cache.v[layer]
+        q = SF.prefill_rope_append(qkv.transpose(0, 1), k, v, cache.pos, cache.lens, self.nh, self.nkv, self.hd,
+                                   rope=self.rope)              # [b, T, nh, d]
+        ctx = SF.prefill_attention(q, k, v, cache.pos, cache.lens, 1.0 / math.sqrt(self.hd))
+        return self.proj(ctx.transpose(0, 1).reshape(T, b, self.nh * self.hd))
+
     def _groups_ok(self, qkv) -> bool:
         g = _PACK.get("groups")
         W = qkv.shape[-1]
@@ -880,6 +898,20 @@ class ParallelTransformerLayer(nn.Module):
         m, mb = self.mlp(ln2)
         return m, mb, residual
 
+    def forward_chunk(self, x, xbias, residual, cache, layer: int):
+        """``forward_decode`` for a piece of a prompt, x [T, b, h] (``ParallelAttention.forward_chunk``)."""
+        training = self.training
+        p = self.cfg.hidden_dropout
+        ln1, residual = self.input_norm.fused(x, xbias, residual, p, training)
+        if self.post_ln_residual:
+            residual = ln1
+        a, ab = self.attention.forward_chunk(ln1, cache, layer)
+        ln2, residual = self.post_attention_norm.fused(a, ab, residual, p, training)
+        if self.post_ln_residual:
+            residual = ln2
+        m, mb = self.mlp(ln2)
+        return m, mb, residual
+
     def forward_phases(self, st):
         """``forward`` cut at its four sequence-parallel exchanges for the sub-batch interleave
         (``ParallelTransformer._forward_subbatch``): each phase ends right after it STARTS an
@@ -1019,6 +1051,14 @@ class ParallelTransformer(nn.Module):
         xbias = residual = None
         for i, layer in enumerate(self.layers):
             x, xbias, residual = layer.forward_extend(x, xbias, residual, cache, i)
+        return self.final_norm.fused(x, xbias, residual, self.cfg.hidden_dropout, self.training)[0]
+
+    def forward_chunk(self, x, cache):
+        """``forward_decode`` for a piece of a prompt, x [T, b, h] with any T: the normalised output
+        [T, b, h]."""
+        xbias = residual = None
+        for i, layer in enumerate(self.layers):
+            x, xbias, residual = layer.forward_chunk(x, xbias, residual, cache, i)
         return self.final_norm.fused(x, xbias, residual, self.cfg.hidden_dropout, self.training)[0]
 
     def forward(self, x, xbias=None, residual=None, doc_start=None):

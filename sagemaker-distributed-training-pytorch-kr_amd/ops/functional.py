@@ -1076,6 +1076,144 @@ def decode_rope_append_multi(qkv, k_cache, v_cache, pos, nh, nkv, hd, rope=None)
 
 
 # --------------------------------------------------------------------------------------------
+# Chunked / prefix-cached prefill (csrc/kernels/prefill_attn.hip): T new tokens per sequence, any
+# 1 <= T <= cap, against a cache that already holds a prefix. ``pos`` (int32 [B], device) is the
+# cache row of new token 0 and ``lens`` the valid keys after the append (clamped to the capacity).
+# Query t sits at row r = pos[b] + t; r < lens[b] attends keys 0 .. r, anything else is padding
+# (a ragged batch's short rows) and returns zeros. pos = lens - T is ``decode_attention_multi``.
+
+PREFILL_TILE = 64       # keys per tile of the kernel's sweep (the emulation walks the same tiles)
+
+
+def prefill_attention_supported(q, k_cache, v_cache=None) -> bool:
+    """The operands prefill_attn.hip takes (smdt_prefill_attn_supported): q [B, T, nh, D] with
+    1 <= T <= cap and otherwise ``decode_attention_supported``'s set (16-bit caches of q's dtype, D
+    in {64, 128}, nh / nkv in {1, 2, 4, 8})."""
+    if q.dim() != 4 or k_cache.dim() != 4 or not 1 <= q.shape[1] <= k_cache.shape[1]:
+        return False
+    return decode_attention_supported(q[:, 0], k_cache, v_cache)
+
+
+def _prefill_limits(pos, lens, T, cap):
+    """[B, T]: the number of keys query t of sequence b sees, pos[b] + t + 1, or 0 for padding."""
+    r = pos.long()[:, None] + torch.arange(T, device=pos.device)[None, :]
+    ok = (r < lens.long().clamp(0, cap)[:, None]) & (r >= 0)
+    return torch.where(ok, r + 1, torch.zeros_like(r))
+
+
+def prefill_attention_ref(q, k_cache, v_cache, pos, lens, scale, emulate: bool = False):
+    """Torch twin of ``prefill_attention``. Default: ``decode_attention_ref`` of every query over
+    its own pos[b] + t + 1 keys (fp32 math, float64 for float64 operands, one rounding at the
+    output); a padding query returns zeros. Keys a query does not see are selected out before any
+    arithmetic.
+
+    ``emulate=True`` places the kernel's rounding points instead: it walks tiles of
+    ``PREFILL_TILE`` keys with a running maximum, the probabilities exp(s - m) are rounded to q's
+    dtype before the P V product (their sum l stays unrounded fp32), the rescale of l and the
+    accumulator is fp32, and the output is rounded once."""
+    B, T, nh, D = q.shape
+    cap, nkv = k_cache.shape[1], k_cache.shape[2]
+    lim = _prefill_limits(pos, lens, T, cap)
+    if not emulate:
+        out = torch.empty_like(q)
+        for t in range(T):
+            o = decode_attention_ref(q[:, t].contiguous(), k_cache, v_cache, lim[:, t], scale)
+            out[:, t] = torch.where((lim[:, t] > 0)[:, None, None], o, torch.zeros((), dtype=q.dtype, device=q.device))
+        return out
+    if nh % nkv:
+        raise ValueError(f"prefill_attention: {nh} query heads are not a multiple of {nkv} kv heads")
+    C, f32 = PREFILL_TILE, torch.float32
+    nc = (cap + C - 1) // C
+    valid = torch.arange(cap, device=q.device)[None, None, :] < lim[:, :, None]               # [B, T, cap]
+    used = valid.any(dim=1)
+    zero = torch.zeros((), dtype=f32, device=q.device)
+    kk = torch.where(used[:, :, None, None], k_cache.to(f32), zero)
+    vv = torch.where(used[:, :, None, None], v_cache.to(f32), zero)
+    qg = q.to(f32).reshape(B, T, nkv, nh // nkv, D)
+    s = torch.einsum("btkgd,bckd->btkgc", qg, kk) * scale
+    s = s.masked_fill(~valid[:, :, None, None, :], float("-inf"))
+    m = torch.full(s.shape[:-1], float("-inf"), dtype=f32, device=q.device)
+    l = torch.zeros_like(m)
+    acc = torch.zeros(s.shape[:-1] + (D,), dtype=f32, device=q.device)
+    for n in range(nc):
+        sn = s[..., n * C:(n + 1) * C]
+        mn = torch.maximum(m, sn.amax(dim=-1))
+        ms = torch.where(mn == float("-inf"), zero, mn)          # no visible key yet: every p is exp(-inf) = 0
+        alpha = torch.exp(m - ms)
+        p = torch.exp(sn - ms.unsqueeze(-1))
+        l = l * alpha + p.sum(dim=-1)
+        acc = acc * alpha.unsqueeze(-1) + torch.einsum("btkgc,bckd->btkgd", p.to(q.dtype).to(f32),
+                                                       vv[:, n * C:(n + 1) * C])
+        m = mn
+    o = torch.where((l > 0).unsqueeze(-1), acc / l.clamp(min=1e-38).unsqueeze(-1), zero)
+    return o.reshape(B, T, nh, D).to(q.dtype)
+
+
+def prefill_attention(q, k_cache, v_cache, pos, lens, scale):
+    """Attention of T new queries per sequence, q [B, T, nh, D] with any 1 <= T <= cap, against
+    the caches [B, cap, nkv, D] that already hold the new tokens' keys. ``pos`` / ``lens`` (int32
+    [B] on q's device, never read on the host): query t sits at cache row pos[b] + t and attends
+    keys 0 .. pos[b] + t if that row is below lens[b]; otherwise it is padding and its row is
+    zeros. No key row at or beyond lens[b] is loaded. Returns [B, T, nh, D]. GPU operands run
+    prefill_attn.hip (a one-pass flash forward on the 32x32x16 MFMA) or raise
+    (``prefill_attention_supported``); CPU operands run the torch twin."""
+    if q.dim() != 4:
+        raise ValueError(f"prefill_attention: q must be [B, T, nh, D], got {tuple(q.shape)}")
+    if not _ext.use_kernels(q, k_cache, v_cache):
+        if not 1 <= q.shape[1] <= k_cache.shape[1]:
+            raise ValueError(f"prefill_attention: T = {q.shape[1]} is outside 1 .. the capacity {k_cache.shape[1]}")
+        return prefill_attention_ref(q, k_cache, v_cache, pos, lens, scale)
+    if not prefill_attention_supported(q, k_cache, v_cache):
+        raise RuntimeError(f"prefill_attention on the GPU needs bf16 / fp16 q [B, T, nh, D] with 1 <= T <= cap and "
+                           f"16-bit caches [B, cap, nkv, D] of q's dtype (not an MXFP8 cache), D in (64, 128) and "
+                           f"nh / nkv in (1, 2, 4, 8); got q {tuple(q.shape)} {q.dtype}, k_cache "
+                           f"{tuple(k_cache.shape)} {k_cache.dtype}, v_cache {tuple(v_cache.shape)} {v_cache.dtype}")
+    return _ext.ext().prefill_attn(q.contiguous(), k_cache, v_cache, pos, lens, float(scale))
+
+
+def prefill_rope_append_ref(qkv, k_cache, v_cache, pos, lens, nh, nkv, hd, rope=None):
+    """Torch twin of ``prefill_rope_append``: ``decode_rope_append_ref`` of token t at position
+    pos[b] + t for the rows below lens[b]; a padding token leaves the caches alone and its q zeros.
+    Writes by selection, so nothing is read on the host."""
+    B, T = qkv.shape[0], qkv.shape[1]
+    cap = k_cache.shape[1]
+    top = cap if rope is None else min(cap, rope[0].shape[0])
+    n = lens.long().clamp(0, cap)
+    rows = torch.arange(B, device=qkv.device)
+    out = qkv.new_zeros(B, T, nh, hd)
+    for t in range(T):
+        p = pos.long() + t
+        ok = ((p >= 0) & (p < n) & (p < top))[:, None, None]
+        pc = p.clamp(0, top - 1)
+        q, k, v = _decode_rope_rows(qkv[:, t], pc, nh, nkv, hd, rope)
+        k_cache[rows, pc] = torch.where(ok, k.to(k_cache.dtype), k_cache[rows, pc])
+        v_cache[rows, pc] = torch.where(ok, v.to(v_cache.dtype), v_cache[rows, pc])
+        out[:, t] = torch.where(ok, q, out[:, t])
+    return out
+
+
+def prefill_rope_append(qkv, k_cache, v_cache, pos, lens, nh, nkv, hd, rope=None):
+    """``decode_rope_append_multi`` for any T >= 1 with the ragged prefill's guard: ``qkv`` [B, T,
+    (nh + 2 nkv) hd]; token t of sequence b is rotated at position pos[b] + t and its k / v are
+    written into cache row pos[b] + t only if that row is below lens[b] (``pos`` / ``lens`` int32
+    [B], device). The written bytes are those of ``decode_rope_append`` at that position. A padding
+    token writes no cache row, never touches a row at or beyond the capacity, and its row of the
+    returned q [B, T, nh, hd] is zeros. The model's sequence-first [T, B, W] projection is passed as
+    ``qkv.transpose(0, 1)`` without a copy. GPU operands run the kernel or raise; CPU operands run
+    the torch twin."""
+    _decode_check_qkv("prefill_rope_append", qkv, nh, nkv, hd, lead="B, T")
+    if qkv.shape[1] < 1:
+        raise ValueError("prefill_rope_append: T must be at least 1")
+    _decode_check_caches("prefill_rope_append", qkv, k_cache, v_cache, nkv, hd)
+    if not _ext.use_kernels(qkv, k_cache, v_cache):
+        return prefill_rope_append_ref(qkv, k_cache, v_cache, pos, lens, nh, nkv, hd, rope)
+    _decode_check_append_gpu("prefill_rope_append", qkv, k_cache, v_cache, hd, rope)
+    if qkv.stride(2) != 1 or qkv.stride(0) % 8 or qkv.stride(1) % 8 or qkv.data_ptr() % 16:
+        qkv = qkv.contiguous()
+    return _ext.ext().prefill_rope_append(qkv, k_cache, v_cache, pos, lens, nh, *_rope_args(rope))
+
+
+# --------------------------------------------------------------------------------------------
 # MXFP8 K/V cache (csrc/kernels/decode_attn_mx.hip, generate(kv_cache_format="mxfp8")). K and V of
 # a layer are each stored as q [B, cap, nkv, D] float8_e4m3fn and s [B, cap, nkv, D / 32] uint8
 # (E8M0, bias 127): a (sequence, position, kv head) row of D elements is D / 32 MX blocks and its
