@@ -25,7 +25,7 @@ cache on LLaMA-7B with a long prompt (``--kv-e2e B:S[,B:S...]``, default 8:3968,
 
     python benchmarks/bench_decode.py [--kernel] [--e2e] [--linear] [--weight-format native,mxfp8,mxfp4]
                                       [--kv-format mxfp8] [--kv-e2e 8:4096]
-                                      [--only llama-7b:8:4096] [--out decode.jsonl] [--quick]
+                                      [--only llama-7b:8:4096] [--out decode.jsonl] [--quick] [--sampler]
 
 ``--speculative``: the multi-token decode step and speculative ``generate`` (same protocol: device
 events, alternating order, minimum of four): ``decode_attention_multi`` (decode_attn_multi.hip) at
@@ -40,6 +40,12 @@ almost nothing, so no tokens/s gain of a real pair is measured here.
 SDPA on the same cache with an explicit mask at a few (B, prefix, T) points, with the workgroup
 count of each; and the time to the first token and peak memory of ``generate`` with
 ``prefill_chunk`` and with a ``cached_prefix`` of 7 / 8 of the prompt against the plain prefill.
+
+``--sampler``: choosing the token. Per (V, B, mode), the time of one ``emit`` of the generation
+loop (token choice, write into the sequence buffer, finished flag) on bf16 logits [B, padded V]:
+the chain of torch ops ``generate`` runs by default against ``generate(sampler="fused")``'s
+``torch.rand`` + one ``sample_tokens`` launch (sample.hip), alternating, minimum of four; and
+OPT-125m ``use_graph=True`` sampled tokens/s at B 1 / 8 with both samplers.
 
 One JSON line per measurement. Needs a GPU: there is no CPU fallback for a timing.
 """
@@ -349,6 +355,73 @@ def bench_e2e(emit, models, quick=False):
         torch.cuda.empty_cache()
 
 
+def bench_sampler_emit(emit, quick=False):
+    """One emit of the generation loop, torch chain against the fused op, per vocabulary, batch and mode."""
+    from smdt_amd.models import generation as G
+    from smdt_amd.ops import functional as SF
+    dev = torch.device("cuda", 0)
+    modes = {"greedy": dict(do_sample=False), "sample": dict(), "top_k50": dict(top_k=50), "top_p0.9": dict(top_p=0.9),
+             "top_k50_top_p0.9": dict(top_k=50, top_p=0.9)}
+    for V, Vpad in ((50272, 50304), (32000, 32000)):
+        for B in ((1, 8) if quick else (1, 8, 64)):
+            logits = (4 * torch.randn(B, Vpad, device=dev)).to(torch.bfloat16)
+            seq = torch.zeros(B, 64, dtype=torch.int64, device=dev)
+            plen = torch.full((B,), 8, dtype=torch.int64, device=dev)
+            gen = torch.Generator(device=dev).manual_seed(1)
+            for mode, kw in modes.items():
+                kw = dict(dict(do_sample=True, top_k=0, top_p=1.0), **kw)
+                finished = torch.zeros(B, dtype=torch.bool, device=dev)
+
+                def chain():
+                    tok = G._pick(logits[:, :V], kw["do_sample"], 0.7, kw["top_k"], kw["top_p"], gen)
+                    tok = torch.where(finished, torch.full_like(tok, 0), tok)
+                    seq.scatter_(1, (plen + 3).unsqueeze(1), tok.unsqueeze(1))
+                    finished.logical_or_(tok == -5)
+
+                def fused():
+                    u = torch.rand(B, generator=gen, device=dev) if kw["do_sample"] else None
+                    SF.sample_tokens(logits[:, :V], u, 0.7, kw["top_k"], kw["top_p"], kw["do_sample"], seq, plen, 3,
+                                     finished, -5, 0)
+                t = _alternate({"torch": chain, "fused": fused}, 200)
+                emit({"bench": "sampler_emit", "V": V, "B": B, "mode": mode, "dtype": "bf16", "temperature": 0.7,
+                      "torch_us": 1e6 * t["torch"], "fused_us": 1e6 * t["fused"], "torch_over_fused": t["torch"] / t["fused"]})
+
+
+def bench_sampler_e2e(emit, quick=False):
+    """Sampled ``generate`` (graph replay) on OPT-125m with the default and the fused sampler, alternating."""
+    from smdt_amd.models.hf import HFCausalLM
+    dev = torch.device("cuda", 0)
+    prompt, new = (32, 33) if quick else (128, 129)
+    model = HFCausalLM.from_pretrained("facebook/opt-125m", params_dtype=torch.bfloat16, device=dev).eval()
+    arms = [None, "fused"]
+    for B in (1, 8):
+        ids = torch.randint(3, 30000, (B, prompt), device=dev)
+
+        def run(sampler, n):
+            gen = torch.Generator(device=dev).manual_seed(2)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            model.generate(ids, max_new_tokens=n, eos_token_id=None, use_graph=True, do_sample=True, temperature=0.7,
+                           top_p=0.9, generator=gen, sampler=sampler)
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0
+        for a in arms:
+            run(a, new)
+        full, pre = {a: [] for a in arms}, {a: [] for a in arms}
+        for r in range(4):
+            for a in (arms if r % 2 == 0 else arms[::-1]):
+                full[a].append(run(a, new))
+                pre[a].append(run(a, 1))
+        base = None
+        for a in arms:
+            tps = B * (new - 1) / (min(full[a]) - min(pre[a]))
+            base = tps if a is None else base
+            emit({"bench": "generate_sampler", "model": "facebook/opt-125m", "B": B, "prompt": prompt, "new_tokens": new,
+                  "sampler": a, "use_graph": True, "temperature": 0.7, "top_p": 0.9, "decode_tokens_per_s": tps,
+                  "ms_per_step": 1e3 * (min(full[a]) - min(pre[a])) / (new - 1), "over_default": tps / base,
+                  "calls_s": full[a]})
+
+
 def _alternate(arms, reps):
     """{name: min of four timings}, the arms alternating in order."""
     for fn in arms.values():
@@ -584,6 +657,8 @@ def main():
     ap.add_argument("--speculative", action="store_true", help="the multi-token step and speculative generate")
     ap.add_argument("--prefill", action="store_true", help="prefill_attention against SDPA, and the time to the first "
                     "token / peak memory of generate(prefill_chunk / cached_prefix) against the plain prefill")
+    ap.add_argument("--sampler", action="store_true", help="the fused token sampler against the torch chain: one "
+                    "emit per vocabulary / batch / mode, and sampled generate on OPT-125m")
     ap.add_argument("--weight-format", default=None,
                     help="with --e2e: comma-separated weight formats to run beside the parent path")
     ap.add_argument("--kv-format", default=None, help="with --kernel: decode_attention_mx against decode_attention; "
@@ -613,6 +688,12 @@ def main():
                 bench_prefill_kernel(emit, args.quick)
             if args.e2e or both:
                 bench_prefill_e2e(emit, args.quick)
+            return
+        if args.sampler:
+            if args.kernel or both:
+                bench_sampler_emit(emit, args.quick)
+            if args.e2e or both:
+                bench_sampler_e2e(emit, args.quick)
             return
         if args.speculative:
             if args.kernel or both:

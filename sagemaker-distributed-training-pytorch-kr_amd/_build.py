@@ -70,7 +70,9 @@ def _run(cmd, verbose):
 KERNEL_FLAGS = {"flash_attn.hip": ["-fno-slp-vectorize"],
                 # prefill_attn: its softmax is the same scalar f32 math; packed fp32 ops are kept out
                 # of it altogether (no v_pk_{add,mul,fma}_f32 is generated)
-                "prefill_attn.hip": ["-fno-slp-vectorize", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+                "prefill_attn.hip": ["-fno-slp-vectorize", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+                # sample: integer work and one exp per element; packed fp32 ops are kept out as well
+                "sample.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def kernel_sources():

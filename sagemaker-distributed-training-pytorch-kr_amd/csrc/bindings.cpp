@@ -1296,6 +1296,62 @@ Tensor decode_rope_append_mx(Tensor qkv, Tensor kq, Tensor ks, Tensor vq, Tensor
   return q;
 }
 
+// ------------------------------------------------------------------ fused token sampler (sample.hip)
+// logits [B, V] with a contiguous last dimension (a column slice of the padded logits is fine),
+// u fp32 [B] when sampling; seq int64 [B, S], plen int64 [B] and finished bool [B] are updated in
+// place when given. Returns tok int64 [B]. The limits live in smdt_sample_supported alone.
+bool sample_tokens_supported(int64_t dtype, int64_t V, double temperature, double top_p) {
+  return smdt_sample_supported((int)dtype, V, temperature, top_p) != 0;
+}
+
+int64_t sample_stage_max() { return smdt_sample_stage_max(); }
+
+Tensor sample_tokens(Tensor logits, OptT u, double temperature, int64_t top_k, double top_p, bool do_sample, OptT seq,
+                     OptT plen, int64_t t, OptT finished, int64_t eos, int64_t pad) {
+  need_cuda(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.stride(1) == 1 && logits.stride(0) >= logits.size(1),
+              "sample_tokens: logits must be [B, V] with a contiguous last dimension and a row stride >= V");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(sample_tokens_supported(dcode(logits), V, do_sample ? temperature : 1.0, top_p),
+              "sample_tokens: unsupported (needs 1 <= V < 2^20, temperature > 0 and 0 < top_p <= 1): V ", V,
+              ", temperature ", temperature, ", top_p ", top_p);
+  auto on_dev = [&](const Tensor& x, at::ScalarType ty, const char* what) {
+    TORCH_CHECK(x.is_cuda() && x.device() == logits.device() && x.scalar_type() == ty && x.is_contiguous(),
+                "sample_tokens: ", what, " must be a contiguous ", ty, " tensor on the logits' device");
+  };
+  const float* up = nullptr;
+  if (do_sample) {
+    TORCH_CHECK(u.has_value(), "sample_tokens: sampling needs u, fp32 [B] in [0, 1)");
+    on_dev(*u, at::kFloat, "u");
+    TORCH_CHECK(u->dim() == 1 && u->size(0) == B, "sample_tokens: u must be [B]");
+    up = u->data_ptr<float>();
+  }
+  int64_t* sp = nullptr;
+  const int64_t* pp = nullptr;
+  int64_t S = 0;
+  if (seq.has_value()) {
+    TORCH_CHECK(plen.has_value(), "sample_tokens: seq needs plen");
+    on_dev(*seq, at::kLong, "seq");
+    on_dev(*plen, at::kLong, "plen");
+    TORCH_CHECK(seq->dim() == 2 && seq->size(0) == B && plen->dim() == 1 && plen->size(0) == B,
+                "sample_tokens: seq must be [B, S] and plen [B]");
+    sp = seq->data_ptr<int64_t>();
+    pp = plen->data_ptr<int64_t>();
+    S = seq->size(1);
+  }
+  unsigned char* fp = nullptr;
+  if (finished.has_value()) {
+    on_dev(*finished, at::kBool, "finished");
+    TORCH_CHECK(finished->dim() == 1 && finished->size(0) == B, "sample_tokens: finished must be [B]");
+    fp = reinterpret_cast<unsigned char*>(finished->data_ptr<bool>());
+  }
+  Tensor tok = torch::empty({B}, logits.options().dtype(at::kLong));
+  check(smdt_sample_tokens(dcode(logits), logits.data_ptr(), logits.stride(0), B, V, up, temperature, top_k, top_p,
+                           do_sample ? 1 : 0, sp, S, pp, t, fp, eos, pad, tok.data_ptr<int64_t>(), cur_stream()),
+        "sample_tokens");
+  return tok;
+}
+
 // ------------------------------------------------------------------ decode linear (decode_linear.hip)
 // fmt: 0 native, 1 mxfp8, 2 mxfp4. The limits live in smdt_decode_linear_supported alone.
 bool decode_linear_supported(int64_t dtype, int64_t fmt, int64_t M, int64_t N, int64_t K) {
@@ -1772,6 +1828,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         arg("scale"), arg("max_len") = 0);
   m.def("decode_rope_append_mx", &decode_rope_append_mx, arg("qkv"), arg("kq"), arg("ks"), arg("vq"), arg("vs"),
         arg("pos"), arg("nh"), arg("cos") = pybind11::none(), arg("sin") = pybind11::none(), arg("rot") = 0);
+  m.def("sample_tokens_supported", &sample_tokens_supported, arg("dtype"), arg("V"), arg("temperature"), arg("top_p"));
+  m.def("sample_stage_max", &sample_stage_max);
+  m.def("sample_tokens", &sample_tokens, arg("logits"), arg("u") = pybind11::none(), arg("temperature") = 1.0,
+        arg("top_k") = 0, arg("top_p") = 1.0, arg("do_sample") = true, arg("seq") = pybind11::none(),
+        arg("plen") = pybind11::none(), arg("t") = 0, arg("finished") = pybind11::none(), arg("eos") = -1,
+        arg("pad") = 0);
   m.def("decode_linear_supported", &decode_linear_supported, arg("dtype"), arg("fmt"), arg("M"), arg("N"), arg("K"));
   m.def("decode_linear_constants", &decode_linear_constants);
   m.def("decode_linear_plan", &decode_linear_plan, arg("fmt"), arg("N"), arg("K"));

@@ -222,6 +222,23 @@ hipError_t smdt_decode_rope_append_mx(int dtype, const void* qkv, void* q_out, v
                                       void* vsc, const int* pos, int B, int nh, int nkv, int D, int cap, int rot,
                                       const float* cos_t, const float* sin_t, int max_pos, hipStream_t st);
 
+// sample.hip: the fused token sampler. logits [B, V] (dtype 0 / 1 / 2, last dimension contiguous,
+// `stride` >= V elements between rows, any alignment), u fp32 [B] in [0, 1) (null when greedy) ->
+// tok int64 [B] by the rule at the head of sample.hip; top_k outside 1 .. V - 1 and top_p == 1 switch
+// that filter off. Bookkeeping (seq null: none): a row with finished[b] set emits pad,
+// seq[b, plen[b] + t] = tok[b] (seq int64 [B, S]; a column outside 0 .. S - 1 is not written),
+// finished[b] |= tok[b] == eos (eos < 0: none; finished null: none). One launch, one workgroup per
+// row, no workspace, no float atomics; the same operands give the same token on every run.
+// Supported (smdt_sample_supported): 1 <= V < 2^20, temperature > 0, 0 < top_p <= 1; anything else
+// returns hipErrorInvalidValue unlaunched. 16-bit rows of up to smdt_sample_stage_max() entries are
+// kept in LDS after the first pass.
+int smdt_sample_stage_max();
+int smdt_sample_supported(int dtype, int64_t V, double temperature, double top_p);
+hipError_t smdt_sample_tokens(int dtype, const void* logits, int64_t stride, int64_t B, int64_t V, const float* u,
+                              double temperature, int64_t top_k, double top_p, int do_sample, int64_t* seq, int64_t S,
+                              const int64_t* plen, int64_t t, unsigned char* finished, int64_t eos, int64_t pad,
+                              int64_t* tok, hipStream_t st);
+
 // decode_linear.hip: weight-streaming out [M, N] = x [M, K] . W [N, K]^T (+ bias [N]) for decode steps
 // (M <= smdt_decode_linear_max_m()). fmt 0: W is the 16-bit parameter (x's dtype); 1: E4M3 bytes
 // [N, K] + E8M0 scales [N, K / 32] (mx_quant.hip's row form); 2: E2M1 nibbles [N, K / 2] (element

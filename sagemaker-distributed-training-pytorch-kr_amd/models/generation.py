@@ -47,6 +47,7 @@ from . import transformer as _T
 from .transformer import TransformerConfig
 
 EOS_POLL_STEPS = 16     # the host asks whether every row has finished at most this often
+SAMPLERS = (None, "fused")
 
 
 def _check_kv_format(cfg: TransformerConfig, fmt, who: str):
@@ -255,7 +256,7 @@ def generate(model, input_ids, attention_mask=None, max_new_tokens: int = 32, do
              cache: Optional[KVCache] = None, weight_format: Optional[str] = None,
              kv_cache_format: Optional[str] = None, draft_model=None, num_draft_tokens: int = 4,
              stats: Optional[dict] = None, prefill_chunk: Optional[int] = None,
-             cached_prefix: Union[None, int, Sequence[int]] = None):
+             cached_prefix: Union[None, int, Sequence[int]] = None, sampler: Optional[str] = None):
     """Greedy or sampled continuation of the right-padded prompts ``input_ids`` [B, Lmax]
     (``attention_mask`` marks the real tokens; None: every row is Lmax long) with a KV cache.
 
@@ -298,7 +299,26 @@ def generate(model, input_ids, attention_mask=None, max_new_tokens: int = 32, do
     returned ``sequences`` keep their meaning (the whole prompt, then the new tokens): the result
     is that of the plain call. Both are refused with ``draft_model`` and ``kv_cache_format`` (or an
     MXFP8 ``cache``) and, on the GPU, for a model outside the kernel's set; ``weight_format`` and
-    ``use_graph`` are allowed."""
+    ``use_graph`` are allowed.
+
+    ``sampler``: None (the chain of torch ops above: ``filter_logits``, an exponential race, then
+    ``where`` / ``scatter_`` / ``logical_or_``) or "fused": choosing the token, the write into
+    ``sequences`` and the finished flag are one ``SF.sample_tokens`` call per emitted token
+    (csrc/kernels/sample.hip on the GPU), after one ``torch.rand(B)`` when sampling. Its rule is
+    ``SF.sample_tokens_ref``: ties at the top-k value are kept as in ``filter_logits``; a tie class
+    at the top-p cut is kept whole, where ``filter_logits``'s unstable sort splits it arbitrarily
+    (on tie-free rows both keep the same set); the token is read off the kept distribution's CDF,
+    in vocabulary order, at one uniform draw per row. Fused greedy tokens are the default path's.
+    Fused sampled tokens follow the same distribution but DIFFER from the default path's under the
+    same ``generator``, because the draw is a different function of it (one uniform per row, not an
+    exponential per vocabulary entry). Needs int64 ``input_ids``, a vocabulary below 2^20 and
+    0 < ``top_p`` <= 1; logits holding NaN or +inf are outside its contract. Refused with
+    ``draft_model`` (the speculative path is unchanged)."""
+    if sampler not in SAMPLERS:
+        raise ValueError(f"generate: sampler must be one of {SAMPLERS}, got {sampler!r}")
+    if sampler is not None and draft_model is not None:
+        raise NotImplementedError(f"generate(sampler={sampler!r}): not supported with a draft model (speculative "
+                                  "verification is greedy and keeps its own accept step)")
     if draft_model is not None and (prefill_chunk is not None or cached_prefix is not None):
         raise NotImplementedError("generate(prefill_chunk / cached_prefix): not supported with a draft model "
                                   "(speculative decoding prefills both models in one pass)")
@@ -327,7 +347,7 @@ def generate(model, input_ids, attention_mask=None, max_new_tokens: int = 32, do
         with dw.decode_weights(state):
             return _generate(model, input_ids, attention_mask, int(max_new_tokens), do_sample, float(temperature),
                              int(top_k), float(top_p), eos_token_id, int(pad_token_id), generator, use_graph, cache,
-                             kv_cache_format, prefill_chunk, starts)
+                             kv_cache_format, prefill_chunk, starts, sampler)
     finally:
         model.train(was_training)
 
@@ -362,7 +382,7 @@ def _prefill_pieces(model, input_ids, plen, cache, chunk, starts):
 
 
 def _generate(model, input_ids, attention_mask, max_new, do_sample, temperature, top_k, top_p, eos, pad, generator,
-              use_graph, cache, kv_cache_format=None, prefill_chunk=None, starts=None):
+              use_graph, cache, kv_cache_format=None, prefill_chunk=None, starts=None, sampler=None):
     cfg = model.cfg
     dev = input_ids.device
     B, L = input_ids.shape
@@ -380,6 +400,10 @@ def _generate(model, input_ids, attention_mask, max_new, do_sample, temperature,
     finished = torch.zeros(B, dtype=torch.bool, device=dev)
 
     def emit(logits, t):
+        if sampler == "fused":         # one launch on the GPU; it refuses what it does not take by name
+            u = torch.rand(B, generator=generator, device=dev) if do_sample else None
+            return SF.sample_tokens(logits[:, :vocab], u, temperature, top_k, top_p, do_sample, seq, plen, t, finished,
+                                    eos, pad)
         tok = _pick(logits[:, :vocab], do_sample, temperature, top_k, top_p, generator)
         tok = torch.where(finished, torch.full_like(tok, pad), tok)
         seq.scatter_(1, (plen + t).unsqueeze(1), tok.unsqueeze(1).to(seq.dtype))

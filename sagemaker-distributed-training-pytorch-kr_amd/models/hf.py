@@ -431,7 +431,8 @@ class HFCausalLM(nn.Module):
         decode GEMM kernel (see ``generate``); the default leaves the linears as they are.
         ``kv_cache_format="mxfp8"`` keeps the K/V cache as MXFP8; the default is the model dtype.
         ``draft_model`` (an ``HFCausalLM`` or a ``GPTModel``), ``num_draft_tokens`` and ``stats``:
-        greedy speculative decoding with the same output tokens (see ``generate``)."""
+        greedy speculative decoding with the same output tokens (see ``generate``).
+        ``sampler="fused"`` chooses every token in one kernel launch (see ``generate``)."""
         from .generation import generate
         if isinstance(kw.get("draft_model"), HFCausalLM):
             kw["draft_model"] = kw["draft_model"].model

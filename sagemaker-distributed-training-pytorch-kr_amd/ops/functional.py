@@ -1214,6 +1214,95 @@ def prefill_rope_append(qkv, k_cache, v_cache, pos, lens, nh, nkv, hd, rope=None
 
 
 # --------------------------------------------------------------------------------------------
+# Fused token sampler (csrc/kernels/sample.hip, generate(sampler="fused")): next-token logits
+# [B, V] -> the emitted token, the write into the sequence buffer and the finished flag. The rule:
+#   greedy    the lowest index of the row maximum;
+#   sampling  p_i = exp((x_i - max) / T). top-k (0 < k < V) keeps x_i >= the k-th largest value,
+#             ties at that value included (``models.generation.filter_logits`` does the same).
+#             top-p (< 1), with Z_k the mass of the top-k survivors, keeps a survivor iff the mass
+#             of the survivors with a STRICTLY greater logit is < top_p * Z_k: the most likely token
+#             always stays and a tie class at the cut stays whole (``filter_logits`` sorts unstably
+#             and splits such a class arbitrarily; on tie-free rows the two keep the same set).
+#             The token is the first kept index, in vocabulary order, whose inclusive prefix mass
+#             exceeds u * Z (Z: the kept mass, u in [0, 1)); -inf entries are never chosen.
+#   then      a finished row emits ``pad``; seq[b, plen[b] + t] = tok[b]; finished[b] |= tok[b] == eos.
+# Rows holding NaN or +inf are outside the contract (the kernel returns some index in 0 .. V - 1).
+
+
+def sample_tokens_supported(logits, temperature: float = 1.0, top_p: float = 1.0) -> bool:
+    """The limits of ``sample_tokens``, here alone: logits [B >= 1, V] in bf16 / fp16 / fp32 with a
+    contiguous last dimension and a row stride >= V, 1 <= V < 2^20, temperature > 0, 0 < top_p <= 1."""
+    if logits.dim() != 2 or logits.dtype not in (torch.bfloat16, torch.float16, torch.float32):
+        return False
+    B, V = logits.shape
+    if B < 1 or not 1 <= V < (1 << 20) or (V > 1 and logits.stride(1) != 1) or (B > 1 and logits.stride(0) < V):
+        return False
+    return temperature > 0 and 0 < top_p <= 1
+
+
+def sample_filter_ref(logits, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0):
+    """float64 (kept [B, V] bool, p [B, V]): the kept set of the sampling rule above and the
+    unnormalised probabilities exp((x - max) / T)."""
+    x = logits.double()
+    V = x.shape[-1]
+    p = torch.exp((x - x.max(dim=-1, keepdim=True).values) / temperature)
+    keep = torch.ones_like(x, dtype=torch.bool)
+    if 0 < top_k < V:
+        keep = x >= x.topk(top_k, dim=-1).values[:, -1:]
+    if top_p < 1.0:
+        pk = p * keep
+        srt, idx = x.sort(dim=-1, descending=True)
+        cum = pk.gather(1, idx).cumsum(dim=-1)
+        # mass strictly above a sorted position: the running sum before the first of its tie class
+        first = torch.searchsorted((-srt).contiguous(), (-srt).contiguous(), right=False)
+        above = torch.where(first > 0, cum.gather(1, (first - 1).clamp(min=0)), torch.zeros_like(cum))
+        ok = above < top_p * pk.sum(dim=-1, keepdim=True)
+        keep = keep & torch.zeros_like(keep).scatter(1, idx, ok)
+    return keep, p
+
+
+def sample_tokens_ref(logits, u=None, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                      do_sample: bool = True, seq=None, plen=None, t: int = 0, finished=None, eos=None, pad: int = 0):
+    """Torch twin of ``sample_tokens`` and the definition of its rule, in float64."""
+    if do_sample:
+        keep, p = sample_filter_ref(logits, temperature, top_k, top_p)
+        cdf = (p * keep).cumsum(dim=-1)
+        tok = (cdf > (u.double() * cdf[:, -1])[:, None]).int().argmax(dim=-1)
+    else:
+        tok = logits.argmax(dim=-1)          # the first of equal maxima
+    if finished is not None:
+        tok = torch.where(finished, torch.full_like(tok, pad), tok)
+    if seq is not None:
+        seq.scatter_(1, (plen + t).unsqueeze(1), tok.unsqueeze(1).to(seq.dtype))
+    if finished is not None and eos is not None:
+        finished.logical_or_(tok == eos)
+    return tok
+
+
+def sample_tokens(logits, u=None, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                  do_sample: bool = True, seq=None, plen=None, t: int = 0, finished=None, eos=None, pad: int = 0):
+    """The next token of every row of ``logits`` [B, V] by the rule above, int64 [B]. ``u``: fp32
+    [B] in [0, 1), one uniform draw per row (unused when ``do_sample`` is False). ``seq`` (int64
+    [B, S]) with ``plen`` (int64 [B]) and host int ``t``, and ``finished`` (bool [B]) with ``eos``
+    (None: no EOS) and ``pad``, are the generation loop's state, updated in place. GPU operands run
+    sample.hip in one launch or raise (``sample_tokens_supported``); CPU operands run the twin.
+    The same operands give the same tokens on every call."""
+    if not sample_tokens_supported(logits, temperature if do_sample else 1.0, top_p):
+        raise ValueError(f"sample_tokens needs bf16 / fp16 / fp32 logits [B, V] with a contiguous last dimension, "
+                         f"1 <= V < 2^20, temperature > 0 and 0 < top_p <= 1; got {tuple(logits.shape)} "
+                         f"{logits.dtype} strides {tuple(logits.stride())}, temperature {temperature}, top_p {top_p}")
+    if do_sample and u is None:
+        raise ValueError("sample_tokens: sampling needs u, one uniform draw in [0, 1) per row")
+    if seq is not None and plen is None:
+        raise ValueError("sample_tokens: seq needs plen")
+    if not _ext.use_kernels(logits):
+        return sample_tokens_ref(logits, u, temperature, top_k, top_p, do_sample, seq, plen, t, finished, eos, pad)
+    return _ext.ext().sample_tokens(logits, u if do_sample else None, float(temperature), int(top_k), float(top_p),
+                                    bool(do_sample), seq, plen, int(t), finished, -1 if eos is None else int(eos),
+                                    int(pad))
+
+
+# --------------------------------------------------------------------------------------------
 # MXFP8 K/V cache (csrc/kernels/decode_attn_mx.hip, generate(kv_cache_format="mxfp8")). K and V of
 # a layer are each stored as q [B, cap, nkv, D] float8_e4m3fn and s [B, cap, nkv, D / 32] uint8
 # (E8M0, bias 127): a (sequence, position, kv head) row of D elements is D / 32 MX blocks and its
