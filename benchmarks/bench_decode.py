@@ -47,6 +47,13 @@ the chain of torch ops ``generate`` runs by default against ``generate(sampler="
 ``torch.rand`` + one ``sample_tokens`` launch (sample.hip), alternating, minimum of four; and
 OPT-125m ``use_graph=True`` sampled tokens/s at B 1 / 8 with both samplers.
 
+``--wq-gemm``: the MX-weight GEMM for rows above 16. ``wq_linear`` (wq_gemm.hip) on LLaMA-7B's four
+layer shapes in both formats at M = 17 .. 8192 against the parent path (torch dequantisation into a
+scratch buffer + the library linear) and against the library bf16 linear on an already dequantised
+weight (the large-M ceiling), alternating, minimum of four; and LLaMA-7B end to end under
+``generate(weight_gemm="fused")`` against the default mode: the 1-token call (the prefill) at
+B 1 / 8 and the decode step at B 32.
+
 One JSON line per measurement. Needs a GPU: there is no CPU fallback for a timing.
 """
 import argparse
@@ -325,6 +332,96 @@ def bench_e2e_formats(emit, models, formats, quick=False):
                       "over_parent": tps / base, "calls_s": full[f]})
         del model
         torch.cuda.empty_cache()
+
+
+WQ_MS = (17, 32, 64, 128, 256, 1024, 8192)
+
+
+def bench_wq_gemm(emit, quick=False, only=None):
+    """``wq_linear`` (wq_gemm.hip) per LLaMA-7B layer shape, format and M against the parent path
+    (the torch dequantisation into a scratch buffer + ``F.linear``) and against ``F.linear`` on an
+    already dequantised bf16 weight (the large-M ceiling: it needs the resident 16-bit copy the
+    feature does without). Every call reads another copy out of a ring, as in ``bench_linear``."""
+    from smdt_amd.ops import functional as SF
+    dev = torch.device("cuda", 0)
+    for lname, (N, K) in LINEAR_SHAPES["llama-7b"].items():
+        if lname == "head" or (only and only != f"llama-7b:{lname}") or (quick and lname != "proj"):
+            continue
+        for fmt in SF.WQ_LINEAR_FORMATS:
+            w = torch.empty(N, K, device=dev, dtype=torch.bfloat16).normal_(0, 0.02)
+            q, s = SF.decode_weight_quantize(w, fmt)
+            wd = SF.decode_weight_dequantize(q, s, fmt).bfloat16()
+            del w
+            nq = max(2, min(64, RING_BYTES // (q.numel() + s.numel())))
+            ring_q = [(q.clone(), s.clone()) for _ in range(nq)]
+            ring_d = [wd.clone() for _ in range(max(2, min(64, RING_BYTES // (N * K * 2))))]
+            scratch = torch.empty(N, K, device=dev, dtype=torch.bfloat16)
+            for M in (WQ_MS[:2] + WQ_MS[-1:] if quick else WQ_MS):
+                x = torch.empty(M, K, device=dev, dtype=torch.bfloat16).normal_()
+                n_ws = SF.wq_linear_workspace_numel(M, N, K, fmt)
+                ws = torch.empty(n_ws, dtype=torch.float32, device=dev) if n_ws else None
+                pos = {"fused": 0, "parent": 0, "ceiling": 0}
+
+                def fused():
+                    pos["fused"] = (pos["fused"] + 1) % nq
+                    return SF.wq_linear(x, *ring_q[pos["fused"]], None, fmt, ws)
+
+                def parent():
+                    pos["parent"] = (pos["parent"] + 1) % nq
+                    return F.linear(x, SF.decode_weight_dequantize_into(scratch, *ring_q[pos["parent"]], fmt))
+
+                def ceiling():
+                    pos["ceiling"] = (pos["ceiling"] + 1) % len(ring_d)
+                    return F.linear(x, ring_d[pos["ceiling"]])
+                want = F.linear(x, wd).float()
+                diff = (fused().float() - want).abs().max().item() / want.abs().max().item()
+                flops = 2.0 * M * N * K
+                reps = max(3, min(200, int(0.03 / max(flops / 3e14, N * K / 2e12, 2e-5))))
+                t = _alternate({"fused": fused, "parent": parent, "ceiling": ceiling}, reps)
+                p = SF.wq_linear_plan(M, N, K, fmt)
+                emit({"bench": "wq_gemm", "linear": lname, "N": N, "K": K, "M": M, "fmt": fmt, "plan": p, "reps": reps,
+                      "fused_us": t["fused"] * 1e6, "parent_us": t["parent"] * 1e6, "ceiling_us": t["ceiling"] * 1e6,
+                      "parent_over_fused": t["parent"] / t["fused"], "fused_over_ceiling": t["fused"] / t["ceiling"],
+                      "fused_TFLOPs": flops / t["fused"] / 1e12, "fused_weight_GBps": _weight_bytes(N, K, fmt) / t["fused"] / 1e9,
+                      "max_rel_diff_vs_bf16_linear": diff})
+            del ring_q, ring_d, scratch, q, s, wd
+            torch.cuda.empty_cache()
+
+
+def bench_wq_gemm_e2e(emit, quick=False):
+    """LLaMA-7B under each quantised format with and without ``weight_gemm="fused"``, alternating:
+    the 1-token call (the prefill) at B 1 / 8 and the decode step at B 32 (graph replay)."""
+    from smdt_amd.models.hf import HFCausalLM
+    dev = torch.device("cuda", 0)
+    name = "facebook/opt-125m" if quick else "llama-7b"
+    model = HFCausalLM.from_pretrained(name, params_dtype=torch.bfloat16, device=dev).eval()
+    prompt, new = (32, 9) if quick else (128, 33)
+    arms = [None, "fused"]
+    for fmt in ("mxfp8", "mxfp4"):
+        for B in (1, 8, 32):
+            ids = torch.randint(3, 30000, (B, prompt), device=dev)
+
+            def run(mode, n):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                model.generate(ids, max_new_tokens=n, eos_token_id=None, use_graph=True, weight_format=fmt,
+                               weight_gemm=mode)
+                torch.cuda.synchronize()
+                return time.perf_counter() - t0
+            steps = new if B == 32 else 1                    # B 1 / 8: the prefill call only
+            full, pre = {a: [] for a in arms}, {a: [] for a in arms}
+            for r in range(4):                               # round 0 warms every shape up
+                for a in (arms if r % 2 == 0 else arms[::-1]):
+                    pre[a].append(run(a, 1))
+                    if steps > 1:
+                        full[a].append(run(a, steps))
+            for a in arms:
+                rec = {"bench": "generate_weight_gemm", "model": name, "weight_format": fmt, "weight_gemm": a, "B": B,
+                       "prompt": prompt, "use_graph": True, "prefill_call_ms": 1e3 * min(pre[a][1:]),
+                       "prefill_fused_speedup": min(pre[None][1:]) / min(pre[a][1:])}
+                if steps > 1:
+                    rec["ms_per_step"] = 1e3 * (min(full[a][1:]) - min(pre[a][1:])) / (steps - 1)
+                emit(rec)
 
 
 def bench_e2e(emit, models, quick=False):
@@ -659,6 +756,9 @@ def main():
                     "token / peak memory of generate(prefill_chunk / cached_prefix) against the plain prefill")
     ap.add_argument("--sampler", action="store_true", help="the fused token sampler against the torch chain: one "
                     "emit per vocabulary / batch / mode, and sampled generate on OPT-125m")
+    ap.add_argument("--wq-gemm", action="store_true", help="the MX-weight GEMM (wq_linear) against the parent path and "
+                    "the bf16 library linear per LLaMA-7B shape / format / M, and generate(weight_gemm='fused') "
+                    "against the default mode")
     ap.add_argument("--weight-format", default=None,
                     help="with --e2e: comma-separated weight formats to run beside the parent path")
     ap.add_argument("--kv-format", default=None, help="with --kernel: decode_attention_mx against decode_attention; "
@@ -694,6 +794,12 @@ def main():
                 bench_sampler_emit(emit, args.quick)
             if args.e2e or both:
                 bench_sampler_e2e(emit, args.quick)
+            return
+        if args.wq_gemm:
+            if args.kernel or both:
+                bench_wq_gemm(emit, args.quick, args.only)
+            if args.e2e or both:
+                bench_wq_gemm_e2e(emit, args.quick)
             return
         if args.speculative:
             if args.kernel or both:

@@ -3,7 +3,7 @@
     python generate.py --model_dir out --instruction "Name three primary colours." \
         [--input "..."] [--max_new_tokens 64] [--temperature 0.7 --top_p 0.9] [--graph]
         [--weight_format {native,mxfp8,mxfp4}] [--kv_cache_format {mxfp8}] [--prefill_chunk N]
-        [--sampler fused]
+        [--sampler fused] [--weight_gemm fused]
 
 ``--model_dir`` is a directory written by ``train.py`` (config.json + weights + tokenizer). The
 prompt is built from the templates the training data used (``smdt_amd.data.sft.PROMPT_DICT``) and
@@ -18,7 +18,10 @@ feeds the prompt in pieces of N tokens (the chunked prefill kernel; same tokens,
 memory; not with ``--kv_cache_format`` or a draft model). ``--sampler fused`` chooses every token
 (top-k / top-p filter, draw, end-of-sequence bookkeeping) in one kernel launch instead of a chain of
 torch ops: the same greedy tokens, and sampled tokens of the same distribution that differ from the
-default's under the same ``--seed`` (not with a draft model).
+default's under the same ``--seed`` (not with a draft model). ``--weight_gemm fused`` (with
+``--weight_format mxfp8`` / ``mxfp4``) runs the prefill and every other linear above 16 rows on the
+quantised copy as well, through the MX-weight GEMM kernel, instead of rebuilding the 16-bit weight
+in a scratch buffer per linear.
 """
 import argparse
 import json
@@ -52,6 +55,8 @@ def main(argv=None):
                     help="feed the prompt in pieces of this many tokens (default: one pass)")
     ap.add_argument("--sampler", choices=["fused"], default=None,
                     help="choose each token in one fused kernel launch (default: torch ops)")
+    ap.add_argument("--weight_gemm", choices=["fused"], default=None,
+                    help="with --weight_format mxfp8 / mxfp4: linears above 16 rows read the quantised weights too")
     ap.add_argument("--draft_model_dir", default=None,
                     help="a smaller model with the same vocabulary: greedy speculative decoding (temperature 0)")
     ap.add_argument("--num_draft_tokens", type=int, default=4, help="tokens the draft proposes per round (1 .. 7)")
@@ -83,7 +88,8 @@ def main(argv=None):
     out = model.generate(ids, max_new_tokens=new, do_sample=sample, temperature=args.temperature if sample else 1.0,
                          top_p=args.top_p, eos_token_id=eos, generator=gen, use_graph=args.graph,
                          weight_format=args.weight_format, kv_cache_format=args.kv_cache_format,
-                         prefill_chunk=args.prefill_chunk, sampler=args.sampler, **spec)
+                         prefill_chunk=args.prefill_chunk, sampler=args.sampler, weight_gemm=args.weight_gemm,
+                         **spec)
     tokens = out[0, ids.shape[1]:].tolist()
     if eos is not None and eos in tokens:
         tokens = tokens[: tokens.index(eos) + 1]

@@ -72,7 +72,9 @@ KERNEL_FLAGS = {"flash_attn.hip": ["-fno-slp-vectorize"],
                 # of it altogether (no v_pk_{add,mul,fma}_f32 is generated)
                 "prefill_attn.hip": ["-fno-slp-vectorize", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                 # sample: integer work and one exp per element; packed fp32 ops are kept out as well
-                "sample.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+                "sample.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+                # wq_gemm: MFMA, converts and fp32 vector adds in the combine; no packed fp32 ops either
+                "wq_gemm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def kernel_sources():

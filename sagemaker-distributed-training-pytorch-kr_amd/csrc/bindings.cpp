@@ -1441,6 +1441,83 @@ Tensor decode_linear(Tensor x, Tensor w, OptT scales, OptT bias, int64_t fmt, Op
   return out;
 }
 
+// ------------------------------------------------------------------ MX-weight GEMM (wq_gemm.hip)
+// fmt: 1 mxfp8, 2 mxfp4 (decode_linear's codes). The limits live in smdt_wq_gemm_supported alone.
+bool wq_linear_supported(int64_t dtype, int64_t fmt, int64_t M, int64_t N, int64_t K) {
+  return smdt_wq_gemm_supported((int)dtype, (int)fmt, M, N, K) != 0;
+}
+
+// {BN, BK, the three BM, the largest skinny M, "split K below this many tiles"}
+std::vector<int64_t> wq_linear_constants() {
+  return {smdt_wq_gemm_bn(), smdt_wq_gemm_bk(), smdt_wq_gemm_bm(0), smdt_wq_gemm_bm(1), smdt_wq_gemm_bm(2),
+          smdt_wq_gemm_skinny_max_m(), smdt_wq_gemm_split_below()};
+}
+
+// (BM, M tiles, N tiles, splits, slice length in k) of x [M, K] against a weight [N, K]
+std::vector<int64_t> wq_linear_plan(int64_t fmt, int64_t M, int64_t N, int64_t K) {
+  TORCH_CHECK(wq_linear_supported(1 /* bf16 */, fmt, M, N, K), "wq_linear_plan: fmt ", fmt, ", M ", M, ", N ",
+              N, ", K ", K);
+  int bm = 0, mt = 0, nt = 0, s = 1, sl = 0;
+  smdt_wq_gemm_plan((int)fmt, M, N, K, &bm, &mt, &nt, &s, &sl);
+  return {bm, mt, nt, s, sl};
+}
+
+Tensor wq_linear(Tensor x, Tensor w, Tensor scales, OptT bias, int64_t fmt, OptT workspace, OptT out_) {
+  need_contig(x, "x");
+  need_contig(w, "w");
+  need_contig(scales, "scales");
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2, "wq_linear: x must be [M, K] and w 2-D");
+  TORCH_CHECK(fmt == 1 || fmt == 2, "wq_linear: fmt must be 1 (mxfp8) or 2 (mxfp4), got ", fmt);
+  const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16,
+              "wq_linear: the quantised formats dequantise to bf16 (fp16 cannot hold the small blocks); x is ",
+              x.scalar_type());
+  TORCH_CHECK(wq_linear_supported(dcode(x), fmt, M, N, K), "wq_linear: unsupported M x N x K = ", M, " x ", N, " x ", K,
+              " (smdt_wq_gemm_supported)");
+  TORCH_CHECK(w.device() == x.device(), "wq_linear: w is on another device");
+  TORCH_CHECK(scales.scalar_type() == at::kByte && scales.dim() == 2 && scales.size(0) == N &&
+                  scales.size(1) == K / 32 && scales.device() == x.device(),
+              "wq_linear: scales must be uint8 [N, K / 32] on x's device");
+  if (fmt == 1) {
+    TORCH_CHECK(w.scalar_type() == at::kFloat8_e4m3fn && w.size(1) == K, "wq_linear: mxfp8 w must be E4M3 [N, K]");
+  } else {
+    TORCH_CHECK(w.scalar_type() == at::kByte && w.size(1) == K / 2, "wq_linear: mxfp4 w must be uint8 [N, K / 2]");
+  }
+  const void* bp = nullptr;
+  if (bias.has_value()) {
+    need_contig(*bias, "bias");
+    TORCH_CHECK(bias->scalar_type() == x.scalar_type() && bias->dim() == 1 && bias->size(0) == N &&
+                    bias->device() == x.device(), "wq_linear: bias must be [N] of x's dtype on its device");
+    bp = bias->data_ptr();
+  }
+  TORCH_CHECK(aligned16(x) && aligned16(w), "wq_linear: x and w must be 16-byte aligned");
+  int bm = 0, mt = 0, nt = 0, S = 1, slice = 0;
+  smdt_wq_gemm_plan((int)fmt, M, N, K, &bm, &mt, &nt, &S, &slice);
+  float* wsp = nullptr;
+  if (S > 1) {
+    TORCH_CHECK(workspace.has_value(), "wq_linear: M ", M, " x N ", N, " x K ", K, " splits K ", S,
+                " ways and needs a workspace of ", S * M * N, " fp32 elements");
+    TORCH_CHECK(workspace->scalar_type() == at::kFloat && workspace->is_contiguous() && workspace->device() == x.device() &&
+                    workspace->numel() >= S * M * N && aligned16(*workspace),
+                "wq_linear: the workspace must be contiguous fp32 on x's device with at least ", S * M * N, " elements");
+    wsp = workspace->data_ptr<float>();
+  }
+  Tensor out;
+  if (out_.has_value()) {
+    out = *out_;
+    need_contig(out, "out");
+    TORCH_CHECK(out.dim() == 2 && out.size(0) == M && out.size(1) == N && out.scalar_type() == x.scalar_type() &&
+                    out.device() == x.device() && aligned16(out),
+                "wq_linear: out must be a contiguous, 16-byte aligned [M, N] tensor of x's dtype on its device");
+  } else {
+    out = torch::empty({M, N}, x.options());
+  }
+  check(smdt_wq_gemm(dcode(x), (int)fmt, x.data_ptr(), w.data_ptr(), scales.data_ptr(), bp, out.data_ptr(), wsp, M, N,
+                     K, cur_stream()),
+        "wq_linear");
+  return out;
+}
+
 // `out` (optional) is a preallocated [B, S, H, D] view with any strides (e.g. the [s, b, h]
 // activation layout used by the transformer trunk). `doc_start` (optional, causal only) selects the
 // per-document kernels.
@@ -1840,6 +1917,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_linear", &decode_linear, arg("x"), arg("w"), arg("scales") = pybind11::none(),
         arg("bias") = pybind11::none(), arg("fmt") = 0, arg("workspace") = pybind11::none(),
         arg("out") = pybind11::none());
+  m.def("wq_linear_supported", &wq_linear_supported, arg("dtype"), arg("fmt"), arg("M"), arg("N"), arg("K"));
+  m.def("wq_linear_constants", &wq_linear_constants);
+  m.def("wq_linear_plan", &wq_linear_plan, arg("fmt"), arg("M"), arg("N"), arg("K"));
+  m.def("wq_linear", &wq_linear, arg("x"), arg("w"), arg("scales"), arg("bias") = pybind11::none(), arg("fmt") = 1,
+        arg("workspace") = pybind11::none(), arg("out") = pybind11::none());
   m.def("window_attn_fwd", &window_attn_fwd, arg("qkv"), arg("table"), arg("window"), arg("shift"), arg("heads"));
   m.def("window_attn_bwd", &window_attn_bwd, arg("qkv"), arg("table"), arg("lse"), arg("dout"), arg("window"),
         arg("shift"), arg("heads"));

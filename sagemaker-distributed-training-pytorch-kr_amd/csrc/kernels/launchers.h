@@ -256,6 +256,23 @@ void smdt_decode_linear_plan(int fmt, int64_t N, int64_t K, int* splits, int* sl
 hipError_t smdt_decode_linear(int dtype, int fmt, const void* x, const void* w, const void* scales, const void* bias,
                               void* out, float* ws, int64_t M, int64_t N, int64_t K, hipStream_t st);
 
+// wq_gemm.hip: out [M, N] = x [M, K] . dequant(W [N, K])^T (+ bias [N]) for any M >= 1 over the
+// quantised operands of decode_linear.hip (fmt 1: E4M3 bytes [N, K]; 2: E2M1 nibbles [N, K / 2]; E8M0
+// scales [N, K / 32]); x / bias / out bf16; N % 8 == 0, K % 32 == 0; x, W, out and ws 16-byte aligned.
+// smdt_wq_gemm_plan gives the tiling of a shape: the M tile (one of smdt_wq_gemm_bm(0 .. 2)), the
+// tile counts and the K split; with splits > 1 the caller provides ws, fp32 [splits, M, N], and a
+// second launch sums it (no atomics). Anything unsupported returns hipErrorInvalidValue unlaunched.
+int smdt_wq_gemm_bn();
+int smdt_wq_gemm_bk();
+int smdt_wq_gemm_bm(int i);
+int smdt_wq_gemm_skinny_max_m();
+int smdt_wq_gemm_split_below();
+int smdt_wq_gemm_supported(int dtype, int fmt, int64_t M, int64_t N, int64_t K);
+void smdt_wq_gemm_plan(int fmt, int64_t M, int64_t N, int64_t K, int* bm, int* mtiles, int* ntiles, int* splits,
+                       int* slice);
+hipError_t smdt_wq_gemm(int dtype, int fmt, const void* x, const void* w, const void* scales, const void* bias,
+                        void* out, float* ws, int64_t M, int64_t N, int64_t K, hipStream_t st);
+
 // window_attn.hip: Swin shifted-window attention on the qkv linear's output over the padded,
 // unrolled grid, qkv [B, ph, pw, 3 heads d] read as (3, heads, d); roll, window partition and head
 // split are address arithmetic. table: fp32 [(2 ws - 1)^2, heads]. out [B, ph, pw, heads d] at the

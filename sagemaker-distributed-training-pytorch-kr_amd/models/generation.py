@@ -194,10 +194,18 @@ def _refuse_chunked(cfg, input_ids, plen, cache, kv_cache_format, prefill_chunk,
     return starts
 
 
-def _decode_weights(model, weight_format):
+def _decode_weights(model, weight_format, weight_gemm=None, rows=()):
     """The ``dw.DecodeWeights`` of a ``generate(weight_format=...)`` call (None for None): every
     refusal raises here, the quantised copies are made (or found in the cache) and the kernel's
-    workspace and the dequantisation scratch are allocated, all before the first decode step."""
+    workspace and the dequantisation scratch are allocated, all before the first decode step.
+    ``weight_gemm="fused"``: no scratch; the MX-weight GEMM's workspace is sized for ``rows``, the
+    row counts the call's linears will see."""
+    if weight_gemm not in dw.WEIGHT_GEMMS:
+        raise ValueError(f"generate: weight_gemm must be one of {dw.WEIGHT_GEMMS}, got {weight_gemm!r}")
+    if weight_gemm is not None and weight_format not in SF.WQ_LINEAR_FORMATS:
+        raise ValueError(f"generate(weight_gemm={weight_gemm!r}): needs a quantised weight_format (one of "
+                         f"{SF.WQ_LINEAR_FORMATS}), got weight_format={weight_format!r}: there is no quantised weight "
+                         "to run the GEMM on")
     if weight_format is None:
         return None
     if weight_format not in SF.DECODE_LINEAR_FORMATS:
@@ -216,8 +224,8 @@ def _decode_weights(model, weight_format):
                                    "training linear); weight formats are for models with plain 16-bit linears")
             linears.append((name, mod.weight, False))
     linears.append(("the LM head", head, True))
-    state = dw.DecodeWeights(weight_format, head_weight=head)
-    state.prepare(linears)
+    state = dw.DecodeWeights(weight_format, head_weight=head, gemm=weight_gemm)
+    state.prepare(linears, rows)
     return state
 
 
@@ -256,7 +264,8 @@ def generate(model, input_ids, attention_mask=None, max_new_tokens: int = 32, do
              cache: Optional[KVCache] = None, weight_format: Optional[str] = None,
              kv_cache_format: Optional[str] = None, draft_model=None, num_draft_tokens: int = 4,
              stats: Optional[dict] = None, prefill_chunk: Optional[int] = None,
-             cached_prefix: Union[None, int, Sequence[int]] = None, sampler: Optional[str] = None):
+             cached_prefix: Union[None, int, Sequence[int]] = None, sampler: Optional[str] = None,
+             weight_gemm: Optional[str] = None):
     """Greedy or sampled continuation of the right-padded prompts ``input_ids`` [B, Lmax]
     (``attention_mask`` marks the real tokens; None: every row is Lmax long) with a KV cache.
 
@@ -274,6 +283,14 @@ def generate(model, input_ids, attention_mask=None, max_new_tokens: int = 32, do
     stream a cached block-scaled copy instead, and the prefill and batches above 16 run the
     ordinary linear over the same dequantised values. The LM head always uses the native form; the
     16-bit parameters stay resident and ``state_dict`` is unchanged.
+
+    ``weight_gemm``: None, or "fused" (needs ``weight_format`` "mxfp8" / "mxfp4"): linears with more
+    than 16 rows (the prefill and every piece of a chunked one, batches above 16, a speculative
+    target's verify step) run the MX-weight GEMM (csrc/kernels/wq_gemm.hip) on the quantised copy
+    itself, dequantising inside the tile, instead of rebuilding the 16-bit weight in a scratch
+    buffer first. Same weight values, fp32 accumulation, one rounding; no scratch is allocated and
+    no step allocates, so ``use_graph`` still captures. A layer linear the kernel does not take
+    (output size no multiple of 8) is refused by name before the prefill.
 
     ``kv_cache_format``: None (a cache in the model dtype) or "mxfp8": K and V are stored as MXFP8,
     the MX quantisation of the 16-bit rows, at 51.6 % of the bytes (head dimension 64 or 128,
@@ -325,7 +342,8 @@ def generate(model, input_ids, attention_mask=None, max_new_tokens: int = 32, do
     if draft_model is not None:
         _refuse_speculative(model, draft_model, input_ids, attention_mask, max_new_tokens, cache, kv_cache_format,
                             do_sample, num_draft_tokens)
-        state = _decode_weights(model, weight_format)
+        B, L = input_ids.shape
+        state = _decode_weights(model, weight_format, weight_gemm, (B * L, B, B * (int(num_draft_tokens) + 1)))
         modes = (model.training, draft_model.training)
         model.eval()
         draft_model.eval()
@@ -338,7 +356,10 @@ def generate(model, input_ids, attention_mask=None, max_new_tokens: int = 32, do
             model.train(modes[0])
     starts = _refuse(model, input_ids, attention_mask, max_new_tokens, cache, kv_cache_format, prefill_chunk,
                      cached_prefix)
-    state = _decode_weights(model, weight_format)
+    B, L = input_ids.shape
+    span = L if starts is None else L - min(starts)           # the pieces _prefill_pieces cuts: whole ones and a rest
+    piece = span if prefill_chunk is None else min(int(prefill_chunk), span)
+    state = _decode_weights(model, weight_format, weight_gemm, (B * piece, B * (span % piece), B))
     if do_sample and temperature <= 0:
         raise ValueError(f"generate: temperature must be positive, got {temperature}")
     was_training = model.training

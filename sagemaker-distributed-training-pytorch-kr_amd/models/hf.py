@@ -432,7 +432,9 @@ class HFCausalLM(nn.Module):
         ``kv_cache_format="mxfp8"`` keeps the K/V cache as MXFP8; the default is the model dtype.
         ``draft_model`` (an ``HFCausalLM`` or a ``GPTModel``), ``num_draft_tokens`` and ``stats``:
         greedy speculative decoding with the same output tokens (see ``generate``).
-        ``sampler="fused"`` chooses every token in one kernel launch (see ``generate``)."""
+        ``sampler="fused"`` chooses every token in one kernel launch (see ``generate``).
+        ``weight_gemm="fused"`` (with ``weight_format`` "mxfp8" / "mxfp4") runs the linears above 16
+        rows on the quantised weights too, through the MX-weight GEMM kernel (see ``generate``)."""
         from .generation import generate
         if isinstance(kw.get("draft_model"), HFCausalLM):
             kw["draft_model"] = kw["draft_model"].model

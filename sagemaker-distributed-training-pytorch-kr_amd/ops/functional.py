@@ -1957,6 +1957,77 @@ def decode_linear(x, w, scales=None, bias=None, fmt: str = "native", workspace=N
 
 
 # --------------------------------------------------------------------------------------------
+# MX-weight GEMM (csrc/kernels/wq_gemm.hip): the same y = x dequant(W)^T (+ b) over the same
+# quantised operands at ANY row count: an MFMA GEMM that dequantises inside the tile, so rows above
+# decode_linear's bound need no 16-bit copy of the weight. bf16, "mxfp8" / "mxfp4" only.
+
+WQ_LINEAR_FORMATS = ("mxfp8", "mxfp4")
+
+
+def _wq_fmt(fmt):
+    if fmt not in WQ_LINEAR_FORMATS:
+        raise ValueError(f"wq_linear: the weight format must be one of {WQ_LINEAR_FORMATS}, got {fmt!r}")
+    return _DL_FMT[fmt]
+
+
+def wq_linear_supported(M: int, N: int, K: int, dtype, fmt: str) -> bool:
+    """Whether wq_gemm.hip takes x [M, K] of ``dtype`` against a weight [N, K] in ``fmt``: the
+    limits live in the kernel file alone (smdt_wq_gemm_supported) and this asks it."""
+    code = {torch.bfloat16: 1, torch.float16: 2}.get(dtype)
+    if code is None or fmt not in WQ_LINEAR_FORMATS or not _ext.available():
+        return False
+    return bool(_ext.ext().wq_linear_supported(code, _DL_FMT[fmt], int(M), int(N), int(K)))
+
+
+def wq_linear_constants() -> dict:
+    """The kernel's tiling constants: W rows (``bn``) and k (``bk``) per workgroup step, the M tiles
+    (``bm``), the largest M one workgroup holds whole (``skinny_max_m``) and the tile count below
+    which K is split."""
+    c = [int(v) for v in _ext.ext().wq_linear_constants()]
+    return {"bn": c[0], "bk": c[1], "bm": tuple(c[2:5]), "skinny_max_m": c[5], "split_below": c[6]}
+
+
+def wq_linear_plan(M: int, N: int, K: int, fmt: str) -> dict:
+    """How the kernel tiles this shape: the M tile, the tile counts, the K split and its slice."""
+    bm, mt, nt, s, sl = (int(v) for v in _ext.ext().wq_linear_plan(_wq_fmt(fmt), int(M), int(N), int(K)))
+    return {"bm": bm, "m_tiles": mt, "n_tiles": nt, "splits": s, "slice": sl, "regime": "skinny" if mt == 1 else "wide"}
+
+
+def wq_linear_workspace_numel(M: int, N: int, K: int, fmt: str) -> int:
+    """fp32 elements of workspace ``wq_linear`` needs for this shape (0: no split)."""
+    s = wq_linear_plan(M, N, K, fmt)["splits"]
+    return s * int(M) * int(N) if s > 1 else 0
+
+
+def wq_linear(x, q, scales, bias=None, fmt: str = "mxfp8", workspace=None, out=None):
+    """y [..., N] = x [..., K] dequant(q, scales)^T (+ bias) for the operands of
+    ``decode_weight_quantize`` at any row count. GPU operands run wq_gemm.hip or raise, naming the
+    shape (``wq_linear_supported``); ``workspace``: fp32, at least ``wq_linear_workspace_numel``
+    elements, needed when the kernel splits K; ``out``: a [M, N] tensor to write (default: a new
+    one). CPU operands run the torch twin (``decode_linear_ref``)."""
+    f = _wq_fmt(fmt)
+    if scales is None:
+        raise ValueError(f"wq_linear: the {fmt} format needs its scales")
+    if not _ext.use_kernels(x, q):
+        y = decode_linear_ref(x, q, scales, bias, fmt)
+        return y if out is None else out.copy_(y.view(out.shape))
+    if x.dtype == torch.float16:
+        raise ValueError(f"wq_linear: the {fmt} format is for bf16 models: its blocks dequantise to bf16, and "
+                         "fp16 cannot hold the small ones")
+    K = x.shape[-1]
+    M = x.numel() // K
+    N = q.shape[0]
+    if not wq_linear_supported(M, N, K, x.dtype, fmt):
+        raise RuntimeError(f"wq_linear: the kernel does not take M x N x K = {M} x {N} x {K}, {x.dtype}, {fmt} "
+                           "(wq_linear_supported: bf16, N a multiple of 8, K a multiple of 32)")
+    x2 = x.reshape(M, K)
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    y = _ext.ext().wq_linear(x2, q, scales, bias, f, workspace, out)
+    return y.view(tuple(x.shape[:-1]) + (N,))
+
+
+# --------------------------------------------------------------------------------------------
 # Switch MLP without host syncs (--moe-grouped-gemm): device routing into an expert-sorted,
 # tile-padded row layout, and expert GEMMs that pick their weight per 256-row tile on the device
 # (csrc/kernels/moe_route.hip, gemm_tn.hip GROUPED, wgrad_gemm.hip wgrad_ranged_kernel).

@@ -12,6 +12,7 @@ from typing import Optional
 
 import torch
 
+from ..ops import _ext
 from ..ops import functional as SF
 from . import dense
 from .dense import linear_rows
@@ -22,23 +23,34 @@ from .dense import linear_rows
 # (M <= 16 rows) run the weight-streaming kernel (csrc/kernels/decode_linear.hip) on the 16-bit
 # parameter ("native") or on a cached MXFP8 / MXFP4 copy of it; larger M (the prefill, big batches)
 # under a quantised format dequantise the copy into one reused scratch buffer and run the existing
-# linear on it, so prefill and decode see the same weight values. The copies are plain tensors in
-# a side table: not parameters, not buffers, in no state_dict.
+# linear on it, so prefill and decode see the same weight values; with ``weight_gemm="fused"`` they
+# run the MX-weight GEMM (csrc/kernels/wq_gemm.hip) on the copy itself instead and no 16-bit form
+# of it is ever built. The copies are plain tensors in a side table: not parameters, not buffers,
+# in no state_dict.
 
 _DECODE = {"state": None}
 _DECODE_WQ: dict = {}
+WEIGHT_GEMMS = (None, "fused")
 
 
 class DecodeWeights:
     """What a ``decode_weights`` context carries: the format, the LM-head weight (always streamed
     in its native form: it is tied to the embedding in OPT / GPT-2 and is the accuracy-sensitive
     linear), the kernel's split-K workspace and the dequantisation scratch. ``prepare`` sizes both
-    buffers for a model, so no decode step allocates them."""
+    buffers for a model, so no decode step allocates them. ``gemm``: None (rows above the decode
+    kernel's bound dequantise into the scratch) or "fused" (they run ``SF.wq_linear`` on the
+    quantised copy; no scratch)."""
 
-    def __init__(self, fmt: str, head_weight=None):
+    def __init__(self, fmt: str, head_weight=None, gemm: Optional[str] = None):
         if fmt not in SF.DECODE_LINEAR_FORMATS:
             raise ValueError(f"weight_format must be None or one of {SF.DECODE_LINEAR_FORMATS}, got {fmt!r}")
+        if gemm not in WEIGHT_GEMMS:
+            raise ValueError(f"weight_gemm must be one of {WEIGHT_GEMMS}, got {gemm!r}")
+        if gemm is not None and fmt not in SF.WQ_LINEAR_FORMATS:
+            raise ValueError(f"weight_gemm={gemm!r} needs a quantised weight_format (one of {SF.WQ_LINEAR_FORMATS}): "
+                             f"with weight_format={fmt!r} there is no quantised weight to run it on")
         self.fmt = fmt
+        self.gemm = gemm
         self.head_weight = head_weight
         self.workspace = None
         self.scratch = None
@@ -46,9 +58,12 @@ class DecodeWeights:
     def format_of(self, weight) -> str:
         return "native" if weight is self.head_weight else self.fmt
 
-    def prepare(self, linears):
+    def prepare(self, linears, rows=()):
         """``linears``: (name, weight, is_head) of every linear that will be routed. Quantises each
-        once (raising for a weight the format cannot take) and allocates the buffers."""
+        once (raising for a weight the format cannot take) and allocates the buffers. ``rows``: the
+        row counts the call will run (prefill, decode step, speculative verify step); in fused mode
+        the split-K workspace is sized for those above the decode kernel's bound, and a layer
+        linear the GEMM kernel does not take is refused here, by name."""
         ws = scr = 0
         dev = dtype = None
         # a decode step has ``batch`` rows, but a short prompt's prefill (rows = batch * length) can
@@ -62,7 +77,17 @@ class DecodeWeights:
                     raise ValueError(f"generate(weight_format={self.fmt!r}): {name} is fp16; the quantised formats are "
                                      "for bf16 models (their blocks dequantise to bf16, fp16 cannot hold the small ones)")
                 decode_weight_q(w, fmt, name)
-                scr = max(scr, w.numel())
+                if self.gemm is None:
+                    scr = max(scr, w.numel())
+                elif w.is_cuda or _ext.available():
+                    # the kernel's shape limits hold on either device; the CPU twin takes any dtype
+                    if not SF.wq_linear_supported(max_m + 1, N, K, w.dtype if w.is_cuda else torch.bfloat16, fmt):
+                        raise ValueError(f"generate(weight_gemm={self.gemm!r}): {name} [{N}, {K}] is not taken by the "
+                                         f"{fmt} GEMM kernel (wq_linear_supported: bf16, output size a multiple of 8, "
+                                         "input size a multiple of 32)")
+                    for m in rows if w.is_cuda else ():
+                        if m > max_m:
+                            ws = max(ws, SF.wq_linear_workspace_numel(m, N, K, fmt))
             if w.is_cuda and SF.decode_linear_supported(max_m, N, K, w.dtype, fmt):
                 ws = max(ws, SF.decode_linear_workspace_numel(max_m, N, K, fmt))
             dev, dtype = w.device, w.dtype
@@ -71,10 +96,10 @@ class DecodeWeights:
         if scr:
             self.scratch = torch.empty(scr, dtype=dtype, device=dev)
 
-    def workspace_for(self, M, N, K, fmt):
+    def workspace_for(self, M, N, K, fmt, numel=SF.decode_linear_workspace_numel):
         """The split-K workspace for this call (None: no split). ``prepare`` has sized it for every
-        shape of its model; a linear it has not seen grows it here."""
-        need = SF.decode_linear_workspace_numel(M, N, K, fmt)
+        shape of its model; a linear (or, in fused mode, a row count) it has not seen grows it here."""
+        need = numel(M, N, K, fmt)
         if not need:
             return None
         if self.workspace is None or self.workspace.numel() < need:
@@ -148,6 +173,9 @@ def _decode_route(st: DecodeWeights, x, weight, bias, add_bias, fp8):
     q, s = decode_weight_q(weight, fmt)
     if kernel:
         return SF.decode_linear(x, q, s, b, fmt, st.workspace_for(M, N, K, fmt))
+    if st.gemm == "fused":       # GPU operands run wq_gemm.hip or raise; CPU operands run the torch twin
+        ws = st.workspace_for(M, N, K, fmt, SF.wq_linear_workspace_numel) if x.is_cuda else None
+        return SF.wq_linear(x, q, s, b, fmt, ws)
     return linear_rows(x, st.dequantised(weight, q, s, fmt), b)
 
 
