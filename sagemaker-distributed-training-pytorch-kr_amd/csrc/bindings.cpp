@@ -237,17 +237,26 @@ void set_rng_step(OptT counter) {
 }
 
 // ------------------------------------------------------------------ optimizer
-void adam(Tensor master, Tensor grad, Tensor m, Tensor v, OptT model_out, double lr, double beta1,
-          double beta2, double eps, double wd, int64_t step, bool adamw, OptT grad_mul,
-          OptT found_inf) {
-  for (auto* t : {&master, &grad, &m, &v}) {
-    need_contig(*t, "adam buffer");
+// The optimizer kernels move 16-byte vectors (f32x4, u16x8; 8-byte stores into the model copy)
+// straight on data_ptr(): need_contig refuses, by name, a buffer that is not 16-byte aligned (a
+// slice of a flat buffer at an odd offset) before anything is launched.
+static void check_adam_buffers(const Tensor& master, const Tensor& grad, const Tensor& m, const Tensor& v) {
+  const std::pair<const Tensor*, const char*> bufs[] = {
+      {&master, "adam master"}, {&grad, "adam grad"}, {&m, "adam exp_avg"}, {&v, "adam exp_avg_sq"}};
+  for (const auto& [t, name] : bufs) {
+    need_contig(*t, name);
     TORCH_CHECK(t->scalar_type() == at::kFloat, "adam: fp32 buffers expected");
     TORCH_CHECK(t->numel() == master.numel(), "adam: buffer size mismatch");
   }
+}
+
+void adam(Tensor master, Tensor grad, Tensor m, Tensor v, OptT model_out, double lr, double beta1,
+          double beta2, double eps, double wd, int64_t step, bool adamw, OptT grad_mul,
+          OptT found_inf) {
+  check_adam_buffers(master, grad, m, v);
   int mdt = 0;
   if (model_out) {
-    need_contig(*model_out, "model_out");
+    need_contig(*model_out, "adam model_out");
     TORCH_CHECK(model_out->numel() == master.numel(), "adam: model_out size mismatch");
     mdt = dcode(*model_out);
     TORCH_CHECK(mdt != 0, "adam: model_out must be bf16/fp16 (fp32 masters ARE the model)");
@@ -271,16 +280,12 @@ void adam(Tensor master, Tensor grad, Tensor m, Tensor v, OptT model_out, double
 void adam_capturable(Tensor master, Tensor grad, Tensor m, Tensor v, OptT model_out, Tensor hyper,
                      double beta1, double beta2, double eps, double wd, bool adamw, OptT grad_mul,
                      OptT found_inf) {
-  for (auto* t : {&master, &grad, &m, &v}) {
-    need_contig(*t, "adam buffer");
-    TORCH_CHECK(t->scalar_type() == at::kFloat, "adam: fp32 buffers expected");
-    TORCH_CHECK(t->numel() == master.numel(), "adam: buffer size mismatch");
-  }
+  check_adam_buffers(master, grad, m, v);
   TORCH_CHECK(hyper.scalar_type() == at::kFloat && hyper.is_cuda() && hyper.numel() == 3 && hyper.is_contiguous(),
               "adam_capturable: hyper = device fp32 [lr, bc1, bc2]");
   int mdt = 0;
   if (model_out) {
-    need_contig(*model_out, "model_out");
+    need_contig(*model_out, "adam model_out");
     TORCH_CHECK(model_out->numel() == master.numel(), "adam: model_out size mismatch");
     mdt = dcode(*model_out);
     TORCH_CHECK(mdt != 0, "adam: model_out must be bf16/fp16 (fp32 masters ARE the model)");
@@ -296,7 +301,7 @@ void adam_capturable(Tensor master, Tensor grad, Tensor m, Tensor v, OptT model_
 }
 
 Tensor sumsq(Tensor x, OptT found_inf) {
-  need_contig(x, "x");
+  need_contig(x, "sumsq x");
   const int64_t n = x.numel();
   const int nb = smdt_sumsq_nblocks(n);
   auto f32 = x.options().dtype(at::kFloat);
@@ -320,15 +325,15 @@ std::vector<Tensor> clip_coef(Tensor sumsq_t, double max_norm, double inv_scale)
 }
 
 void scale_(Tensor x, OptT mul, double cmul) {
-  need_contig(x, "x");
+  need_contig(x, "scale_ x");
   check(smdt_scale(dcode(x), x.data_ptr(), x.numel(), mul ? mul->data_ptr<float>() : nullptr,
                    (float)cmul, cur_stream()),
         "scale");
 }
 
 void cast_(Tensor x, Tensor y, bool accumulate) {
-  need_contig(x, "x");
-  need_contig(y, "y");
+  need_contig(x, "cast_ x");
+  need_contig(y, "cast_ y");
   TORCH_CHECK(x.numel() == y.numel(), "cast: size mismatch");
   check(smdt_cast(dcode(x), dcode(y), x.data_ptr(), y.data_ptr(), x.numel(), accumulate ? 1 : 0,
                   cur_stream()),

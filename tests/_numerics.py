@@ -33,6 +33,15 @@ LN_ELEM_TOL = {torch.bfloat16: 2.0 ** -6, torch.float16: 2.0 ** -9, torch.float3
 LN_COL_TOL = 1.25e-6
 LN_STAT_TOL = 7.5e-7
 
+# Fused Adam (optim.hip). Each tolerance is 4x the largest error of ``adam_kernel_emulation`` against
+# ``adam_ref`` measured by test_numerics_sensitivity.py over ``ADAM_CASES`` (every size of
+# ``ADAM_SIZES``, every mode):
+#   m' relative 1.62e-7, v' relative 2.86e-7 (both largest in L2 mode, which adds a rounding);
+#   p': |p' - ref| <= a eps32 |ref| + b |ref - p|. a is measured where the step is below 2^-8 |p'|
+#     (the roundings of the two subtractions at p's magnitude: 0.988 of eps32 |p'|), b where the step
+#     is at least |p'| (the fp32 arithmetic of the update itself: 2.99e-7 of the step).
+ADAM_TOL = {"m": 6.5e-7, "v": 1.15e-6, "p_a": 3.96, "p_b": 1.2e-6}
+
 
 def row_rel_err(out, ref, floor_frac: float = 1e-4, row_floor=None) -> float:
     """max over rows of max|out - ref| / max|ref| (rows = every index but the last). Rows whose
@@ -775,3 +784,190 @@ def wgrad_exact_bias_twin(bg, a):
     out = bg + a.float().sum(0)
     assert torch.equal(out.double(), bg.double() + a.double().sum(0))
     return out
+
+
+# ------------------------------------------------------------------------------- fused Adam
+#
+# optim.hip's Adam / AdamW step over flat fp32 buffers. ``adam_case`` builds inputs on which every
+# term of the update is visible somewhere, ``adam_ref`` is the float64 textbook step (with a knob
+# that breaks one term), ``adam_kernel_emulation`` the same step in fp32 in the kernel's operation
+# order, and ``adam_excess`` the criterion the GPU tests judge the kernel by.
+
+ADAM_SIZES = (1, 3, 4, 5, 1023, 1024, 1027, 1028, 3074, 262147)
+ADAM_LR, ADAM_EPS = 1e-2, 1e-8
+# The geometry case (run at every size of ADAM_SIZES) and the mode cases (each at two or three
+# sizes): adamw, weight decay, grad_mul, step, betas, model copy dtype, sizes.
+ADAM_GEOMETRY_MODE = dict(adamw=True, wd=0.1, grad_mul=0.37, step=2, betas=(0.9, 0.999), model=torch.bfloat16)
+ADAM_MODES = (
+    dict(adamw=True, wd=0.1, grad_mul=None, step=1, betas=(0.9, 0.95), model=torch.bfloat16, sizes=(5, 1027, 3074)),
+    dict(adamw=True, wd=0.1, grad_mul=0.37, step=2, betas=(0.9, 0.999), model=torch.float16, sizes=(1027, 262147)),
+    dict(adamw=False, wd=0.1, grad_mul=0.37, step=1, betas=(0.9, 0.999), model=None, sizes=(3, 1028)),
+    dict(adamw=False, wd=0.1, grad_mul=None, step=1000, betas=(0.9, 0.95), model=torch.bfloat16, sizes=(1027, 3074)),
+    dict(adamw=True, wd=0.0, grad_mul=0.37, step=100000, betas=(0.9, 0.999), model=torch.float16, sizes=(4, 1023)),
+    dict(adamw=False, wd=0.0, grad_mul=None, step=2, betas=(0.9, 0.95), model=None, sizes=(1024, 1027)),
+    dict(adamw=True, wd=0.1, grad_mul=None, step=1000, betas=(0.9, 0.999), model=None, sizes=(5, 3074)),
+)
+ADAM_CASES = tuple((n, ADAM_GEOMETRY_MODE) for n in ADAM_SIZES) + tuple(
+    (n, {k: v for k, v in md.items() if k != "sizes"}) for md in ADAM_MODES for n in md["sizes"])
+ADAM_MUTATIONS = ("eps_dropped", "eps_in_sqrt", "no_bc2", "bc_swapped", "decay_step_size", "modes_swapped",
+                  "grad_mul_on_l2", "v_raw_grad")
+
+
+def f32_value(x) -> float:
+    """x rounded to fp32, as a Python float: the value a kernel receives for a ``float`` argument."""
+    return float(torch.tensor(x, dtype=torch.float32))
+
+
+def adam_kind(adamw: bool) -> str:
+    return "mixed" if adamw else "aligned"
+
+
+def adam_case(n, kind, seed=41):
+    """p, g, m, v (fp32, CPU generator) for one Adam step.
+      * g = sign * 10^U(-12, 3): with eps = 1e-8 the smallest gradients have sqrt(v) << eps (the
+        update is m / eps, so eps dropped or moved is an O(1) error there) and the largest do not see
+        eps at all. |g| >= 1e-12 keeps g * grad_mul, (1 - beta1) g and even (1 - beta2) (g grad_mul)^2
+        (>= 1e-28) far above the fp32 denormal range (1.2e-38): no term depends on flush-to-zero.
+      * p = sign' * 10^U(-4, 2).
+      * exact zeros: one element in ten has g = 0, one in ten p = 0, one in ten both (such an
+        element must stay exactly 0: the alignment padding of the flat buffers relies on it).
+      * m, v: the float64 moments after two warm-up steps on gradients g * U(0.5, 2), so m has g's
+        sign and m' = beta1 m + (1 - beta1) g does not cancel. A cancelling m' has an unbounded
+        relative error in fp32 whatever the kernel does; a criterion that had to allow for it could
+        not judge m' or the step p' - p relatively.
+      * kind "mixed": the sign of p is independent of g's (decoupled decay and update may cancel in
+        p' - p; both are then far below eps32 |p|, which the criterion's first term covers).
+        kind "aligned": p has g's sign, for L2 mode, where g * grad_mul + wd * p must not cancel
+        for the same reason as m'."""
+    assert kind in ("mixed", "aligned"), kind
+    gen = torch.Generator().manual_seed(seed + 7919 * (kind == "aligned"))
+
+    def logu(lo, hi):
+        return torch.pow(10.0, lo + (hi - lo) * torch.rand(n, generator=gen, dtype=torch.float64))
+
+    def sign():
+        return torch.randint(0, 2, (n,), generator=gen).double() * 2.0 - 1.0
+
+    sg = sign()
+    g = sg * logu(-12.0, 3.0)
+    p = (sg if kind == "aligned" else sign()) * logu(-4.0, 2.0)
+    z = torch.randint(0, 10, (n,), generator=gen)
+    g[(z == 0) | (z == 1)] = 0.0
+    p[(z == 1) | (z == 2)] = 0.0
+    g = g.float()
+    m = torch.zeros(n, dtype=torch.float64)
+    v = torch.zeros(n, dtype=torch.float64)
+    for step in (1, 2):
+        gw = (g.double() * (0.5 + 1.5 * torch.rand(n, generator=gen, dtype=torch.float64))).float()
+        _, m, v = adam_ref(p, gw, m, v, lr=0.0, b1=0.9, b2=0.95, eps=ADAM_EPS, wd=0.0, step=step, adamw=True)
+    return {"p": p.float(), "g": g, "m": m.float(), "v": v.float()}
+
+
+def adam_ref(p, g, m, v, *, lr, b1, b2, eps, wd, step, adamw, grad_mul=None, mutate=None):
+    """float64 Adam (L2 form: g + wd p into the moments) / AdamW (decoupled: p -= lr wd p) step,
+    textbook form; returns p', m', v'. The hyperparameters are the fp32 values the kernel is given
+    (lr, betas, eps, wd rounded to fp32 first: 1 - fp32(0.999) differs from 0.001 by 1.3e-5); the
+    bias corrections 1 - beta^step come from the unrounded betas, which is the binding's definition.
+    ``grad_mul`` is used as given. ``mutate`` (one of ADAM_MUTATIONS) breaks one term."""
+    assert mutate is None or mutate in ADAM_MUTATIONS, mutate
+    lr, b1f, b2f, eps, wd = (f32_value(x) for x in (lr, b1, b2, eps, wd))
+    gm = 1.0 if grad_mul is None else float(grad_mul)
+    bc1, bc2 = 1.0 - b1 ** step, 1.0 - b2 ** step
+    if mutate == "bc_swapped":
+        bc1, bc2 = bc2, bc1
+    if mutate == "no_bc2":
+        bc2 = 1.0
+    if mutate == "modes_swapped":
+        adamw = not adamw
+    P, G, M, V = (t.detach().double() for t in (p, g, m, v))
+    gj, graw = G * gm, G
+    if not adamw:
+        gj = (G + wd * P) * gm if mutate == "grad_mul_on_l2" else gj + wd * P
+        graw = G + wd * P
+    M = b1f * M + (1.0 - b1f) * gj
+    gv = graw if mutate == "v_raw_grad" else gj
+    V = b2f * V + (1.0 - b2f) * gv * gv
+    if mutate == "eps_dropped":
+        denom = (V / bc2).sqrt()
+    elif mutate == "eps_in_sqrt":
+        denom = (V / bc2 + eps).sqrt()
+    else:
+        denom = (V / bc2).sqrt() + eps
+    if adamw:
+        P = P - (lr / bc1 if mutate == "decay_step_size" else lr) * wd * P
+    P = P - (lr / bc1) * (M / denom)
+    return P, M, V
+
+
+def adam_kernel_emulation(p, g, m, v, *, lr, b1, b2, eps, wd, step, adamw, grad_mul=None):
+    """adam_batch_kernel's step in fp32, one rounding per operation, in its order: gj = g * gm; the
+    L2 term gj += wd * p; m' = b1 m + (1 - b1) gj; v' = b2 v + ((1 - b2) gj) gj;
+    denom = sqrt(v') * rsqrt(bc2) + eps; p -= (lr * wd) * p (decoupled); p -= (lr / bc1) * (m' / denom).
+    bc1 and bc2 are computed in float64 and cast to fp32, as the binding does. (The compiler may
+    contract a multiply-add into one rounding; the tolerances' factor of 4 covers that.)"""
+    f32 = torch.float32
+
+    def c(x):
+        return torch.tensor(x, dtype=f32)
+
+    lr, b1f, b2f, eps, wd = (c(x) for x in (lr, b1, b2, eps, wd))
+    bc1, bc2 = c(1.0 - b1 ** step), c(1.0 - b2 ** step)
+    P, G, M, V = (t.detach().to(f32) for t in (p, g, m, v))
+    gj = G if grad_mul is None else G * c(grad_mul)
+    if not adamw:
+        gj = gj + wd * P
+    M = b1f * M + (c(1.0) - b1f) * gj
+    V = b2f * V + ((c(1.0) - b2f) * gj) * gj
+    denom = V.sqrt() * torch.rsqrt(bc2) + eps
+    upd = M / denom
+    if adamw:
+        P = P - (lr * wd) * P
+    P = P - (lr / bc1) * upd
+    return P, M, V
+
+
+def _worst_ratio(err, den, where=None):
+    """max over (selected) elements of err / den; 0 / 0 counts as 0, x / 0 and a non-finite err as inf."""
+    r = torch.where(err == 0, torch.zeros_like(err), err / den)
+    r = torch.where(torch.isfinite(err), r, torch.full_like(err, float("inf")))
+    if where is not None:
+        r = r[where]
+    return r.max().item() if r.numel() else 0.0
+
+
+def adam_errors(got, ref, p_old):
+    """The measured figures of one step (``got``, ``ref``: p', m', v'; ``p_old``: p before it):
+    m, v: largest relative error; p_a: largest |p' - ref| / (eps32 |ref|) over elements whose step
+    |ref - p| is below 2^-8 |ref| (there the arithmetic of the update contributes < 1e-2 of eps32 |ref|:
+    what is left is the rounding of the subtractions at p's magnitude); p_b: largest
+    |p' - ref| / |ref - p| over elements whose step is at least |ref| (p = 0 included: the error of
+    the update itself)."""
+    e32 = torch.finfo(torch.float32).eps
+    (pg, mg, vg), (pr, mr, vr) = ((t.detach().double().cpu() for t in x) for x in (got, ref))
+    dp = (pr - p_old.detach().double().cpu()).abs()
+    err = (pg - pr).abs()
+    return {"m": _worst_ratio((mg - mr).abs(), mr.abs()), "v": _worst_ratio((vg - vr).abs(), vr.abs()),
+            "p_a": _worst_ratio(err, e32 * pr.abs(), dp <= pr.abs() * 2.0 ** -8),
+            "p_b": _worst_ratio(err, dp, dp >= pr.abs())}
+
+
+def adam_excess(got, ref, p_old, tol=None):
+    """The Adam criterion: per output, the worst element's error over its bound (pass: every
+    value <= 1). m', v': |x - ref| <= tol |ref|. p': |p' - ref| <= p_a eps32 |ref| + p_b |ref - p|:
+    the step p' - p is judged to p_b of itself, not to a fraction of |p|, which would hide it. A
+    bound of 0 (an element with p = g = m = 0) demands an exact 0."""
+    tol = tol or ADAM_TOL
+    e32 = torch.finfo(torch.float32).eps
+    (pg, mg, vg), (pr, mr, vr) = ((t.detach().double().cpu() for t in x) for x in (got, ref))
+    dp = (pr - p_old.detach().double().cpu()).abs()
+    return {"m": _worst_ratio((mg - mr).abs(), tol["m"] * mr.abs()),
+            "v": _worst_ratio((vg - vr).abs(), tol["v"] * vr.abs()),
+            "p": _worst_ratio((pg - pr).abs(), tol["p_a"] * e32 * pr.abs() + tol["p_b"] * dp)}
+
+
+def adam_hyper(mode):
+    """The keyword arguments of ``adam_ref`` / ``adam_kernel_emulation`` for a mode of ADAM_MODES;
+    grad_mul is the fp32 value the kernel reads from its device scalar."""
+    gm = mode["grad_mul"]
+    return dict(lr=ADAM_LR, b1=mode["betas"][0], b2=mode["betas"][1], eps=ADAM_EPS, wd=mode["wd"], step=mode["step"],
+                adamw=mode["adamw"], grad_mul=None if gm is None else f32_value(gm))

@@ -385,3 +385,74 @@ def test_flash_criterion_rejects_wrong_gradient_rows(profile, dtype, causal):
     if profile != "very_low":
         true_max = N.flash_kernel_emulation(q, k, v, do, N.FLASH_SCALE, causal)
         assert N.flash_excess(true_max["dq"], emu["dq"], ref["dq"], dtype, fl["dq"])[0] > 1.0
+
+
+# ------------------------------------------------------------------------------- fused Adam
+
+def _adam_case_io(n, mode):
+    c = N.adam_case(n, N.adam_kind(mode["adamw"]))
+    return c, N.adam_hyper(mode)
+
+
+def _adam_id(case):
+    n, md = case
+    return (f"{n}-{'adamw' if md['adamw'] else 'l2'}-wd{md['wd']}-gm{md['grad_mul']}-t{md['step']}"
+            f"-b{md['betas'][1]}")
+
+
+def test_adam_emulation_within_a_quarter_of_the_tolerances():
+    """The measurement ADAM_TOL is sized from (4x the largest value seen here over every case of
+    the GPU test, see the comment beside it in _numerics.py): the kernel's fp32 operation order
+    against the float64 reference, under the criterion the GPU tests use. Elements with
+    p = g = m = 0 stay exactly 0 in the emulation too."""
+    worst = {"m": 0.0, "v": 0.0, "p_a": 0.0, "p_b": 0.0}
+    for n, mode in N.ADAM_CASES:
+        c, hy = _adam_case_io(n, mode)
+        ref = N.adam_ref(c["p"], c["g"], c["m"], c["v"], **hy)
+        emu = N.adam_kernel_emulation(c["p"], c["g"], c["m"], c["v"], **hy)
+        e = N.adam_errors(emu, ref, c["p"])
+        print(f"adam emulation {_adam_id((n, mode))}: " + " ".join(f"{k}={x:.3g}" for k, x in e.items()))
+        for k in worst:
+            worst[k] = max(worst[k], e[k])
+        ex = N.adam_excess(emu, ref, c["p"])
+        assert max(ex.values()) <= 0.25 * 1.01, (n, mode, ex)
+        dead = (c["p"] == 0) & (c["g"] == 0)
+        assert bool((c["m"][dead] == 0).all()) and bool((emu[0][dead] == 0).all()) and bool((ref[0][dead] == 0).all())
+    print("adam emulation, largest: " + " ".join(f"{k}={x:.3g}" for k, x in worst.items()))
+    for k in worst:                   # the constants are 4x the measurement, not more
+        assert 0.25 * N.ADAM_TOL[k] <= worst[k] * 1.07, (k, worst[k], N.ADAM_TOL[k])
+
+
+@pytest.mark.parametrize("mutation", N.ADAM_MUTATIONS)
+def test_adam_criterion_rejects_mutations(mutation):
+    """Each mutation of ``adam_ref`` (one term of the step wrong) is at least 10 tolerances outside
+    the criterion on at least one case of the GPU test, on which the emulation passes."""
+    caught = []
+    for n, mode in N.ADAM_CASES:
+        c, hy = _adam_case_io(n, mode)
+        ref = N.adam_ref(c["p"], c["g"], c["m"], c["v"], **hy)
+        bad = N.adam_excess(N.adam_ref(c["p"], c["g"], c["m"], c["v"], mutate=mutation, **hy), ref, c["p"])
+        if max(bad.values()) >= 10.0:
+            emu = N.adam_excess(N.adam_kernel_emulation(c["p"], c["g"], c["m"], c["v"], **hy), ref, c["p"])
+            assert max(emu.values()) <= 1.0, (n, mode, emu)
+            caught.append((_adam_id((n, mode)), max(bad.values())))
+    print(f"adam mutation {mutation}: rejected on {len(caught)} of {len(N.ADAM_CASES)} cases, "
+          f"worst excess {max((x for _, x in caught), default=0.0):.3g}")
+    assert caught, mutation
+
+
+def test_adam_criterion_rejects_a_stale_or_truncated_model_copy():
+    """The model copy is judged bit for bit against the kernel's own p' cast once (round to nearest
+    even). On the test's inputs and lr a copy of the previous p, and a truncated copy, differ from it
+    on a large share of the elements: the equality cannot pass by accident."""
+    n, mode = 3074, N.ADAM_MODES[0]
+    c, hy = _adam_case_io(n, mode)
+    p1 = N.adam_kernel_emulation(c["p"], c["g"], c["m"], c["v"], **hy)[0]
+    for dt in (torch.bfloat16, torch.float16):
+        good = p1.to(dt)
+        stale = c["p"].to(dt)
+        shift = 16 if dt == torch.bfloat16 else None
+        assert (good != stale).float().mean().item() > 0.1
+        if shift:
+            trunc = (p1.view(torch.int32) >> shift << shift).view(torch.float32).to(dt)
+            assert (good != trunc).float().mean().item() > 0.25
