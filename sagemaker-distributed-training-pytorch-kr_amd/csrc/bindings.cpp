@@ -153,7 +153,10 @@ std::vector<Tensor> bias_act_bwd(Tensor dy, Tensor x, OptT bias, int64_t act, bo
   if (want_dbias) {
     const int slices = smdt_bias_act_slices(rows, (int)N);
     part = torch::empty({slices, N}, x.options().dtype(at::kFloat));
-    dbias = dbias_acc ? acc_target(dbias_acc, N, "dbias_acc") : torch::empty({N}, x.options().dtype(at::kFloat));
+    // rows == 0 launches nothing: a fresh d(bias) is then the empty sum
+    dbias = dbias_acc ? acc_target(dbias_acc, N, "dbias_acc")
+                      : (rows > 0 ? torch::empty({N}, x.options().dtype(at::kFloat))
+                                  : torch::zeros({N}, x.options().dtype(at::kFloat)));
   }
   check(smdt_bias_act_bwd(dcode(x), (int)act, dy.data_ptr(), x.data_ptr(), optr(bias),
                           dx.data_ptr(), want_dbias ? part.data_ptr<float>() : nullptr,
@@ -528,6 +531,7 @@ void paced_copy(Tensor recv, Tensor send, int64_t blocks, int64_t ns) {
 void rope_(Tensor x, Tensor cos_t, Tensor sin_t, int64_t rot, int64_t pos_div, int64_t pos_mod,
            bool backward) {
   need_cuda(x, "x");
+  if (x.dim() == 3 && x.numel() == 0) return;  // nothing to rotate; an empty tensor's strides mean nothing
   TORCH_CHECK(x.dim() == 3 && x.stride(2) == 1, "rope: x must be [ntok, nh, d] with unit last stride");
   need_contig(cos_t, "cos");
   need_contig(sin_t, "sin");
@@ -858,6 +862,10 @@ void bias_grad(Tensor dy, Tensor out, bool accumulate) {
   need_contig(dy, "dy");
   const int64_t N = dy.size(-1), rows = dy.numel() / N;
   Tensor o = acc_target(out, N, "bias_grad out");
+  if (rows == 0) {  // nothing to launch: the empty sum
+    if (!accumulate) o.zero_();
+    return;
+  }
   const int slices = smdt_bias_act_slices(rows, (int)N);
   auto part = torch::empty({slices, N}, dy.options().dtype(at::kFloat));
   check(smdt_bias_grad(dcode(dy), dy.data_ptr(), rows, (int)N, part.data_ptr<float>(),

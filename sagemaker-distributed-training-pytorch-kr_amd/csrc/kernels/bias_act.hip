@@ -208,6 +208,10 @@ static int pf_slices(int64_t rows, int* rows_per_slice) {
 }
 
 static int act_slices(int64_t rows, int N, int* rows_per_slice) {
+  if (rows <= 0) {  // empty input: no slice (and no division by want = 0 below)
+    *rows_per_slice = 1;
+    return 0;
+  }
   int colblocks = (N / 8 + 255) / 256;
   int64_t want = (int64_t)1024 / colblocks;
   if (want < 1) want = 1;
@@ -228,7 +232,8 @@ extern "C" int smdt_bias_act_slices(int64_t rows, int N) {
 
 extern "C" hipError_t smdt_bias_act_fwd(int dtype, int act, const void* x, const void* bias,
                                         void* y, int64_t rows, int N, hipStream_t st) {
-  if (N % 8 != 0 || rows <= 0) return hipErrorInvalidValue;
+  if (N % 8 != 0) return hipErrorInvalidValue;
+  if (rows <= 0) return hipSuccess;  // empty input: nothing to launch (the binding zeroes a fresh d(bias))
   int rps;
   int slices = pf_slices(rows, &rps);
   dim3 grid((N / 8 + 255) / 256, slices);
@@ -246,7 +251,8 @@ extern "C" hipError_t smdt_bias_act_bwd(int dtype, int act, const void* dy, cons
                                         const void* bias, void* dx, float* partials,
                                         float* dbias, int64_t rows, int N, int accumulate,
                                         hipStream_t st) {
-  if (N % 8 != 0 || rows <= 0) return hipErrorInvalidValue;
+  if (N % 8 != 0) return hipErrorInvalidValue;
+  if (rows <= 0) return hipSuccess;  // empty input: nothing to launch (the binding zeroes a fresh d(bias))
   int rps;
   // with d(bias): the partials slab was sized by smdt_bias_act_slices (~1024 blocks)
   int slices = dbias ? act_slices(rows, N, &rps) : pf_slices(rows, &rps);
@@ -275,7 +281,8 @@ extern "C" hipError_t smdt_col_sum(const float* partials, int nslices, int N, fl
 
 extern "C" hipError_t smdt_bias_grad(int dtype, const void* dy, int64_t rows, int N,
                                      float* partials, float* out, int accumulate, hipStream_t st) {
-  if (N % 8 != 0 || rows <= 0) return hipErrorInvalidValue;
+  if (N % 8 != 0) return hipErrorInvalidValue;
+  if (rows <= 0) return hipSuccess;  // empty input: nothing to launch (the binding zeroes a fresh d(bias))
   int rps;
   int slices = act_slices(rows, N, &rps);
   dim3 grid((N / 8 + 255) / 256, slices);

@@ -239,6 +239,7 @@ extern "C" hipError_t smdt_ce_stats(int dtype, const void* logits, const int64_t
                                     float* row_max, float* row_sumexp, float* row_tgt,
                                     hipStream_t st) {
   if (V % 8 != 0 || Vvalid < 1 || Vvalid > V) return hipErrorInvalidValue;
+  if (rows <= 0) return hipSuccess;
   if (dtype == 1) hipLaunchKernelGGL(ce_stats_kernel<bf16>, dim3(rows), dim3(256), 0, st, (const bf16*)logits, target, rows, V, Vvalid, vstart, row_max, row_sumexp, row_tgt);
   else if (dtype == 2) hipLaunchKernelGGL(ce_stats_kernel<f16>, dim3(rows), dim3(256), 0, st, (const f16*)logits, target, rows, V, Vvalid, vstart, row_max, row_sumexp, row_tgt);
   else hipLaunchKernelGGL(ce_stats_kernel<float>, dim3(rows), dim3(256), 0, st, (const float*)logits, target, rows, V, Vvalid, vstart, row_max, row_sumexp, row_tgt);
@@ -250,6 +251,7 @@ extern "C" hipError_t smdt_ce_bwd(int dtype, const void* logits, const int64_t* 
                                   void* dlogits, int64_t rows, int V, int Vvalid,
                                   int64_t vstart, int64_t ignore_index, hipStream_t st) {
   if (V % 8 != 0 || Vvalid < 1 || Vvalid > V) return hipErrorInvalidValue;
+  if (rows <= 0) return hipSuccess;
   if (dtype == 1) hipLaunchKernelGGL(ce_bwd_kernel<bf16>, dim3(rows), dim3(256), 0, st, (const bf16*)logits, target, gmax, gsum, dloss, (bf16*)dlogits, rows, V, Vvalid, vstart, ignore_index);
   else if (dtype == 2) hipLaunchKernelGGL(ce_bwd_kernel<f16>, dim3(rows), dim3(256), 0, st, (const f16*)logits, target, gmax, gsum, dloss, (f16*)dlogits, rows, V, Vvalid, vstart, ignore_index);
   else hipLaunchKernelGGL(ce_bwd_kernel<float>, dim3(rows), dim3(256), 0, st, (const float*)logits, target, gmax, gsum, dloss, (float*)dlogits, rows, V, Vvalid, vstart, ignore_index);

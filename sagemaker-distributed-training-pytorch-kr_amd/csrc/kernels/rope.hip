@@ -101,6 +101,7 @@ extern "C" hipError_t smdt_rope(int dtype, void* x, int64_t ntok, int nh, int64_
                                 const float* sin_t, int pos_div, int pos_mod, int backward,
                                 hipStream_t st) {
   if (rot % 16 != 0) return hipErrorInvalidValue;
+  if (ntok <= 0 || nh <= 0) return hipSuccess;
   float sign = backward ? -1.f : 1.f;
   if (ntok <= 0x7FFFFFFF && (int64_t)nh * (rot / 16) >= 64) {   // one block per token
     const dim3 g((unsigned)ntok);

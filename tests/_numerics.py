@@ -971,3 +971,462 @@ def adam_hyper(mode):
     gm = mode["grad_mul"]
     return dict(lr=ADAM_LR, b1=mode["betas"][0], b2=mode["betas"][1], eps=ADAM_EPS, wd=mode["wd"], step=mode["step"],
                 adamw=mode["adamw"], grad_mul=None if gm is None else f32_value(gm))
+
+
+# ------------------------------------------------- loss, RoPE and bias-activation kernels
+#
+# cross_entropy.hip, rope.hip, bias_act.hip (and the row gather of transpose.hip), judged by
+# tests/test_pointwise_loss_gpu.py. Per op: a case builder, a float64 reference of the plain
+# operation, and an emulation that places the kernel's rounding points (fp32 arithmetic in the
+# kernel's order, the fp32 product x * log2 e inside the fast exponential, one rounding to the
+# storage type, d(bias) as the sum of the rounded dx). The emulations take ``mutate`` (one thing
+# wrong); test_numerics_sensitivity.py measures every tolerance below from the emulation and shows
+# that each criterion rejects each mutation.
+
+PL_DTYPES = (torch.bfloat16, torch.float16, torch.float32)
+_BF, _HF, _F32 = PL_DTYPES
+
+# Each tolerance is 4x the largest error of the op's emulation against its float64 reference over
+# the cases the GPU tests run (test_numerics_sensitivity.py measures them and asserts the factor).
+# Element errors are row-relative (``row_rel_err``), the loss is judged against max(1, |row max|)
+# (``ce_loss_err``), column sums against the sum over rows of |term| (``col_rel_err``).
+#   two-kernel CE, measured: loss bf16 1.56e-7, fp16 1.06e-7, fp32 1.64e-7 (the fp32 sum
+#     log S + M - x_t at M's magnitude); gradient (with ``pl_ce_ref``'s row floor) bf16 3.62e-3 (one
+#     rounding, 2^-8 of a row max just above a power of two), fp16 4.77e-4 (2^-11), fp32 3.61e-7
+PL_CE_TOL = {_BF: {"loss": 6.3e-7, "grad": 1.45e-2}, _HF: {"loss": 4.3e-7, "grad": 1.91e-3},
+             _F32: {"loss": 6.6e-7, "grad": 1.45e-6}}
+#   fused CE, measured: loss bf16 6.21e-8, fp16 6.86e-8; softmax - onehot and the local e = exp(x - m)
+#     bf16 2.52e-3, fp16 3.39e-4; the local sum (relative) bf16 1.93e-7, fp16 8.75e-8
+PL_CEF_TOL = {_BF: {"loss": 2.5e-7, "d": 1.01e-2, "sum": 7.8e-7}, _HF: {"loss": 2.75e-7, "d": 1.36e-3, "sum": 3.5e-7}}
+#   RoPE, measured: one rotation bf16 3.82e-3, fp16 4.72e-4, fp32 1.13e-7; forward then inverse (two
+#     roundings) bf16 6.49e-3, fp16 8.92e-4, fp32 2.37e-7
+PL_ROPE_TOL = {_BF: {"rot": 1.53e-2, "roundtrip": 2.6e-2}, _HF: {"rot": 1.89e-3, "roundtrip": 3.57e-3},
+               _F32: {"rot": 4.6e-7, "roundtrip": 9.5e-7}}
+#   bias + GeLU (both forms; y and dx), measured: bf16 3.54e-3, fp16 4.65e-4, fp32 1.63e-6 (dx of the
+#     tanh form at |z| ~ 5: 1 - s cancels and is multiplied by z (d0 + d1 z^2) ~ 30);
+#   saturated z (|z| >= 6), measured: bf16 1.09e-5, fp16 2.41e-4, fp32 9.87e-6 (dx of the erf form at
+#     z = -6: cdf = 0.5 (1 + erf) rounds to 0 where Phi(-6) = 1e-9, judged against the floor 1e-4);
+#   SwiGLU (y, d gate, d up), measured: bf16 3.33e-3, fp16 4.55e-4, fp32 2.22e-7
+PL_ACT_TOL = {_BF: {"gelu": 1.42e-2, "saturation": 4.4e-5, "swiglu": 1.34e-2},
+              _HF: {"gelu": 1.86e-3, "saturation": 9.7e-4, "swiglu": 1.82e-3},
+              _F32: {"gelu": 6.6e-6, "saturation": 4.0e-5, "swiglu": 8.9e-7}}
+#   d(bias) and bias_grad against the float64 column sum of the same rounded terms (+ the prefill
+#     when accumulating), measured 1.11e-7 (fp32, 5000 rows: slices of 5 rows, then 1000 slices)
+PL_COL_TOL = 4.5e-7
+
+
+def _c32(x):
+    return torch.tensor(x, dtype=torch.float32)
+
+
+def fast_exp(x):
+    """__expf: exp2 of the fp32 product x * log2 e."""
+    return torch.exp2(x * _c32(_LOG2E_F32))
+
+
+# ---- cross entropy
+
+PL_CE_V = (8, 520, 2048, 2056, 4104)       # a block's sweep is 256 threads x 8 columns = 2048
+PL_CE_ROWS = 37
+PL_CE_PROFILES = ("peaked", "ascending", "descending", "offset", "scattered_inf", "aligned_inf")
+# (V, vvalid (0: no padding), profile): every V peaked; each padding kind (inside the last vector,
+# a whole vector dropped, a single column) at one and two sweeps; each profile at 2056 and 4104
+PL_CE_CASES = tuple((V, 0, "peaked") for V in PL_CE_V) \
+    + tuple((V, vv, "peaked") for V in (520, 2056) for vv in (V - 1, V - 7, V - 8, 1)) + ((8, 7, "peaked"), (8, 1, "peaked")) \
+    + tuple((V, 0, p) for V in (2056, 4104) for p in PL_CE_PROFILES[1:]) + ((520, 513, "aligned_inf"), (2056, 2049, "ascending"))
+PL_CE_MUTATIONS = ("skip_vector", "pad_leak", "onehot_plus_1", "vstart_ignored")
+# (V, vvalid, shards): vocab-parallel use without a process group; slices of 1040 and 520 columns,
+# targets below, inside and above each slice; one case with padding in the last slice
+PL_CE_SHARD_CASES = ((2080, 0, 2), (2080, 0, 4), (2080, 2075, 4))
+# fused kernel: the edge of thread 1023's first vector and each NV (4 | 7 | 8) boundary
+PL_CEF_V = (8, 8184, 8192, 8200, 32768, 32776, 57344, 57352, 65536)
+
+
+def pl_ce_case(V, dtype, profile="peaked", vvalid=0, rows=PL_CE_ROWS, ignore_index=-100, seed=9):
+    """Logits [rows, V] in ``dtype``, targets (half the row's argmax over the valid columns, half a
+    random valid finite column, row 5 ignored) and an O(1) signed dloss. The padding columns
+    (>= vvalid) hold the row's LARGEST values, so padding that leaks into the sum is an O(1) error."""
+    assert profile in PL_CE_PROFILES, profile
+    g = torch.Generator().manual_seed(seed + V)
+    nv = vvalid or V
+    z = 8.0 * torch.randn(rows, V, generator=g)
+    if profile == "ascending":              # every online update meets a new maximum and rescales
+        z = z.sort(-1).values
+    elif profile == "descending":
+        z = z.sort(-1, descending=True).values
+    elif profile == "offset":               # a large common offset: exp(x - max) must not see it
+        z = 0.5 * z + (1.0e4 if dtype == torch.bfloat16 else 3.0e4)
+    elif profile == "scattered_inf":
+        hole = torch.rand(rows, V, generator=g) < 0.2
+        hole[:, 0] = False
+        z = z.masked_fill(hole, float("-inf"))
+    elif profile == "aligned_inf":          # thread 1's first vector is -inf only
+        assert V >= 24
+        z[:, 8:16] = float("-inf")
+    z[:, nv:] = z[:, :nv].amax(-1, keepdim=True) + 4.0
+    z = z.to(dtype)
+    zv = z[:, :nv].float()
+    tgt = zv.argmax(-1)
+    rnd = torch.multinomial(torch.isfinite(zv).float(), 1, generator=g)[:, 0]
+    tgt[1::2] = rnd[1::2]
+    if rows > 5:
+        tgt[5] = ignore_index
+    return z, tgt, torch.randn(rows, generator=g)
+
+
+def pl_ce_ref(logits, tgt, dl=None, vvalid=0, ignore_index=-100):
+    """float64 per-row loss and d(sum dl loss)/dlogits of the full row (dl None: ones, the fused
+    kernel's softmax - onehot). Columns >= vvalid are padding; an ignored row is all zeros. Also
+    returns the row max of the valid columns (what the loss is judged against) and the gradient's
+    ``row_floor``: |dl| max_j p_j. The kernels form p - 1 in fp32, so where the target is the argmax
+    of a peaked row the whole row cancels down to |dl| (1 - p_t) while p_t carries an absolute error
+    of eps32 p_t: such a row is judged against what p's accuracy can deliver, not against ~0."""
+    z = logits.detach().double().cpu()
+    tgt = tgt.cpu()
+    rows, V = z.shape
+    nv = vvalid or V
+    z[:, nv:] = float("-inf")
+    lse = torch.logsumexp(z, -1)
+    valid = tgt != ignore_index
+    t = torch.where(valid, tgt, torch.zeros_like(tgt))
+    loss = torch.where(valid, lse - z.gather(1, t[:, None])[:, 0], torch.zeros_like(lse))
+    grad = torch.exp(z - lse[:, None])
+    pmax = grad.amax(-1)
+    grad[torch.arange(rows), t] -= 1.0
+    scale = valid.double() if dl is None else dl.detach().double().cpu() * valid
+    return loss, grad * scale[:, None], z.amax(-1), pmax * scale.abs()
+
+
+def ce_loss_err(loss, ref, row_max) -> float:
+    """max over rows of |loss - ref| / max(1, |row max|): log S + M - x_t is an fp32 sum at M's magnitude."""
+    e = (loss.detach().double().cpu() - ref).abs() / row_max.abs().clamp_min(1.0)
+    return float("inf") if not bool(torch.isfinite(e).all()) else e.max().item()
+
+
+def _ce_merge(m, s, om, os_):
+    ninf = float("-inf")
+    nm = torch.maximum(m, om)
+    z = torch.zeros_like(s)
+    return nm, torch.where(m == ninf, z, s * fast_exp(m - nm)) + torch.where(om == ninf, z, os_ * fast_exp(om - nm))
+
+
+def ce_stats_emulation(lg, tgt, vstart=0, vvalid=0, mutate=None):
+    """ce_stats_kernel in fp32 in its order: thread i of 256 takes the 8-column vectors i, i + 256, ...
+    with an online (max, sum) pair (the sum rescaled by the fast exp of the old max minus the new),
+    the pairs merged by the wave butterfly and then the four waves in order. A vector that is -inf only,
+    met with m still -inf, makes s = NaN (exp(-inf - -inf)) and leaves m = -inf; every reader of s
+    tests m == -inf first and takes 0, so the NaN never leaves the thread. Returns (max, sumexp, target logit or 0)."""
+    ninf = float("-inf")
+    rows, V = lg.shape
+    nv = vvalid or V
+    x = lg.detach().float().cpu().clone()
+    tgt = tgt.cpu()
+    if mutate == "pad_leak":
+        nv_sum = V
+    else:
+        nv_sum = nv
+        x[:, nv:] = ninf
+    nvec = (nv_sum + 7) // 8
+    sweeps = (nvec + 255) // 256
+    xp = torch.full((rows, sweeps * 2048), ninf)
+    xp[:, :nvec * 8] = x[:, :nvec * 8]
+    xp = xp.view(rows, sweeps, 256, 8)
+    live = (torch.arange(sweeps * 256) < nvec).view(sweeps, 256)
+    if mutate == "skip_vector":             # the row's last live vector never enters the sum
+        live.view(-1)[nvec - 1] = False
+    m = torch.full((rows, 256), ninf)
+    s = torch.zeros(rows, 256)
+    for k in range(sweeps):
+        v = xp[:, k]
+        lm = v.amax(-1)
+        upd = live[k][None].expand(rows, 256)
+        nm = torch.maximum(m, lm)
+        acc = torch.zeros(rows, 256)
+        for j in range(8):
+            acc = acc + fast_exp(v[..., j] - nm)
+        sn = torch.where(m == ninf, torch.zeros_like(s), s * fast_exp(m - nm)) + acc
+        s, m = torch.where(upd, sn, s), torch.where(upd, nm, m)
+    m, s = m.view(rows, 4, 64), s.view(rows, 4, 64)
+    for o in (32, 16, 8, 4, 2, 1):
+        idx = torch.arange(64) ^ o
+        m, s = _ce_merge(m, s, m[..., idx], s[..., idx])
+    M, S = m[:, 0, 0], s[:, 0, 0]
+    for w in (1, 2, 3):
+        M, S = _ce_merge(M, S, m[:, w, 0], s[:, w, 0])
+    t = tgt - vstart
+    inr = (t >= 0) & (t < nv)
+    xt = lg.detach().float().cpu().gather(1, t.clamp(0, V - 1)[:, None])[:, 0]
+    return M, S, torch.where(inr, xt, torch.zeros_like(xt))
+
+
+def ce_combine_stats(stats):
+    """The shards' (max, sumexp, target logit) -> the row's, by ``_FusedCE.forward``'s formula."""
+    gmax = torch.stack([st[0] for st in stats]).amax(0)
+    se = sum(st[1] * torch.exp(st[0] - gmax) for st in stats)
+    return gmax, se, sum(st[2] for st in stats)
+
+
+def ce_loss_from_stats(gmax, se, tg, tgt, ignore_index=-100):
+    loss = torch.log(se) + gmax - tg
+    return torch.where(tgt == ignore_index, torch.zeros_like(loss), loss)
+
+
+def ce_bwd_emulation(lg, tgt, gmax, gsum, dl, vstart=0, vvalid=0, ignore_index=-100, mutate=None):
+    """ce_bwd_kernel: (fast_exp(x - M) * (1 / S) - [j == t]) * dloss in fp32, rounded once to lg's type."""
+    rows, V = lg.shape
+    nv = vvalid or V
+    x = lg.detach().float().cpu()
+    tgt = tgt.cpu()
+    g = torch.where(tgt == ignore_index, torch.zeros(rows), dl.detach().float().cpu())
+    p = fast_exp(x - gmax[:, None]) * (1.0 / gsum)[:, None]
+    if mutate != "pad_leak":
+        p[:, nv:] = 0.0
+    t = tgt - vstart + (1 if mutate == "onehot_plus_1" else 0)
+    hit = torch.arange(V)[None] == t[:, None]
+    return (torch.where(hit, p - 1.0, p) * g[:, None]).to(lg.dtype)
+
+
+def ce_shard_vvalid(nv, r, vl):
+    """Valid columns of shard r of width vl when the first nv global columns are valid (0: all)."""
+    vv = min(max(nv - r * vl, 0), vl)
+    assert vv > 0, "a vocab shard holds only padding"
+    return 0 if vv == vl else vv
+
+
+def ce_emulation(lg, tgt, dl, vvalid=0, ignore_index=-100, shards=1, mutate=None):
+    """``cross_entropy`` on ``shards`` vocab slices without a process group: per slice ce_stats with
+    vstart = r V / R, the statistics combined on the host, ce_bwd per slice with the global
+    statistics. Returns loss (fp32) and the concatenated gradient (lg's type)."""
+    V = lg.shape[1]
+    vl = V // shards
+    nv = vvalid or V
+    parts = []
+    for r in range(shards):
+        vs = 0 if mutate == "vstart_ignored" else r * vl
+        parts.append((lg[:, r * vl:(r + 1) * vl], vs, ce_shard_vvalid(nv, r, vl)))
+    stats = [ce_stats_emulation(x, tgt, vs, vv, mutate) for x, vs, vv in parts]
+    gmax, se, tg = ce_combine_stats(stats)
+    loss = ce_loss_from_stats(gmax, se, tg, tgt.cpu(), ignore_index)
+    grad = torch.cat([ce_bwd_emulation(x, tgt, gmax, se, dl, vs, vv, ignore_index, mutate) for x, vs, vv in parts], -1)
+    return loss, grad
+
+
+def ce_fused_emulation(lg, tgt, vvalid=0, ignore_index=-100, local=False, vstart=0):
+    """ce_fused_kernel: the row max first, S = sum fast_exp(x - M) in fp32, then in place
+    fast_exp(x - M) / S - onehot rounded once (0 on padding and ignored rows) and
+    loss = __logf(S) + M - x_t (log2 S * ln 2 in fp32). ``local``: e = fast_exp(x - M) rounded once
+    and stats [3, rows] = (M, S, target logit of this slice or 0)."""
+    rows, V = lg.shape
+    nv = vvalid or V
+    x = lg.detach().float().cpu()
+    tgt = tgt.cpu()
+    xv = x.clone()
+    xv[:, nv:] = float("-inf")
+    M = xv.amax(-1)
+    e = fast_exp(xv - M[:, None])
+    S = e.sum(-1)
+    t = tgt - vstart if local else tgt
+    ign = torch.zeros(rows, dtype=torch.bool) if local else tgt == ignore_index
+    inr = ~ign & (t >= 0) & (t < nv)
+    xt = torch.where(inr, x.gather(1, t.clamp(0, V - 1)[:, None])[:, 0], torch.zeros(rows))
+    if local:
+        return e.to(lg.dtype), torch.stack([M, S, xt])
+    inv = torch.where(ign, torch.zeros(rows), 1.0 / S)
+    hit = (torch.arange(V)[None] == t[:, None]) & ~ign[:, None]
+    p = e * inv[:, None]
+    loss = torch.where(ign, torch.zeros(rows), torch.log2(S) * _c32(0.6931471805599453) + M - xt)
+    return torch.where(hit, p - 1.0, p).to(lg.dtype), loss
+
+
+# ---- RoPE
+
+PL_ROPE_MUTATIONS = ("sin_sign", "pos_t_mod_s", "interleaved", "skip_last_group", "rotate_tail")
+# (nh, d, rot): grid-stride, the token-per-block boundary (nh * rot / 16 = 64), its second loop
+# trip (320 items), and partial rotary on both sides of the dispatch
+PL_ROPE_SHAPES = ((7, 128, 128), (8, 128, 128), (40, 128, 128), (3, 128, 16), (5, 128, 64), (16, 128, 64), (36, 80, 32))
+
+
+# base of the tests' tables: the slowest pair still turns by 4^-(1 - 2 / rot) >= 0.25 rad per
+# position, so a pair left unrotated is an O(0.25) error at every position >= 1 (with the usual
+# 10000 the last pairs turn by 1e-4 rad at the small positions a quick test uses: invisible)
+PL_ROPE_BASE = 4.0
+
+
+def rope_kernel_for(nh, rot):
+    return "tok" if nh * (rot // 16) >= 64 else "grid"
+
+
+def rope_ref(x, cos, sin, rot, pos_div, pos_mod, inverse=False, dtype=torch.float64, mutate=None):
+    """Rotate-half RoPE of x [ntok, nh, d] in ``dtype`` from the fp32 tables: token t has position
+    (t // pos_div) % pos_mod; elements [rot, d) pass through. float64: the reference (its gradient
+    for an upstream dy is the inverse rotation of dy); float32: the kernel's arithmetic (the
+    products and their difference / sum each rounded), see ``rope_kernel_emulation``."""
+    assert mutate is None or mutate in PL_ROPE_MUTATIONS, mutate
+    X = x.detach().to(dtype)
+    ntok, _, d = X.shape
+    half = rot // 2
+    t = torch.arange(ntok, device=x.device)
+    pos = t % pos_mod if mutate == "pos_t_mod_s" else (t // pos_div) % pos_mod
+    c = cos.to(x.device)[pos].to(dtype)[:, None, :]
+    s = sin.to(x.device)[pos].to(dtype)[:, None, :]
+    if inverse != (mutate == "sin_sign"):
+        s = -s
+    out = X.clone()
+    if mutate == "interleaved":
+        a, b = X[..., 0:rot:2], X[..., 1:rot:2]
+        out[..., 0:rot:2], out[..., 1:rot:2] = a * c - b * s, b * c + a * s
+        return out
+    a, b = X[..., :half], X[..., half:rot]
+    oa, ob = a * c - b * s, b * c + a * s
+    if mutate == "skip_last_group":
+        oa[..., half - 8:], ob[..., half - 8:] = a[..., half - 8:], b[..., half - 8:]
+    out[..., :half], out[..., half:rot] = oa, ob
+    if mutate == "rotate_tail" and rot < d:
+        hw = min(half, (d - rot) // 2)
+        ta, tb = X[..., rot:rot + hw], X[..., rot + hw:rot + 2 * hw]
+        out[..., rot:rot + hw] = ta * c[..., :hw] - tb * s[..., :hw]
+        out[..., rot + hw:rot + 2 * hw] = tb * c[..., :hw] + ta * s[..., :hw]
+    return out
+
+
+def rope_kernel_emulation(x, cos, sin, rot, pos_div, pos_mod, inverse=False, mutate=None):
+    """rope.hip's rounding points: fp32 products and sums, one rounding to x's type; [rot, d) untouched."""
+    return rope_ref(x, cos, sin, rot, pos_div, pos_mod, inverse, torch.float32, mutate).to(x.dtype)
+
+
+# ---- bias + GeLU, SwiGLU, bias gradient
+
+_GELU_K0, _GELU_K1 = 0.7978845608028654, 0.044715
+PL_ACT_ROWS = (1, 3, 4, 5, 9)                 # a partial-free launch gives a thread 4 rows: tails 1, 3, 0, 1, 1
+PL_ACT_N = (8, 2040, 2048, 2056)              # 2056: one live thread in a second column block
+PL_DBIAS_SHAPES = ((1, 8), (7, 8), (1025, 8), (5000, 8), (37, 2056))
+PL_ACT_MUTATIONS = ("no_bias", "act_swapped")
+PL_COL_MUTATIONS = ("last_row_dropped", "overwrite")
+
+
+def act_case(rows, N, dtype, seed=17, bias=True):
+    """x, dy ~ N(0, 1.5^2) / N(0, 1) and a bias ~ N(0, 1) (O(1): a dropped bias is an O(1) error)."""
+    g = torch.Generator().manual_seed(seed + rows + N)
+    x = (1.5 * torch.randn(rows, N, generator=g)).to(dtype)
+    dy = torch.randn(rows, N, generator=g).to(dtype)
+    return x, (torch.randn(N, generator=g).to(dtype) if bias else None), dy
+
+
+def gelu_saturation_case(dtype):
+    """One row of 8 equal values per z in +-6, +-12, +-40, +-1e4 (and +-65504 for fp16); dy = 1."""
+    zs = [6.0, 12.0, 40.0, 1.0e4] + ([65504.0] if dtype == torch.float16 else [])
+    z = torch.tensor([sg * v for v in zs for sg in (1.0, -1.0)])
+    x = z[:, None].expand(-1, 8).contiguous().to(dtype)
+    return x, torch.ones_like(x)
+
+
+def bias_act_ref(x, bias, dy, act, mutate=None):
+    """float64 GeLU(x + bias) (act 0: tanh form, 1: erf form) and dy * GeLU'(x + bias)."""
+    assert mutate is None or mutate in PL_ACT_MUTATIONS, mutate
+    z = x.detach().double().cpu()
+    if bias is not None and mutate != "no_bias":
+        z = z + bias.detach().double().cpu()
+    a = act ^ 1 if mutate == "act_swapped" else act
+    z.requires_grad_()
+    y = torch.nn.functional.gelu(z, approximate="tanh" if a == 0 else "none")
+    y.backward(dy.detach().double().cpu())
+    return y.detach(), z.grad
+
+
+def _gelu_sigmoid32(z, z2):
+    c0 = _c32(-2.0 * _GELU_K0 * _LOG2E_F32)
+    c1 = _c32(-2.0 * _GELU_K0 * _GELU_K1 * _LOG2E_F32)
+    return 1.0 / (1.0 + torch.exp2(z * (z2 * c1 + c0)))
+
+
+def bias_act_emulation(x, bias, dy, act):
+    """bias_act.hip in fp32 in its order, each of y and dx rounded once to x's type. act 0 is
+    activations.h's sigmoid form of the tanh GeLU: s = 1 / (1 + 2^(z (c0 + c1 z^2))), y = z s,
+    y' = (z s)(d0 + d1 z^2)(1 - s) + s. act 1: y = (0.5 z)(1 + erf(z / sqrt 2)),
+    y' = cdf + z pdf with pdf = 0.3989 * fast_exp((-0.5 z) z)."""
+    z = x.detach().float().cpu()
+    if bias is not None:
+        z = z + bias.detach().float().cpu()
+    g = dy.detach().float().cpu()
+    if act == 0:
+        z2 = z * z
+        s = _gelu_sigmoid32(z, z2)
+        y = z * s
+        d = ((z * s) * (z2 * _c32(6.0 * _GELU_K0 * _GELU_K1) + _c32(2.0 * _GELU_K0))) * (1.0 - s) + s
+    else:
+        er = torch.erf(z * _c32(0.7071067811865476))
+        y = (0.5 * z) * (1.0 + er)
+        d = 0.5 * (1.0 + er) + z * (_c32(0.3989422804014327) * fast_exp((-0.5 * z) * z))
+    return y.to(x.dtype), (g * d).to(x.dtype)
+
+
+def swiglu_case(rows, F, dtype, seed=19):
+    g = torch.Generator().manual_seed(seed + rows + F)
+    x = (1.5 * torch.randn(rows, 2 * F, generator=g)).to(dtype)
+    return x, torch.randn(rows, F, generator=g).to(dtype)
+
+
+def swiglu_ref(x, dy):
+    """float64 silu(gate) * up of x = [gate | up] and its gradient [d gate | d up]."""
+    xd = x.detach().double().cpu().requires_grad_()
+    g, u = xd.chunk(2, -1)
+    y = torch.nn.functional.silu(g) * u
+    y.backward(dy.detach().double().cpu())
+    return y.detach(), xd.grad
+
+
+def swiglu_emulation(x, dy):
+    """swiglu kernels in fp32 in their order: silu = g / (1 + fast_exp(-g)); backward
+    sg = 1 / (1 + fast_exp(-g)), d up = dy (g sg), d gate = (dy up)(sg (1 + g (1 - sg)))."""
+    g, u = x.detach().float().cpu().chunk(2, -1)
+    d = dy.detach().float().cpu()
+    y = (g / (1.0 + fast_exp(-g))) * u
+    sg = 1.0 / (1.0 + fast_exp(-g))
+    du = d * (g * sg)
+    dg = (d * u) * (sg * (1.0 + g * (1.0 - sg)))
+    return y.to(x.dtype), torch.cat([dg, du], -1).to(x.dtype)
+
+
+def bias_act_slices(rows, N):
+    """(slices, rows per slice) of the launches that write d(bias) partials: about 1024 blocks."""
+    colblocks = (N // 8 + 255) // 256
+    want = min(max(1024 // colblocks, 1), rows)
+    rps = (rows + want - 1) // want
+    return (rows + rps - 1) // rps, rps
+
+
+def col_sum_ref(t, prefill=None):
+    """float64 column sums of t [rows, N] (+ prefill) and the sums of |term| (+ |prefill|) they are
+    judged against."""
+    T = t.detach().double().cpu()
+    s, sc = T.sum(0), T.abs().sum(0)
+    if prefill is None:
+        return s, sc
+    return s + prefill.detach().double().cpu(), sc + prefill.detach().double().cpu().abs()
+
+
+def col_sum_emulation(t, prefill=None, mutate=None):
+    """The two-phase d(bias) reduce in fp32: each slice of ``bias_act_slices`` sums its rows in
+    order in a register, the slices are then summed, and the result overwrites the output or is
+    added to ``prefill`` (accumulate)."""
+    assert mutate is None or mutate in PL_COL_MUTATIONS, mutate
+    rows, N = t.shape
+    slices, rps = bias_act_slices(rows, N)
+    pad = torch.zeros(slices * rps, N)
+    pad[:rows] = t.detach().float().cpu()
+    if mutate == "last_row_dropped":        # the first slice stops one row early
+        pad[min(rps, rows) - 1] = 0.0
+    pad = pad.view(slices, rps, N)
+    acc = torch.zeros(slices, N)
+    for j in range(rps):
+        acc = acc + pad[:, j]
+    s = acc.sum(0)
+    return s if (prefill is None or mutate == "overwrite") else prefill.detach().float().cpu() + s
+
+
+def ce_local_ref(lg, vvalid=0):
+    """float64 e = exp(x - m) of the slice's valid columns (0 on padding) and its row sums."""
+    z = lg.detach().double().cpu()
+    z[:, (vvalid or z.shape[1]):] = float("-inf")
+    e = torch.exp(z - z.amax(-1, keepdim=True))
+    return e, e.sum(-1)

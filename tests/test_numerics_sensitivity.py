@@ -456,3 +456,207 @@ def test_adam_criterion_rejects_a_stale_or_truncated_model_copy():
         if shift:
             trunc = (p1.view(torch.int32) >> shift << shift).view(torch.float32).to(dt)
             assert (good != trunc).float().mean().item() > 0.25
+
+
+# ------------------------------------- loss, RoPE and bias-activation kernels (pointwise_loss)
+#
+# CPU side of tests/test_pointwise_loss_gpu.py: the emulations' errors under the GPU tests' criteria
+# (each tolerance constant of _numerics.py is 4x the figure printed here) and, per criterion, a twin
+# with one thing wrong that it rejects.
+
+PL_T = list(N.PL_DTYPES)
+PL_16 = PL_T[:2]
+_dtn = {torch.bfloat16: "bf16", torch.float16: "fp16", torch.float32: "fp32"}
+_ids = lambda ts: [_dtn[t] for t in ts]
+
+
+def _quarter(name, dtype, errs, tols):
+    print(f"{name} {_dtn.get(dtype, '')}: " + " ".join(f"{k}={v:.3g} (tol {tols[k]:.3g})" for k, v in errs.items()))
+    for k, v in errs.items():
+        assert v <= tols[k] / 4, f"{name} {k}: emulation error {v:.4g} > a quarter of {tols[k]:.4g}"
+
+
+def _ce_errs(dtype, V, vv, profile, shards=1, mutate=None):
+    lg, tgt, dl = N.pl_ce_case(V, dtype, profile, vv)
+    rl, rg, rmax, fl = N.pl_ce_ref(lg, tgt, dl, vv)
+    loss, grad = N.ce_emulation(lg, tgt, dl, vv, shards=shards, mutate=mutate)
+    if mutate is None:
+        assert (grad[:, vv or V:] == 0).all() and (grad[5] == 0).all() and loss[5] == 0
+    return N.ce_loss_err(loss, rl, rmax), N.row_rel_err(grad, rg, row_floor=fl)
+
+
+@pytest.mark.parametrize("dtype", PL_T, ids=_ids(PL_T))
+def test_pl_ce_emulation_within_a_quarter_of_the_tolerances(dtype):
+    e = {"loss": 0.0, "grad": 0.0}
+    for V, vv, prof, sh in [c + (1,) for c in N.PL_CE_CASES] + [(V, vv, "peaked", sh) for V, vv, sh in N.PL_CE_SHARD_CASES]:
+        el, eg = _ce_errs(dtype, V, vv, prof, sh)
+        e = {"loss": max(e["loss"], el), "grad": max(e["grad"], eg)}
+    _quarter("two-kernel CE", dtype, e, N.PL_CE_TOL[dtype])
+
+
+def test_pl_ce_aligned_inf_vector_does_not_reach_the_result():
+    """Columns 8..15 all -inf is thread 1's first vector, met with m = -inf: the thread's s becomes
+    NaN (exp(-inf - -inf)) while its m stays -inf, and every reader of s tests m == -inf first, so
+    loss and gradient equal the float64 reference. (Read as a defect at first; it is none.)"""
+    for dtype in PL_T:
+        for V, vv in ((520, 513), (2056, 0), (4104, 0)):
+            el, eg = _ce_errs(dtype, V, vv, "aligned_inf")
+            assert el <= N.PL_CE_TOL[dtype]["loss"] / 4 and eg <= N.PL_CE_TOL[dtype]["grad"] / 4, (dtype, V, el, eg)
+
+
+_CE_MUT_CASES = {"skip_vector": [(2056, 0, "ascending", 1), (2056, 2049, "ascending", 1)],
+                 "pad_leak": [(2056, 2055, "peaked", 1), (520, 512, "peaked", 1), (2080, 2075, "peaked", 4)],
+                 "onehot_plus_1": [(8, 0, "peaked", 1), (2056, 0, "peaked", 1)],
+                 "vstart_ignored": [(2080, 0, "peaked", 2), (2080, 0, "peaked", 4)]}
+
+
+@pytest.mark.parametrize("mutate", N.PL_CE_MUTATIONS)
+@pytest.mark.parametrize("dtype", PL_T, ids=_ids(PL_T))
+def test_pl_ce_criterion_rejects_each_mutation(dtype, mutate):
+    tol = N.PL_CE_TOL[dtype]
+    for V, vv, prof, sh in _CE_MUT_CASES[mutate]:
+        el, eg = _ce_errs(dtype, V, vv, prof, sh, mutate=mutate)
+        print(f"CE {mutate} {_dtn[dtype]} V={V} vv={vv} shards={sh}: loss {el:.3g} grad {eg:.3g}")
+        assert el > 2 * tol["loss"] or eg > 2 * tol["grad"]
+        assert eg > 2 * tol["grad"]        # the gradient criterion alone sees every one of them
+
+
+def _cef_cases():
+    return [(V, vv) for V in N.PL_CEF_V for vv in (0, V - 1, V - 8, 1) if 0 <= vv < V]
+
+
+@pytest.mark.parametrize("dtype", PL_16, ids=_ids(PL_16))
+def test_pl_ce_fused_emulation_within_a_quarter_of_the_tolerances(dtype):
+    e = {"loss": 0.0, "d": 0.0, "sum": 0.0}
+    for V, vv in _cef_cases():
+        lg, tgt, _ = N.pl_ce_case(V, dtype, "peaked", vv, rows=5)
+        tgt[2] = -100
+        rl, rd, rmax, fl = N.pl_ce_ref(lg, tgt, None, vv)
+        d, loss = N.ce_fused_emulation(lg, tgt, vv)
+        assert (d[:, vv or V:] == 0).all() and (d[2] == 0).all() and loss[2] == 0
+        e["loss"], e["d"] = max(e["loss"], N.ce_loss_err(loss, rl, rmax)), max(e["d"], N.row_rel_err(d, rd, row_floor=fl))
+        if V in (8200, 32776):
+            ee, st = N.ce_fused_emulation(lg, tgt, vv, local=True, vstart=V // 2)
+            re_, rs = N.ce_local_ref(lg, vv)
+            e["d"] = max(e["d"], N.row_rel_err(ee, re_))
+            e["sum"] = max(e["sum"], ((st[1].double() - rs).abs() / rs).max().item())
+    _quarter("fused CE", dtype, e, N.PL_CEF_TOL[dtype])
+
+
+_ROPE_LAYOUTS = (("sb", 3, 5, 5), ("bs", 1, 5, 9))     # name, pos_div, pos_mod = s, table rows
+
+
+def _rope_inputs(nh, d, rot, dtype, rows):
+    from smdt_amd.ops import functional as SF
+    g = torch.Generator().manual_seed(23 + nh + rot)
+    cos, sin = SF.rope_tables(rows, rot, base=N.PL_ROPE_BASE)
+    return torch.randn(15, nh, d, generator=g).to(dtype), cos, sin
+
+
+@pytest.mark.parametrize("dtype", PL_T, ids=_ids(PL_T))
+def test_pl_rope_emulation_within_a_quarter_of_the_tolerances(dtype):
+    e = {"rot": 0.0, "roundtrip": 0.0}
+    for nh, d, rot in N.PL_ROPE_SHAPES:
+        for _, pdiv, s, trows in _ROPE_LAYOUTS:
+            x, cos, sin = _rope_inputs(nh, d, rot, dtype, trows)
+            for inv in (False, True):
+                y = N.rope_kernel_emulation(x, cos, sin, rot, pdiv, s, inv)
+                assert torch.equal(y[..., rot:], x[..., rot:])
+                e["rot"] = max(e["rot"], N.row_rel_err(y, N.rope_ref(x, cos, sin, rot, pdiv, s, inv)))
+            back = N.rope_kernel_emulation(N.rope_kernel_emulation(x, cos, sin, rot, pdiv, s), cos, sin, rot, pdiv, s, True)
+            e["roundtrip"] = max(e["roundtrip"], N.row_rel_err(back, x.double()))
+    _quarter("RoPE", dtype, e, N.PL_ROPE_TOL[dtype])
+
+
+def test_pl_rope_reference_gradient_is_the_inverse_rotation():
+    """<R x, dy> = <x, R^T dy> in float64: what the autograd test of ``apply_rope`` relies on."""
+    x, cos, sin = _rope_inputs(5, 128, 64, torch.float32, 5)
+    dy = torch.randn(x.shape, generator=torch.Generator().manual_seed(1)).double()
+    lhs = (N.rope_ref(x, cos, sin, 64, 3, 5) * dy).sum()
+    rhs = (x.double() * N.rope_ref(dy, cos, sin, 64, 3, 5, inverse=True)).sum()
+    assert abs(lhs - rhs) <= 1e-12 * (x.double().abs() * dy.abs()).sum()
+
+
+@pytest.mark.parametrize("mutate", N.PL_ROPE_MUTATIONS)
+@pytest.mark.parametrize("dtype", PL_T, ids=_ids(PL_T))
+def test_pl_rope_criterion_rejects_each_mutation(dtype, mutate):
+    for nh, d, rot in ((7, 128, 128), (8, 128, 128), (5, 128, 64), (36, 80, 32)):
+        if mutate == "rotate_tail" and rot == d:
+            continue
+        x, cos, sin = _rope_inputs(nh, d, rot, dtype, 5)
+        bad = N.rope_kernel_emulation(x, cos, sin, rot, 3, 5, mutate=mutate)
+        if mutate == "rotate_tail":        # the tail is judged bitwise
+            assert not torch.equal(bad[..., rot:], x[..., rot:])
+            continue
+        err = N.row_rel_err(bad, N.rope_ref(x, cos, sin, rot, 3, 5))
+        print(f"RoPE {mutate} {_dtn[dtype]} nh={nh} d={d} rot={rot}: {err:.3g}")
+        assert err > 2 * N.PL_ROPE_TOL[dtype]["rot"]
+
+
+def _act_errs(x, b, dy, act, mutate=None):
+    y, dx = N.bias_act_emulation(x, b, dy, act)
+    ry, rdx = N.bias_act_ref(x, b, dy, act, mutate)
+    assert torch.isfinite(y).all() and torch.isfinite(dx).all()
+    return N.row_rel_err(y, ry), N.row_rel_err(dx, rdx)
+
+
+@pytest.mark.parametrize("dtype", PL_T, ids=_ids(PL_T))
+def test_pl_activation_emulations_within_a_quarter_of_the_tolerance(dtype):
+    e = {"gelu": 0.0, "saturation": 0.0, "swiglu": 0.0}
+    for act, k in ((0, "gelu"), (1, "gelu")):
+        for rows in N.PL_ACT_ROWS:
+            for n in N.PL_ACT_N:
+                for bias in (True, False):
+                    e[k] = max(e[k], *_act_errs(*N.act_case(rows, n, dtype, bias=bias), act))
+        e["saturation"] = max(e["saturation"], *_act_errs(N.gelu_saturation_case(dtype)[0], None, N.gelu_saturation_case(dtype)[1], act))
+    for rows in (1, 3):
+        for F in N.PL_ACT_N:
+            x, dy = N.swiglu_case(rows, F, dtype)
+            x[0, :8], x[0, 8:16] = 100.0, -100.0          # saturated gates
+            (y, dx), (ry, rdx) = N.swiglu_emulation(x, dy), N.swiglu_ref(x, dy)
+            assert torch.isfinite(y).all() and torch.isfinite(dx).all()
+            e["swiglu"] = max(e["swiglu"], N.row_rel_err(y, ry), N.row_rel_err(dx[:, :F], rdx[:, :F]),
+                              N.row_rel_err(dx[:, F:], rdx[:, F:]))
+    _quarter("activations", dtype, e, N.PL_ACT_TOL[dtype])
+
+
+@pytest.mark.parametrize("dtype", PL_T, ids=_ids(PL_T))
+def test_pl_activation_criterion_rejects_each_mutation(dtype):
+    """The bias dropped: rejected for every type. erf swapped with tanh (they differ by at most
+    4.7e-4): only the fp32 criterion can see it, and it does; bf16 and fp16 cannot."""
+    tol = N.PL_ACT_TOL[dtype]["gelu"]
+    for act in (0, 1):
+        x, b, dy = N.act_case(9, 2056, dtype)
+        ey, edx = _act_errs(x, b, dy, act, "no_bias")
+        assert ey > 2 * tol and edx > 2 * tol
+        ey, edx = _act_errs(x, b, dy, act, "act_swapped")
+        print(f"act {act} swapped {_dtn[dtype]}: y {ey:.3g} dx {edx:.3g} (tol {tol:.3g})")
+        if dtype == torch.float32:
+            assert ey > 2 * tol and edx > 2 * tol
+        else:
+            assert ey <= tol                   # within the 16-bit rounding: not distinguishable
+
+
+def _col_errs(rows, n, dtype, mutate=None):
+    x, b, dy = N.act_case(rows, n, dtype)
+    dx = N.bias_act_emulation(x, b, dy, 0)[1]
+    pre = 10.0 * torch.randn(n, generator=torch.Generator().manual_seed(rows))
+    ref, sc = N.col_sum_ref(dx)
+    refp, scp = N.col_sum_ref(dx, pre)
+    return (N.col_rel_err(N.col_sum_emulation(dx, None, mutate), ref, sc),
+            N.col_rel_err(N.col_sum_emulation(dx, pre, mutate), refp, scp))
+
+
+def test_pl_column_sum_emulation_within_a_quarter_of_the_tolerance():
+    e = {}
+    for dtype in PL_T:
+        e[_dtn[dtype]] = max(max(_col_errs(rows, n, dtype)) for rows, n in N.PL_DBIAS_SHAPES)
+    _quarter("d(bias)", None, e, dict.fromkeys(e, N.PL_COL_TOL))
+
+
+@pytest.mark.parametrize("rows,n", [(7, 8), (1025, 8), (5000, 8), (37, 2056)])
+def test_pl_column_sum_criterion_rejects_each_mutation(rows, n):
+    fresh, acc = _col_errs(rows, n, torch.bfloat16, "last_row_dropped")
+    assert fresh > 2 * N.PL_COL_TOL and acc > 2 * N.PL_COL_TOL, (fresh, acc)
+    fresh, acc = _col_errs(rows, n, torch.bfloat16, "overwrite")
+    assert fresh <= N.PL_COL_TOL and acc > 2 * N.PL_COL_TOL, (fresh, acc)
