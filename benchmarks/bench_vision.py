@@ -64,6 +64,9 @@ def main():
     p.add_argument("--fused-window-attn", type=int, default=0, choices=[0, 1],
                    help="Swin models: 1 = the fused window-attention kernel (csrc/kernels/window_attn.hip) "
                         "instead of the batched-GEMM op chain")
+    p.add_argument("--fused-bn", type=int, default=0, choices=[0, 1],
+                   help="ResNet models: 1 = BatchNorm (+ add) (+ ReLU) as one op on the fused kernels "
+                        "(csrc/kernels/batchnorm.hip) instead of MIOpen batch-norm and elementwise ops")
     p.add_argument("--optim", default="smdt", choices=["smdt", "torch"],
                    help="smdt: the hand-written fused Adam (optim.hip, device-side step count: "
                         "capturable) over the DDP's flat buffers; torch: torch.optim.Adam(fused)")
@@ -106,7 +109,12 @@ def main():
     dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
     torch.manual_seed(0)
     torch.backends.cudnn.benchmark = True
-    model = zoo.create(a.model, **({"fused_window_attention": True} if a.fused_window_attn else {}))
+    model_kwargs = {"fused_window_attention": True} if a.fused_window_attn else {}
+    if a.fused_bn:
+        if not a.model.startswith(("resnet", "resnext", "wide_resnet")):
+            raise SystemExit(f"--fused-bn 1: '{a.model}' is not a ResNet")
+        model_kwargs["fused_bn"] = True
+    model = zoo.create(a.model, **model_kwargs)
     zoo.reset_classifier(model, a.num_classes)
     mf = torch.channels_last if (a.channels_last and dev.type == "cuda") else torch.contiguous_format
     bucket = int(a.bucket_mb * 2 ** 20 / 4) if a.bucket_mb > 0 else "auto"
@@ -227,6 +235,7 @@ def main():
                        "augment": "prefetched (side stream)" if a.prefetch else "in line",
                        "hip_graph": graph_note,
                        "fused_window_attn": a.fused_window_attn,
+                       "fused_bn": a.fused_bn,
                        "backend": dist.get_backend() if dist.is_initialized() else None,
                        "ddp_bucket": {"elements": model.bucket_size, "count": len(model.buckets),
                                       "MB": round(model.bucket_size * 4 / 2 ** 20, 2)} if a.ddp == "smdt" else None},

@@ -78,6 +78,9 @@ def args_fn(argv=None):
     parser.add_argument("--fused-window-attn", type=str2bool, default=False,
                         help="Swin models: run the attention core between the qkv and proj linears as one "
                              "fused HIP kernel (csrc/kernels/window_attn.hip); same parameters and checkpoints")
+    parser.add_argument("--fused-bn", type=str2bool, default=False,
+                        help="ResNet models: run every BatchNorm (+ residual add) (+ ReLU) as one op on the "
+                             "fused HIP kernels (csrc/kernels/batchnorm.hip); same parameters and checkpoints")
     return parser.parse_args(argv)
 
 
@@ -131,6 +134,11 @@ def train(args):
             model_kwargs["fused_window_attention"] = True
         else:
             print("=> --fused-window-attn ignored: '{}' is not a Swin model".format(args.model_name))
+    if args.fused_bn:
+        if args.model_name.startswith(("resnet", "resnext", "wide_resnet")):
+            model_kwargs["fused_bn"] = True
+        else:
+            print("=> --fused-bn ignored: '{}' is not a ResNet model".format(args.model_name))
     model = util.torch_model(args.model_name, num_classes=args.num_classes, pretrained=args.pretrained,
                              **model_kwargs)
     dev = args.device

@@ -1017,6 +1017,121 @@ std::vector<Tensor> window_attn_bwd(Tensor qkv, Tensor table, Tensor lse, Tensor
   return {dqkv, dtable};
 }
 
+// ------------------------------------------------------------------ BatchNorm + residual + ReLU (batchnorm.hip)
+// Activations are the [M, C] view of a channels-last tensor; per-channel tensors are fp32 [C]. The
+// limits live in smdt_bn_act_supported alone; workspaces come from the caching allocator and nothing
+// is read on the host, so the calls capture in a graph.
+bool bn_act_supported(int64_t dtype, int64_t M, int64_t C) { return smdt_bn_act_supported((int)dtype, M, C) != 0; }
+
+// threads, max tile groups, min rows a thread, target workgroups, finalize slab lanes, finalize channels
+std::vector<int64_t> bn_act_constants() {
+  std::vector<int64_t> v;
+  for (int i = 0; i < 6; ++i) v.push_back(smdt_bn_act_constant(i));
+  return v;
+}
+
+// -> tile_groups, ntiles, row_lanes, slab_rows, nslabs
+std::vector<int64_t> bn_act_plan(int64_t M, int64_t C) {
+  TORCH_CHECK(bn_act_supported(1 /* bf16 */, M, C), "bn_act_plan: M ", M, ", C ", C, " is not supported");
+  int tg, nt, rl, ns;
+  int64_t slab;
+  smdt_bn_act_plan(M, C, &tg, &nt, &rl, &slab, &ns);
+  return {tg, nt, rl, slab, ns};
+}
+
+static void bn_check_act(const Tensor& t, const Tensor& x, const char* n) {
+  need_contig(t, n);
+  TORCH_CHECK(t.sizes() == x.sizes() && t.dtype() == x.dtype() && t.device() == x.device(), "bn_act: '", n,
+              "' must have x's shape, dtype and device");
+}
+
+static float* bn_check_vec(const Tensor& t, const Tensor& x, const char* n) {
+  need_contig(t, n);
+  TORCH_CHECK(t.scalar_type() == at::kFloat && t.dim() == 1 && t.size(0) == x.size(1) && t.device() == x.device(),
+              "bn_act: '", n, "' must be fp32 [C] on x's device");
+  return t.data_ptr<float>();
+}
+
+static void bn_check_x(const Tensor& x) {
+  need_contig(x, "x");
+  TORCH_CHECK(x.dim() == 2, "bn_act: x must be the [M, C] view of a channels-last activation");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf, "bn_act: x must be bf16 or fp16, got ",
+              x.scalar_type());
+  TORCH_CHECK(bn_act_supported(dcode(x), x.size(0), x.size(1)), "bn_act: unsupported M x C = ", x.size(0), " x ",
+              x.size(1), " (smdt_bn_act_supported: C a multiple of 8)");
+}
+
+static Tensor bn_workspace(const Tensor& x) {
+  int tg, nt, rl, ns;
+  int64_t slab;
+  smdt_bn_act_plan(x.size(0), x.size(1), &tg, &nt, &rl, &slab, &ns);
+  return torch::empty({2, (int64_t)ns, x.size(1)}, x.options().dtype(at::kFloat));
+}
+
+// -> y, mean, invstd. training: batch statistics (mean / invstd returned for the backward) and the
+// running ones, when given, updated in place; else the running statistics normalise and mean /
+// invstd come back empty.
+std::vector<Tensor> bn_act_fwd(Tensor x, OptT res, Tensor gamma, Tensor beta, OptT running_mean, OptT running_var,
+                               bool training, double momentum, double eps, bool relu) {
+  bn_check_x(x);
+  const int64_t M = x.size(0), C = x.size(1);
+  if (res) bn_check_act(*res, x, "residual");
+  TORCH_CHECK(!res || relu, "bn_act: a residual without ReLU is not one of the kernel's modes");
+  const float* g = bn_check_vec(gamma, x, "gamma");
+  const float* b = bn_check_vec(beta, x, "beta");
+  float* rm = running_mean ? bn_check_vec(*running_mean, x, "running_mean") : nullptr;
+  float* rv = running_var ? bn_check_vec(*running_var, x, "running_var") : nullptr;
+  auto y = torch::empty_like(x);
+  Tensor mean, invstd;
+  if (training) {
+    TORCH_CHECK(M > 1, "bn_act: training needs more than one value per channel");
+    auto f32 = x.options().dtype(at::kFloat);
+    mean = torch::empty({C}, f32);
+    invstd = torch::empty({C}, f32);
+    auto ws = bn_workspace(x);
+    check(smdt_bn_stats(dcode(x), x.data_ptr(), ws.data_ptr<float>(), mean.data_ptr<float>(),
+                        invstd.data_ptr<float>(), rm, rv, M, C, (float)eps, (float)momentum, cur_stream()),
+          "bn_stats");
+    check(smdt_bn_apply(dcode(x), x.data_ptr(), optr(res), g, b, mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                        y.data_ptr(), M, C, relu ? 1 : 0, (float)eps, 0, cur_stream()),
+          "bn_apply");
+  } else {
+    TORCH_CHECK(rm && rv, "bn_act: eval mode needs the running statistics");
+    check(smdt_bn_apply(dcode(x), x.data_ptr(), optr(res), g, b, rm, rv, y.data_ptr(), M, C, relu ? 1 : 0, (float)eps,
+                        1, cur_stream()),
+          "bn_apply");
+  }
+  return {y, mean, invstd};
+}
+
+// y: the stored output when the forward had a ReLU (its sign is the mask). -> dx, dres (empty
+// without want_dres), dgamma, dbeta. training = false: mean / invstd are constants (eval mode).
+std::vector<Tensor> bn_act_bwd(Tensor dy, Tensor x, OptT y, Tensor gamma, Tensor mean, Tensor invstd, bool want_dres,
+                               bool training) {
+  bn_check_x(x);
+  bn_check_act(dy, x, "dy");
+  if (y) bn_check_act(*y, x, "y");
+  TORCH_CHECK(!want_dres || y, "bn_act: a residual without ReLU is not one of the kernel's modes");
+  const int64_t M = x.size(0), C = x.size(1);
+  const float* g = bn_check_vec(gamma, x, "gamma");
+  const float* mu = bn_check_vec(mean, x, "mean");
+  const float* is = bn_check_vec(invstd, x, "invstd");
+  auto f32 = x.options().dtype(at::kFloat);
+  auto dgamma = torch::empty({C}, f32), dbeta = torch::empty({C}, f32);
+  auto dx = torch::empty_like(x);
+  Tensor dres;
+  if (want_dres) dres = torch::empty_like(x);
+  auto ws = bn_workspace(x);
+  check(smdt_bn_bwd_reduce(dcode(x), dy.data_ptr(), x.data_ptr(), optr(y), mu, is, ws.data_ptr<float>(),
+                           dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), M, C, cur_stream()),
+        "bn_bwd_reduce");
+  check(smdt_bn_bwd_dx(dcode(x), dy.data_ptr(), x.data_ptr(), optr(y), g, mu, is, dgamma.data_ptr<float>(),
+                       dbeta.data_ptr<float>(), dx.data_ptr(), want_dres ? dres.data_ptr() : nullptr, M, C,
+                       training ? 1 : 0, cur_stream()),
+        "bn_bwd_dx");
+  return {dx, dres, dgamma, dbeta};
+}
+
 // ------------------------------------------------------------------ incremental decoding
 // q [B, nh, D], caches [B, cap, nkv, D], lens int32 [B] on the device (valid keys per sequence, the
 // new token included); max_len <= cap bounds the grid (0: cap). Everything the kernel does not
@@ -1938,6 +2053,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("window_attn_fwd", &window_attn_fwd, arg("qkv"), arg("table"), arg("window"), arg("shift"), arg("heads"));
   m.def("window_attn_bwd", &window_attn_bwd, arg("qkv"), arg("table"), arg("lse"), arg("dout"), arg("window"),
         arg("shift"), arg("heads"));
+  m.def("bn_act_supported", &bn_act_supported, arg("dtype"), arg("M"), arg("C"));
+  m.def("bn_act_constants", &bn_act_constants);
+  m.def("bn_act_plan", &bn_act_plan, arg("M"), arg("C"));
+  m.def("bn_act_fwd", &bn_act_fwd, arg("x"), arg("residual"), arg("gamma"), arg("beta"), arg("running_mean"),
+        arg("running_var"), arg("training"), arg("momentum"), arg("eps"), arg("relu"));
+  m.def("bn_act_bwd", &bn_act_bwd, arg("dy"), arg("x"), arg("y"), arg("gamma"), arg("mean"), arg("invstd"),
+        arg("want_dres"), arg("training"));
   m.def("ce_stats", &ce_stats);
   m.def("set_rng_step", &set_rng_step);
   m.def("adam_capturable", &adam_capturable);

@@ -287,6 +287,33 @@ hipError_t smdt_window_attn_bwd(int dtype, const void* qkv, const float* table, 
                                 const void* dout, void* dqkv, float* partials, float* dtable, int B, int ph,
                                 int pw, int heads, int ws, int shift, hipStream_t st);
 
+// batchnorm.hip: BatchNorm (+ residual) (+ ReLU) on channels-last activations seen as [M, C] (bf16 / fp16,
+// C % 8 == 0, 16-byte aligned); gamma / beta / statistics / dgamma / dbeta fp32 [C]. The grid of a shape
+// comes from smdt_bn_act_plan (tile_groups x 8 channels a workgroup, 256 / tile_groups row lanes, slabs of
+// slab_rows rows); ws is fp32 scratch of 2 * nslabs * C elements. Modes: plain, ReLU, residual + ReLU.
+// smdt_bn_act_constant: 0 threads, 1 max tile groups, 2 min rows a thread, 3 target workgroups,
+// 4 finalize slab lanes, 5 finalize channels. Anything unsupported returns hipErrorInvalidValue unlaunched.
+int smdt_bn_act_supported(int dtype, int64_t M, int64_t C);
+void smdt_bn_act_plan(int64_t M, int64_t C, int* tile_groups, int* ntiles, int* row_lanes, int64_t* slab_rows,
+                      int* nslabs);
+int smdt_bn_act_constant(int which);
+// mean, invstd = rsqrt(biased var + eps) of x's columns; running_mean / running_var (null: none) move by
+// momentum towards the mean and the unbiased variance (M >= 2 then)
+hipError_t smdt_bn_stats(int dtype, const void* x, float* ws, float* mean, float* invstd, float* running_mean,
+                         float* running_var, int64_t M, int64_t C, float eps, float momentum, hipStream_t st);
+// y = act(gamma stat (x - mean) + beta (+ res)); stat is invstd, or a variance with stat_is_var (eval mode)
+hipError_t smdt_bn_apply(int dtype, const void* x, const void* res, const float* gamma, const float* beta,
+                         const float* mean, const float* stat, void* y, int64_t M, int64_t C, int relu, float eps,
+                         int stat_is_var, hipStream_t st);
+// g = dy (y > 0), or dy with y null: dbeta = sum g, dgamma = sum g xhat
+hipError_t smdt_bn_bwd_reduce(int dtype, const void* dy, const void* x, const void* y, const float* mean,
+                              const float* invstd, float* ws, float* dgamma, float* dbeta, int64_t M, int64_t C,
+                              hipStream_t st);
+// dx = gamma invstd (g - dbeta / M - xhat dgamma / M) (training) or gamma invstd g; dres (null: none) = g
+hipError_t smdt_bn_bwd_dx(int dtype, const void* dy, const void* x, const void* y, const float* gamma,
+                          const float* mean, const float* invstd, const float* dgamma, const float* dbeta, void* dx,
+                          void* dres, int64_t M, int64_t C, int training, hipStream_t st);
+
 // gemm_tn.hip: C[M, N] = A[M, K] . B[N, K]^T (16-bit in / out, fp32 accumulate) with an epilogue:
 // epi 0 none, 1 + bias[n], 2 C = pre-activation and C2 = gelu_tanh(C + bias[n]) (bias_gelu fusion),
 // 3 C = product * gelu_tanh'(aux + bias[n]) (fc2 dgrad + GeLU backward; aux = pre-activation [M, N]).

@@ -17,6 +17,8 @@ from typing import List, Optional, Type, Union
 import torch
 import torch.nn as nn
 
+from ..ops import functional as Fn
+
 
 def conv3x3(i, o, stride=1, groups=1, dilation=1):
     return nn.Conv2d(i, o, 3, stride=stride, padding=dilation, groups=groups, bias=False, dilation=dilation)
@@ -26,11 +28,28 @@ def conv1x1(i, o, stride=1):
     return nn.Conv2d(i, o, 1, stride=stride, bias=False)
 
 
+def bn_act(bn: nn.BatchNorm2d, x, residual=None, relu=True):
+    """``relu(bn(x) + residual)`` through ``batch_norm_act`` on the module's tensors (the module
+    stays the holder of parameters and buffers); counts the batch as ``bn`` itself would."""
+    if bn.training and bn.track_running_stats:
+        bn.num_batches_tracked.add_(1)
+    return Fn.batch_norm_act(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.training, bn.momentum,
+                             bn.eps, residual=residual, relu=relu)
+
+
+def _fused_identity(block, x):
+    if block.downsample is None:
+        return x
+    return bn_act(block.downsample[1], block.downsample[0](x), relu=False)
+
+
 class BasicBlock(nn.Module):
     expansion = 1
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, base_width=64, dilation=1):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, base_width=64, dilation=1,
+                 fused_bn=False):
         super().__init__()
+        self.fused_bn = fused_bn
         self.conv1 = conv3x3(inplanes, planes, stride)
         self.bn1 = nn.BatchNorm2d(planes)
         self.relu = nn.ReLU(inplace=True)
@@ -39,6 +58,9 @@ class BasicBlock(nn.Module):
         self.downsample = downsample
 
     def forward(self, x):
+        if self.fused_bn:
+            out = bn_act(self.bn1, self.conv1(x))
+            return bn_act(self.bn2, self.conv2(out), residual=_fused_identity(self, x))
         idt = x
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.bn2(self.conv2(out))
@@ -50,8 +72,10 @@ class BasicBlock(nn.Module):
 class Bottleneck(nn.Module):
     expansion = 4
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, base_width=64, dilation=1):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, base_width=64, dilation=1,
+                 fused_bn=False):
         super().__init__()
+        self.fused_bn = fused_bn
         width = int(planes * (base_width / 64.0)) * groups
         self.conv1 = conv1x1(inplanes, width)
         self.bn1 = nn.BatchNorm2d(width)
@@ -63,6 +87,10 @@ class Bottleneck(nn.Module):
         self.downsample = downsample
 
     def forward(self, x):
+        if self.fused_bn:
+            out = bn_act(self.bn1, self.conv1(x))
+            out = bn_act(self.bn2, self.conv2(out))
+            return bn_act(self.bn3, self.conv3(out), residual=_fused_identity(self, x))
         idt = x
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.relu(self.bn2(self.conv2(out)))
@@ -74,8 +102,11 @@ class Bottleneck(nn.Module):
 
 class ResNet(nn.Module):
     def __init__(self, block: Type[Union[BasicBlock, Bottleneck]], layers: List[int], num_classes=1000,
-                 zero_init_residual=False, groups=1, width_per_group=64):
+                 zero_init_residual=False, groups=1, width_per_group=64, fused_bn=False):
         super().__init__()
+        # fused_bn: every BatchNorm2d (+ add) (+ ReLU) runs as one batch_norm_act op; the modules,
+        # state_dict keys and init are the same either way
+        self.fused_bn = fused_bn
         self.inplanes = 64
         self.groups, self.base_width = groups, width_per_group
         self.conv1 = nn.Conv2d(3, 64, kernel_size=7, stride=2, padding=3, bias=False)
@@ -106,14 +137,16 @@ class ResNet(nn.Module):
         if stride != 1 or self.inplanes != planes * block.expansion:
             down = nn.Sequential(conv1x1(self.inplanes, planes * block.expansion, stride),
                                  nn.BatchNorm2d(planes * block.expansion))
-        layers = [block(self.inplanes, planes, stride, down, self.groups, self.base_width)]
+        layers = [block(self.inplanes, planes, stride, down, self.groups, self.base_width, fused_bn=self.fused_bn)]
         self.inplanes = planes * block.expansion
         for _ in range(1, blocks):
-            layers.append(block(self.inplanes, planes, groups=self.groups, base_width=self.base_width))
+            layers.append(block(self.inplanes, planes, groups=self.groups, base_width=self.base_width,
+                                fused_bn=self.fused_bn))
         return nn.Sequential(*layers)
 
     def forward(self, x):
-        x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
+        stem = bn_act(self.bn1, self.conv1(x)) if self.fused_bn else self.relu(self.bn1(self.conv1(x)))
+        x = self.maxpool(stem)
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         x = torch.flatten(self.avgpool(x), 1)
         return self.fc(x)

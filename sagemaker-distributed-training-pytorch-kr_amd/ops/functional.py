@@ -769,6 +769,187 @@ def window_attention(qkv, table, window: int, shift: int, num_heads: int):
 
 
 # --------------------------------------------------------------------------------------------
+# BatchNorm2d (+ residual add) (+ ReLU) in one op for the ResNets (csrc/kernels/batchnorm.hip).
+#
+# The ReLU's backward mask is the sign of the stored output, g = dy * (y > 0): y is alive anyway as
+# the next convolution's input, so no mask tensor is kept. batch_norm_act_ref is the definition.
+
+
+def batch_norm_act_backward_ref(dy, x, y, gamma, mean, invstd, training: bool):
+    """Backward of ``batch_norm_act_ref`` from saved tensors: ``y`` is the stored output when the
+    forward had a ReLU, else None. Returns (dx, g, dgamma, dbeta) in the compute type (fp32, or
+    float64 for float64 ``x``); g is the gradient of the residual."""
+    ct = torch.float64 if x.dtype == torch.float64 else torch.float32
+    sh = (1, -1, 1, 1)
+    g = dy.to(ct)
+    if y is not None:
+        g = g * (y > 0)
+    xhat = (x.to(ct) - mean.to(ct).view(sh)) * invstd.to(ct).view(sh)
+    dbeta = g.sum((0, 2, 3))
+    dgamma = (g * xhat).sum((0, 2, 3))
+    dx = g
+    if training:
+        M = x.numel() // x.shape[1]
+        dx = g - dbeta.view(sh) / M - xhat * (dgamma.view(sh) / M)
+    return dx * (gamma.to(ct) * invstd.to(ct)).view(sh), g, dgamma, dbeta
+
+
+class _BNActRef(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, residual, gamma, beta, running_mean, running_var, training, momentum, eps, relu):
+        ct = torch.float64 if x.dtype == torch.float64 else torch.float32
+        sh = (1, -1, 1, 1)
+        xf = x.to(ct)
+        if training:
+            M = x.numel() // x.shape[1]
+            mean = xf.mean((0, 2, 3))
+            var = (xf - mean.view(sh)).square().mean((0, 2, 3))
+            if running_mean is not None:
+                running_mean.mul_(1 - momentum).add_(mean.to(running_mean.dtype), alpha=momentum)
+            if running_var is not None:
+                running_var.mul_(1 - momentum).add_((var * (M / (M - 1))).to(running_var.dtype), alpha=momentum)
+        else:
+            mean, var = running_mean.to(ct), running_var.to(ct)
+        invstd = torch.rsqrt(var + eps)
+        y = (xf - mean.view(sh)) * invstd.view(sh) * gamma.to(ct).view(sh) + beta.to(ct).view(sh)
+        if residual is not None:
+            y = y + residual.to(ct)
+        if relu:
+            y = y.relu()
+        y = y.to(x.dtype)
+        ctx.save_for_backward(x, y if relu else None, gamma, mean, invstd)
+        ctx.args = (training, residual is not None, beta.dtype)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, y, gamma, mean, invstd = ctx.saved_tensors
+        training, has_res, bdtype = ctx.args
+        dx, g, dgamma, dbeta = batch_norm_act_backward_ref(dy, x, y, gamma, mean, invstd, training)
+        return (dx.to(x.dtype), g.to(x.dtype) if has_res else None, dgamma.to(gamma.dtype), dbeta.to(bdtype),
+                None, None, None, None, None, None)
+
+
+def _bn_act_check(x, running_mean, running_var, training, momentum, residual):
+    if x.dim() != 4:
+        raise ValueError(f"batch_norm_act: x must be [N, C, H, W], got {tuple(x.shape)}")
+    if momentum is None:
+        raise ValueError("batch_norm_act: momentum=None (cumulative moving average) is not supported; "
+                         "give the running statistics a momentum")
+    if not training and (running_mean is None or running_var is None):
+        training = True     # no running statistics: batch statistics always, as nn.BatchNorm2d
+    if training and x.numel() // max(x.shape[1], 1) == 1:
+        raise ValueError(f"batch_norm_act: expected more than 1 value per channel when training, got input size "
+                         f"{tuple(x.shape)}")
+    if residual is not None:
+        fmt = lambda t: (t.permute(0, 2, 3, 1).is_contiguous(), t.is_contiguous())  # noqa: E731
+        if residual.shape != x.shape or residual.dtype != x.dtype or residual.dim() != 4 or fmt(residual) != fmt(x):
+            raise ValueError(f"batch_norm_act: the residual must have x's shape, dtype and memory format: x "
+                             f"{tuple(x.shape)} {x.dtype} strides {x.stride()}, residual {tuple(residual.shape)} "
+                             f"{residual.dtype} strides {residual.stride()}")
+    return training
+
+
+def batch_norm_act_ref(x, gamma, beta, running_mean, running_var, training: bool, momentum: float = 0.1,
+                       eps: float = 1e-5, residual=None, relu: bool = True):
+    """Torch twin and definition of ``batch_norm_act``: ``F.batch_norm`` arithmetic written out
+    (biased batch variance normalises, the unbiased one moves ``running_var``), then the residual
+    add, then ReLU; fp32 arithmetic (float64 for float64 operands), one rounding to x's dtype. The
+    backward masks by the stored output, g = dy * (y > 0)."""
+    training = _bn_act_check(x, running_mean, running_var, training, momentum, residual)
+    return _BNActRef.apply(x, residual, gamma, beta, running_mean, running_var, training, momentum, eps, relu)
+
+
+def batch_norm_act_supported(x, gamma, beta, running_mean=None, running_var=None, residual=None,
+                             relu: bool = True) -> bool:
+    """Whether batchnorm.hip takes these operands: a bf16 / fp16 GPU activation in channels_last
+    memory format with fp32 per-channel tensors, in one of its modes (plain, ReLU, residual + ReLU).
+    The shape limits live in the kernel file alone (smdt_bn_act_supported) and this asks it."""
+    code = {torch.bfloat16: 1, torch.float16: 2}.get(x.dtype)
+    if code is None or not x.is_cuda or x.dim() != 4 or not x.permute(0, 2, 3, 1).is_contiguous():
+        return False
+    if residual is not None and not relu:
+        return False
+    for t in (gamma, beta):
+        if t is None or not t.is_cuda or not t.is_floating_point():
+            return False
+    for t in (running_mean, running_var):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            return False
+    C = x.shape[1]
+    return _ext.available() and bool(_ext.ext().bn_act_supported(code, x.numel() // max(C, 1), C))
+
+
+def bn_act_constants() -> dict:
+    """The kernels' geometry constants: threads of a workgroup, the most channel groups (of 8
+    channels) in a channel tile, the rows a thread walks at least before a slab is split, the
+    workgroup count the plan aims at, and the finalize kernels' slab lanes and channels."""
+    c = [int(v) for v in _ext.ext().bn_act_constants()]
+    return dict(zip(("threads", "max_tile_groups", "min_rows", "target_blocks", "finalize_lanes",
+                     "finalize_channels"), c))
+
+
+def bn_act_plan(M: int, C: int) -> dict:
+    """How the kernels split [M, C]: channel groups per tile, tiles, row lanes of a workgroup, rows
+    of a slab and slabs (the grid is tiles x slabs)."""
+    tg, nt, rl, slab, ns = (int(v) for v in _ext.ext().bn_act_plan(int(M), int(C)))
+    return {"tile_groups": tg, "tiles": nt, "row_lanes": rl, "slab_rows": slab, "slabs": ns}
+
+
+def _nhwc_rows(t):
+    return t.permute(0, 2, 3, 1).reshape(-1, t.shape[1])    # a view: t is channels_last
+
+
+def _nchw_view(t2, like):
+    N, C, H, W = like.shape
+    return t2.view(N, H, W, C).permute(0, 3, 1, 2)
+
+
+class _BNAct(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, residual, gamma, beta, running_mean, running_var, training, momentum, eps, relu):
+        gf = gamma.detach().float().contiguous()
+        bf = beta.detach().float().contiguous()
+        x2 = _nhwc_rows(x)
+        r2 = None if residual is None else _nhwc_rows(residual)
+        y2, mean, invstd = _ext.ext().bn_act_fwd(x2, r2, gf, bf, running_mean, running_var, training, momentum, eps,
+                                                 relu)
+        y = _nchw_view(y2, x)
+        if training:
+            ctx.save_for_backward(x, y if relu else None, gf, mean, invstd)
+        elif any(ctx.needs_input_grad):     # the statistics are constants; copies, as a later step may move them
+            ctx.save_for_backward(x, y if relu else None, gf, running_mean.clone(), running_var.clone())
+        ctx.args = (training, residual is not None, gamma.dtype, beta.dtype, eps)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, y, gf, mean, stat = ctx.saved_tensors
+        training, has_res, gdtype, bdtype, eps = ctx.args
+        invstd = stat if training else torch.rsqrt(stat + eps)
+        dy2 = _nhwc_rows(dy.contiguous(memory_format=torch.channels_last))
+        dx2, dres2, dgamma, dbeta = _ext.ext().bn_act_bwd(dy2, _nhwc_rows(x), None if y is None else _nhwc_rows(y),
+                                                          gf, mean, invstd, has_res, training)
+        return (_nchw_view(dx2, x), _nchw_view(dres2, x) if has_res else None, dgamma.to(gdtype), dbeta.to(bdtype),
+                None, None, None, None, None, None)
+
+
+def batch_norm_act(x, gamma, beta, running_mean, running_var, training: bool, momentum: float = 0.1,
+                   eps: float = 1e-5, residual=None, relu: bool = True):
+    """``relu(batch_norm(x) + residual)`` as one op (``residual`` and ``relu`` optional): x is
+    [N, C, H, W]; in training the batch statistics normalise and the running ones are updated in
+    place. A bf16 / fp16 GPU activation in ``channels_last`` format with C a multiple of 8 runs the
+    fused HIP kernels (two sweeps forward, two backward; under autocast a bf16 x is taken with its
+    fp32 parameters as they come); the CPU, fp32 / float64, NCHW-contiguous inputs, other C and
+    SMDT_DISABLE_KERNELS=1 run the torch twin, ``batch_norm_act_ref``. Refused by name: one value per
+    channel in training, ``momentum=None``, and a residual of another shape, dtype or memory format."""
+    training = _bn_act_check(x, running_mean, running_var, training, momentum, residual)
+    if _ext.use_kernels(x) and batch_norm_act_supported(x, gamma, beta, running_mean, running_var, residual, relu):
+        return _BNAct.apply(x, residual, gamma, beta, running_mean, running_var, training, momentum, eps, relu)
+    return _BNActRef.apply(x, residual, gamma, beta, running_mean, running_var, training, momentum, eps, relu)
+
+
+# --------------------------------------------------------------------------------------------
 # Rotary embedding
 
 
