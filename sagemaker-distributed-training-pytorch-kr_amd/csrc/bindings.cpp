@@ -417,6 +417,67 @@ std::vector<Tensor> fp8_quantize(Tensor x, Tensor scale, Tensor amax, int64_t fm
   return {q};
 }
 
+// ------------------------------------------------------------------ FP8-output producers
+// The forward of a norm or an activation whose consumer is an FP8 linear (delayed scaling): the
+// output leaves as q (float8_e4m3fn, the output's shape) = fp8_quantize(y, scale), amax merged in
+// place, with the 16-bit y beside it (keep16) or without it (then y comes back undefined / None).
+static void need_fp8_out(const Tensor& x, const Tensor& scale, const Tensor& amax, bool ok, const char* what,
+                         int64_t width) {
+  TORCH_CHECK(ok, what, ": the FP8-output form takes bf16 / fp16 rows of a width its *_fp8_supported function accepts, got ",
+              x.scalar_type(), " with ", width);
+  need_f32_slot(scale, x, "scale");
+  need_f32_slot(amax, x, "amax");
+}
+
+std::vector<Tensor> layernorm_fwd_fp8(Tensor x, OptT res, OptT bias, Tensor gamma, OptT beta, double eps,
+                                      double p_drop, int64_t seed, int64_t offset, bool rms, Tensor scale,
+                                      Tensor amax, bool keep16, OptT x2) {
+  need_contig(x, "x");
+  need_contig(gamma, "gamma");
+  const int64_t H = x.size(-1);
+  const int64_t rows = x.numel() / H;
+  TORCH_CHECK(gamma.numel() == H, "layernorm: gamma size mismatch");
+  need_fp8_out(x, scale, amax, H < (int64_t(1) << 31) && smdt_layernorm_fp8_supported(dcode(x), (int)H) != 0, "layernorm_fwd_fp8", H);
+  if (res) { need_contig(*res, "residual"); TORCH_CHECK(res->sizes() == x.sizes() && res->dtype() == x.dtype(), "layernorm: residual mismatch"); }
+  if (bias) { need_contig(*bias, "bias"); TORCH_CHECK(bias->numel() == H && bias->dtype() == gamma.dtype(), "layernorm: bias mismatch"); }
+  if (beta) { need_contig(*beta, "beta"); TORCH_CHECK(beta->numel() == H && beta->dtype() == gamma.dtype(), "layernorm: beta mismatch"); }
+  if (x2) { need_contig(*x2, "x2"); TORCH_CHECK(x2->sizes() == x.sizes() && x2->dtype() == x.dtype(), "layernorm: x2 mismatch"); }
+  Tensor y;
+  if (keep16) y = torch::empty_like(x);
+  auto q = torch::empty(x.sizes(), x.options().dtype(at::kFloat8_e4m3fn));
+  auto s = torch::empty_like(x);     // the norm's input, saved for the backward (as want_s)
+  auto f32 = x.options().dtype(at::kFloat);
+  auto mean = torch::empty({rows}, f32);
+  auto rstd = torch::empty({rows}, f32);
+  check(smdt_layernorm_fwd_fp8(dcode(x), dcode(gamma), x.data_ptr(), optr(res), optr(bias), gamma.data_ptr(),
+                               optr(beta), keep16 ? y.data_ptr() : nullptr, s.data_ptr(), mean.data_ptr<float>(),
+                               rstd.data_ptr<float>(), rows, (int)H, (float)eps, (float)p_drop, (uint64_t)seed,
+                               (uint64_t)offset, rms ? 1 : 0, optr(x2), q.data_ptr(), scale.data_ptr<float>(),
+                               amax.data_ptr<float>(), cur_stream()),
+        "layernorm_fwd_fp8");
+  return {y, s, mean, rstd, q};
+}
+
+// act: 0 = bias + GeLU-tanh, 1 = bias + GeLU-erf, 2 = SwiGLU (x = [gate | up], no bias) -> (y, q)
+std::vector<Tensor> act_fwd_fp8(Tensor x, OptT bias, int64_t act, Tensor scale, Tensor amax, bool keep16) {
+  need_contig(x, "x");
+  TORCH_CHECK(act >= 0 && act <= 2, "act_fwd_fp8: act must be 0, 1 or 2");
+  const int64_t W = x.size(-1);
+  TORCH_CHECK(act != 2 || (W % 2 == 0 && !bias), "act_fwd_fp8: SwiGLU takes an even last dim and no bias");
+  const int64_t N = act == 2 ? W / 2 : W, rows = x.numel() / W;
+  need_fp8_out(x, scale, amax, N < (int64_t(1) << 31) && smdt_act_fp8_supported(dcode(x), (int)N) != 0, "act_fwd_fp8", N);
+  if (bias) { need_contig(*bias, "bias"); TORCH_CHECK(bias->numel() == N && bias->dtype() == x.dtype(), "bias_act: bias mismatch"); }
+  auto sizes = x.sizes().vec();
+  sizes.back() = N;
+  Tensor y;
+  if (keep16) y = torch::empty(sizes, x.options());
+  auto q = torch::empty(sizes, x.options().dtype(at::kFloat8_e4m3fn));
+  check(smdt_act_fwd_fp8(dcode(x), (int)act, x.data_ptr(), optr(bias), keep16 ? y.data_ptr() : nullptr, q.data_ptr(),
+                         scale.data_ptr<float>(), amax.data_ptr<float>(), rows, (int)N, cur_stream()),
+        "act_fwd_fp8");
+  return {y, q};
+}
+
 // ------------------------------------------------------------------ MX (block-scaled) FP8
 // x [R, C] bf16 / fp16 -> the row form (q [R, C], s [R, C / 32]) and / or the column form
 // (qt [C, R], st [C, R / 32]: the quantisation of x^T) in float8_e4m3fn (fmt 0) or float8_e5m2
@@ -1986,6 +2047,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("transpose2d", &transpose2d);
   m.def("fp8_quantize", &fp8_quantize);
   m.def("fp8_update_scales", &fp8_update_scales);
+  m.def("layernorm_fwd_fp8", &layernorm_fwd_fp8, arg("x"), arg("res"), arg("bias"), arg("gamma"), arg("beta"),
+        arg("eps"), arg("p_drop"), arg("seed"), arg("offset"), arg("rms"), arg("scale"), arg("amax"),
+        arg("keep16"), arg("x2") = pybind11::none());
+  m.def("act_fwd_fp8", &act_fwd_fp8, arg("x"), arg("bias"), arg("act"), arg("scale"), arg("amax"), arg("keep16"));
   m.def("mx_quantize", &mx_quantize, arg("x"), arg("fmt"), arg("rows") = true, arg("cols") = false);
   m.def("gemm_mx", &gemm_mx, arg("a"), arg("sa"), arg("b"), arg("sb"), arg("bias") = pybind11::none(),
         arg("out_dtype") = 1, arg("max_blocks") = 0);

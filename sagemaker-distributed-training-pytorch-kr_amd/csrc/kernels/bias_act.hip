@@ -11,6 +11,7 @@
 
 #include "activations.h"
 #include "common.h"
+#include "fp8_round.h"
 #include "launchers.h"
 
 namespace smdt {
@@ -152,6 +153,98 @@ __global__ __launch_bounds__(256) void swiglu_bwd_kernel(const T* __restrict__ d
 }
 
 
+
+// FP8-output forward of the three activations (ACT 0 = bias + GeLU-tanh, 1 = bias + GeLU-erf over
+// x [rows, N]; 2 = SwiGLU over x [rows, 2N] = [gate | up]): y [rows, N] leaves as E4M3 bytes q for
+// the next linear's FP8 GEMM, with the 16-bit y beside it (KEEP) or without it. q is fp8_quantize's
+// function of the rounded 16-bit y (fp8_round.h) and the arithmetic before the rounding is that of
+// the 16-bit kernels above, so the bytes and the amax equal those of the two-pass chain.
+//
+// Work split as in bias_act_fwd_kernel: a thread owns 8 columns of a slice of kPF rows and has all
+// its loads in flight at once. 8 columns are only 8 bytes, so neighbouring lanes swap: of rows
+// (r, r + 1) the even lane takes the pair's 16 bytes of row r and the odd lane those of row r + 1
+// (one 16-byte store per lane per two rows; N % 16 == 0 keeps both lanes of a pair inside the row
+// and the stores aligned). A slice's odd last rows leave as 8 bytes per lane. No thread returns
+// early: every lane takes part in the swaps and in the block's amax reduction, which ends in one
+// atomic max per block.
+template <typename T>
+struct ActIn {
+  Raw8<T> a, b;   // the pre-activation (ACT 0 / 1), or gate and up (ACT 2)
+};
+
+template <typename T, int ACT, bool NT>
+__device__ __forceinline__ ActIn<T> act_load(const T* __restrict__ x, int64_t r, int N, int c) {
+  ActIn<T> in;
+  const T* p = ACT == 2 ? x + r * 2 * N + c : x + r * N + c;
+  in.a = NT ? load_raw8_nt(p) : load_raw8(p);
+  if constexpr (ACT == 2) in.b = NT ? load_raw8_nt(p + N) : load_raw8(p + N);
+  else in.b = in.a;
+  return in;
+}
+
+template <typename T, int ACT, bool KEEP, int KR = 4>
+__global__ __launch_bounds__(256) void act_fwd_fp8_kernel(const T* __restrict__ x, const T* __restrict__ bias,
+                                                          T* __restrict__ y, uint8_t* __restrict__ q,
+                                                          const float* __restrict__ scale_p,
+                                                          float* __restrict__ amax, int64_t rows, int N,
+                                                          int rows_per_slice) {
+  static_assert(KR % 2 == 0, "rows are stored in pairs");
+  __shared__ unsigned red[4];
+  const int ch = blockIdx.x * 256 + threadIdx.x;
+  const bool valid = ch * 8 < N;
+  const bool odd = threadIdx.x & 1;
+  const float scale = *scale_p;
+  float b[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) b[j] = 0.f;
+  if (ACT != 2 && bias && valid) load_vec<T, 8>(bias + ch * 8, b);
+  const int64_t r0 = (int64_t)blockIdx.y * rows_per_slice;
+  const int64_t r1 = r0 + rows_per_slice < rows ? r0 + rows_per_slice : rows;
+  unsigned am = 0;
+  auto row_op = [&](int64_t r, const ActIn<T>& in, unsigned (&w)[2]) {
+    float v[8];
+    cvt_raw8<T>(in.a, v);
+    if constexpr (ACT == 2) {
+      float u[8];
+      cvt_raw8<T>(in.b, u);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = silu(v[j]) * u[j];
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = act_fwd<ACT>(v[j] + b[j]);
+    }
+    const u16x8 y16 = round16x8<T>(v);
+    if constexpr (KEEP) *reinterpret_cast<u16x8*>(y + r * N + ch * 8) = y16;
+    const unsigned m = quant_f32<false, 8>(v, scale, w);
+    am = m > am ? m : am;
+  };
+  int64_t r = r0;
+  for (; r + KR <= r1; r += KR) {
+    unsigned w[KR][2];
+#pragma unroll
+    for (int u = 0; u < KR; ++u) w[u][0] = w[u][1] = 0u;
+    if (valid) {
+      ActIn<T> in[KR];
+#pragma unroll
+      for (int u = 0; u < KR; ++u) in[u] = act_load<T, ACT, true>(x, r + u, N, ch * 8);
+#pragma unroll
+      for (int u = 0; u < KR; ++u) row_op(r + u, in[u], w[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < KR; u += 2) {
+      const u32x4 o = pair_bytes16(w[u], w[u + 1], odd);
+      if (valid) *reinterpret_cast<u32x4*>(q + (r + u + (odd ? 1 : 0)) * N + (ch & ~1) * 8) = o;
+    }
+  }
+  if (valid) {
+    for (; r < r1; ++r) {
+      unsigned w[2];
+      row_op(r, act_load<T, ACT, false>(x, r, N, ch * 8), w);
+      *reinterpret_cast<u32x2*>(q + r * N + ch * 8) = u32x2{w[0], w[1]};
+    }
+  }
+  merge_amax(am, red, amax);
+}
 
 __global__ __launch_bounds__(256) void col_partials_reduce_kernel(const float* __restrict__ part,
                                                                  int nslices, int N,
@@ -313,5 +406,38 @@ extern "C" hipError_t smdt_swiglu_bwd(int dtype, const void* dy, const void* x, 
   if (dtype == 1) hipLaunchKernelGGL(swiglu_bwd_kernel<bf16>, g2, dim3(256), 0, st, (const bf16*)dy, (const bf16*)x, (bf16*)dx, rows, F);
   else if (dtype == 2) hipLaunchKernelGGL(swiglu_bwd_kernel<f16>, g2, dim3(256), 0, st, (const f16*)dy, (const f16*)x, (f16*)dx, rows, F);
   else hipLaunchKernelGGL(swiglu_bwd_kernel<float>, g2, dim3(256), 0, st, (const float*)dy, (const float*)x, (float*)dx, rows, F);
+  return hipGetLastError();
+}
+
+// The FP8-output forward (act_fwd_fp8_kernel): 16-bit dtypes, rows of bytes that stay 16-byte aligned.
+extern "C" int smdt_act_fp8_supported(int dtype, int N) {
+  return (dtype == 1 || dtype == 2) && N >= 16 && N % 16 == 0;
+}
+
+extern "C" hipError_t smdt_act_fwd_fp8(int dtype, int act, const void* x, const void* bias, void* y, void* q,
+                                       const float* scale, float* amax, int64_t rows, int N, hipStream_t st) {
+  if (!smdt_act_fp8_supported(dtype, N) || act < 0 || act > 2 || rows > (int64_t(1) << 40) || q == nullptr ||
+      scale == nullptr || amax == nullptr)
+    return hipErrorInvalidValue;
+  if (rows <= 0) return hipSuccess;
+  int rps;
+  int slices = pf_slices(rows, &rps);
+  dim3 grid((N / 8 + 255) / 256, slices);
+#define SMDT_ACT_Q(T, A)                                                                                  \
+  do {                                                                                                    \
+    if (y != nullptr)                                                                                     \
+      hipLaunchKernelGGL((act_fwd_fp8_kernel<T, A, true>), grid, dim3(256), 0, st, (const T*)x,            \
+                         (const T*)bias, (T*)y, (uint8_t*)q, scale, amax, rows, N, rps);                   \
+    else                                                                                                  \
+      hipLaunchKernelGGL((act_fwd_fp8_kernel<T, A, false>), grid, dim3(256), 0, st, (const T*)x,           \
+                         (const T*)bias, (T*)nullptr, (uint8_t*)q, scale, amax, rows, N, rps);             \
+  } while (0)
+#define SMDT_ACT_Q_T(T)                                                                                   \
+  do {                                                                                                    \
+    if (act == 0) SMDT_ACT_Q(T, 0); else if (act == 1) SMDT_ACT_Q(T, 1); else SMDT_ACT_Q(T, 2);           \
+  } while (0)
+  if (dtype == 1) SMDT_ACT_Q_T(bf16); else SMDT_ACT_Q_T(f16);
+#undef SMDT_ACT_Q_T
+#undef SMDT_ACT_Q
   return hipGetLastError();
 }

@@ -5,12 +5,9 @@
 //   q[i] = fp8( clamp(float(x[i]) * scale, -max, max) )     round-to-nearest-even (v_cvt_pk_*_f32)
 //   amax = max(amax, max_i |float(x[i])|)                    before scaling, merged atomically
 //
-// The clamp is written with compares, which keep a NaN (fminf / fmaxf would drop it), so a NaN
-// input comes out as an FP8 NaN and +-inf saturates. A NaN is stored as 0x7f | sign in both
-// formats, the byte PyTorch's own cast produces. |x| is merged as its bit pattern: non-negative
-// floats order as unsigned integers, inf sorts above every finite value and NaN above inf, so a
-// non-finite input always leaves a non-finite amax. The merge is a max, so quantising the same
-// tensor again (activation recompute) changes nothing.
+// The rounding, saturation, NaN and amax-merge rule lives in fp8_round.h, which the producers that
+// write their output already quantised (layernorm.hip, bias_act.hip) share. The merge is a max,
+// so quantising the same tensor again (activation recompute) changes nothing.
 //
 // Two kernels:
 //   * fp8_quantize_flat: activations and gradients. A flat stream, 16 elements (two 16-byte
@@ -27,6 +24,7 @@
 // fp8_update_scales: one launch over the table of every FP8 tensor of a model. Everything stays on
 // the device (no host sync), so a captured training step advances its own scales.
 #include "common.h"
+#include "fp8_round.h"
 #include "launchers.h"
 
 namespace smdt {
@@ -34,76 +32,22 @@ namespace smdt {
 constexpr int kQT = 64;          // tile edge of the transposing kernel (elements)
 constexpr int kQPad = 4;         // LDS row padding in bytes (keeps rows 4-byte aligned)
 
-template <bool BF8> constexpr float fp8_max() { return BF8 ? 57344.f : 448.f; }
-
-// Four floats -> four FP8 bytes (element 0 in the low byte).
-template <bool BF8>
-__device__ __forceinline__ unsigned cvt4(float a, float b, float c, float d) {
-  int w = 0;
-  if constexpr (BF8) {
-    w = __builtin_amdgcn_cvt_pk_bf8_f32(a, b, w, false);
-    w = __builtin_amdgcn_cvt_pk_bf8_f32(c, d, w, true);
-  } else {
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, w, false);
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
-  }
-  unsigned u = (unsigned)w;
-  const float v[4] = {a, b, c, d};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    if (v[i] != v[i]) {   // canonical NaN byte, sign kept
-      const unsigned nan = 0x7Fu | ((__float_as_uint(v[i]) >> 24) & 0x80u);
-      u = (u & ~(0xFFu << (8 * i))) | (nan << (8 * i));
-    }
-  }
-  return u;
-}
-
 // 16 raw 16-bit elements -> 16 FP8 bytes; returns max |x| of them as a bit pattern.
 template <typename T, bool BF8>
 __device__ __forceinline__ unsigned quant16(const u16x8& lo, const u16x8& hi, float scale, u32x4& out) {
-  constexpr float kMax = fp8_max<BF8>();
-  float v[16];
-  unsigned am = 0;
+  float f[16];
 #pragma unroll
   for (int j = 0; j < 16; ++j) {
     const unsigned short bits = j < 8 ? lo[j] : hi[j - 8];
     T t;
     __builtin_memcpy(&t, &bits, 2);
-    const float f = to_f32(t);
-    const unsigned ab = __float_as_uint(f) & 0x7FFFFFFFu;
-    am = ab > am ? ab : am;
-    float s = f * scale;
-    s = s > kMax ? kMax : s;      // compares are false for NaN: it passes through
-    s = s < -kMax ? -kMax : s;
-    v[j] = s;
+    f[j] = to_f32(t);
   }
+  unsigned w[4];
+  const unsigned am = quant_f32<BF8, 16>(f, scale, w);
 #pragma unroll
-  for (int k = 0; k < 4; ++k) out[k] = cvt4<BF8>(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]);
+  for (int k = 0; k < 4; ++k) out[k] = w[k];
   return am;
-}
-
-__device__ __forceinline__ unsigned wave_umax(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned w = (unsigned)__shfl_xor((int)v, o, kWave);
-    v = w > v ? w : v;
-  }
-  return v;
-}
-
-// Block-wide max of the bit patterns, merged into *amax by one atomic per block.
-__device__ __forceinline__ void merge_amax(unsigned am, unsigned* red, float* __restrict__ amax) {
-  am = wave_umax(am);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) red[wid] = am;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned m = red[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) m = red[w] > m ? red[w] : m;
-    if (m != 0) atomicMax(reinterpret_cast<unsigned*>(amax), m);
-  }
 }
 
 template <typename T, bool BF8>

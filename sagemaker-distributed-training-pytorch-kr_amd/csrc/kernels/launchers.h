@@ -40,6 +40,21 @@ hipError_t smdt_swiglu_fwd(int dtype, const void* x, void* y, int64_t rows, int 
 hipError_t smdt_swiglu_bwd(int dtype, const void* dy, const void* x, void* dx, int64_t rows,
                            int F, hipStream_t st);
 
+// FP8-output forward of the producers of an FP8 linear's input (delayed scaling): q [rows, H or N]
+// E4M3 = fp8_quantize(y rounded to the 16-bit dtype, *scale), *amax merged with max |y|; y may be
+// null (q alone). dtype bf16 / fp16; the widths the *_fp8_supported functions take.
+int smdt_layernorm_fp8_supported(int dtype, int H);
+hipError_t smdt_layernorm_fwd_fp8(int dtype, int wdtype, const void* x, const void* res,
+                                  const void* bias, const void* gamma, const void* beta, void* y,
+                                  void* s_out, float* mean, float* rstd, int64_t rows, int H,
+                                  float eps, float p_drop, uint64_t seed, uint64_t offset, int rms,
+                                  const void* x2, void* q, const float* scale, float* amax,
+                                  hipStream_t st);
+// act: 0 = bias + GeLU-tanh, 1 = bias + GeLU-erf (x [rows, N]); 2 = SwiGLU (x [rows, 2N], no bias)
+int smdt_act_fp8_supported(int dtype, int N);
+hipError_t smdt_act_fwd_fp8(int dtype, int act, const void* x, const void* bias, void* y, void* q,
+                            const float* scale, float* amax, int64_t rows, int N, hipStream_t st);
+
 // softmax.hip
 hipError_t smdt_softmax_fwd(int dtype, int mode, const void* x, const uint8_t* mask, void* y,
                             int64_t rows, int sq, int sk, int heads, float scale,

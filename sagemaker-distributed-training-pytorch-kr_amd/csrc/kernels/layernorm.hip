@@ -16,6 +16,7 @@
 //  * Dropout uses a stateless keyed hash of (row, col) (see dropout_mask8), so the backward
 //    pass recomputes the mask instead of storing it.
 #include "common.h"
+#include "fp8_round.h"
 #include "launchers.h"
 
 namespace smdt {
@@ -40,6 +41,10 @@ struct LnFwdArgs {
   const void* x2;        // [rows, H] optional second summand of x (a reduce-scatter's incoming
                          // partial: x + x2 is the row-parallel output, added here instead of in
                          // a separate pass)
+  // FP8-output forms (ln_fwd_kernel<.., Q> with Q != 0): the normalised row also leaves as E4M3
+  void* q;               // [rows, H] bytes
+  const float* q_scale;  // the consumer's delayed scale (one value)
+  float* q_amax;         // merged with max |y rounded to T| by one atomic per block
 };
 
 struct LnBwdArgs {
@@ -104,9 +109,19 @@ __device__ __forceinline__ void dropout_mask8(uint32_t key, int64_t row, int H, 
   }
 }
 
-template <typename T, typename W, int G, int C>
+// Q: 0 = the 16-bit output alone; 1 = y and its E4M3 quantisation q; 2 = q alone (y is never
+// written). q is fp8_quantize's function of the rounded 16-bit y (fp8_round.h), made from the
+// registers that hold the normalised row. A lane's C chunks lie G * 8 columns apart, so its bytes
+// come in runs of 8. Chunks c and c + 1 that are full for the whole group (the geometry's
+// (c + 2) * G <= H / 8 with H % 16 == 0, uniform over the block) are swapped between neighbouring
+// lanes and leave as one 16-byte store per lane; an odd last chunk or a partly filled one leaves
+// as 8 bytes.
+template <typename T, typename W, int G, int C, int Q = 0>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(LnFwdArgs a) {
   __shared__ float scratch[8];
+  [[maybe_unused]] float qscale = 1.f;
+  [[maybe_unused]] unsigned qam = 0;
+  if constexpr (Q != 0) qscale = *a.q_scale;
   const int H = a.H;
   const int tid_in_group = threadIdx.x % G;
   const int groups_per_block = 256 / G;
@@ -200,16 +215,56 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(LnFwdArgs a) {
       a.rstd[row] = rs;
     }
     T* yr = (T*)a.y + row * H;
+    [[maybe_unused]] unsigned qb[C][2];
 #pragma unroll
     for (int c = 0; c < C; ++c) {
       int ch = c * G + tid_in_group;
       if (ch < nchunk) {
         float o[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = (v[c][j] - mu) * rs * g[c][j] + b[c][j];
-        store_vec<T, 8>(yr + ch * 8, o);
+        for (int j = 0; j < 8; ++j) {
+          // Bit identity with the 16-bit form rests on what the compiler does with that form: it
+          // contracts this multiply-add to one fma in every instantiation and rounds to T with
+          // plain conversions. The FP8 forms spell both out (fmaf here, round16x8 below), since
+          // some of their instantiations were otherwise left with a separate add or a
+          // single-rounding mixed-precision fma. A compiler that treats the 16-bit form
+          // differently breaks the identity; tests/test_fp8_fused_quant_gpu.py is the guard.
+          if constexpr (Q == 0) o[j] = (v[c][j] - mu) * rs * g[c][j] + b[c][j];
+          else o[j] = __builtin_fmaf((v[c][j] - mu) * rs, g[c][j], b[c][j]);
+        }
+        if constexpr (Q == 0) store_vec<T, 8>(yr + ch * 8, o);
+        if constexpr (Q != 0) {
+          const u16x8 y16 = round16x8<T>(o);
+          if constexpr (Q == 1) *reinterpret_cast<u16x8*>(yr + ch * 8) = y16;
+          const unsigned m = quant_f32<false, 8>(o, qscale, qb[c]);
+          qam = m > qam ? m : qam;
+        }
+      } else if constexpr (Q != 0) {
+        qb[c][0] = qb[c][1] = 0u;
       }
     }
+    if constexpr (Q != 0) {
+      uint8_t* qr = (uint8_t*)a.q + row * H;
+      const bool odd = tid_in_group & 1;
+#pragma unroll
+      for (int c = 0; c < C; c += 2) {
+        if (c + 1 < C && (c + 2) * G <= nchunk && (H & 15) == 0) {   // both chunks full: 16 bytes per lane
+          const u32x4 w = pair_bytes16(qb[c], qb[c + 1], odd);
+          const int ch = (odd ? c + 1 : c) * G + (tid_in_group & ~1);
+          *reinterpret_cast<u32x4*>(qr + ch * 8) = w;
+        } else {
+#pragma unroll
+          for (int d = c; d < c + 2 && d < C; ++d) {
+            const int ch = d * G + tid_in_group;
+            if (ch < nchunk) *reinterpret_cast<u32x2*>(qr + ch * 8) = u32x2{qb[d][0], qb[d][1]};
+          }
+        }
+      }
+    }
+  }
+  if constexpr (Q != 0) {
+    __shared__ unsigned qred[4];
+    merge_amax(qam, qred, a.q_amax);
   }
 }
 
@@ -390,10 +445,10 @@ __global__ __launch_bounds__(256) void ln_partials_reduce_kernel(const float* __
   colsum_block(part + (int64_t)q * H, nblocks, 3 * (int64_t)H, H, out, (acc_mask >> q) & 1);
 }
 
-template <typename T, typename W, int G>
+template <typename T, typename W, int G, int Q>
 static hipError_t ln_fwd_dispatch_c(const LnFwdArgs& a, int C, int grid, hipStream_t st) {
 #define SMDT_LN_FWD_CASE(CC) \
-  case CC: hipLaunchKernelGGL((ln_fwd_kernel<T, W, G, CC>), dim3(grid), dim3(256), 0, st, a); break;
+  case CC: hipLaunchKernelGGL((ln_fwd_kernel<T, W, G, CC, Q>), dim3(grid), dim3(256), 0, st, a); break;
   switch (C) {
     SMDT_LN_FWD_CASE(1) SMDT_LN_FWD_CASE(2) SMDT_LN_FWD_CASE(3) SMDT_LN_FWD_CASE(4)
     SMDT_LN_FWD_CASE(5) SMDT_LN_FWD_CASE(6) SMDT_LN_FWD_CASE(7) SMDT_LN_FWD_CASE(8)
@@ -427,14 +482,20 @@ static void ln_geometry(int H, int* G, int* C) {
   *C = (nchunk + *G - 1) / *G;
 }
 
-template <typename T, typename W>
+template <typename T, typename W, int Q = 0>
 static hipError_t ln_fwd_typed(const LnFwdArgs& a, hipStream_t st) {
   int G, C;
   ln_geometry(a.H, &G, &C);
   int rows_per_block = 256 / G;
   int grid = stream_grid(a.rows, rows_per_block);
-  if (G == 64) return ln_fwd_dispatch_c<T, W, 64>(a, C, grid, st);
-  return ln_fwd_dispatch_c<T, W, 256>(a, C, grid, st);
+  if (G == 64) return ln_fwd_dispatch_c<T, W, 64, Q>(a, C, grid, st);
+  return ln_fwd_dispatch_c<T, W, 256, Q>(a, C, grid, st);
+}
+
+// The FP8-output forms: y != nullptr keeps the 16-bit output beside q.
+template <typename T, typename W>
+static hipError_t ln_fwd_fp8_typed(const LnFwdArgs& a, hipStream_t st) {
+  return a.y != nullptr ? ln_fwd_typed<T, W, 1>(a, st) : ln_fwd_typed<T, W, 2>(a, st);
 }
 
 template <typename T, typename W>
@@ -468,12 +529,34 @@ extern "C" hipError_t smdt_layernorm_fwd(int dtype, int wdtype, const void* x, c
                                          const void* x2, hipStream_t st) {
   if (H % 8 != 0 || H > 16384) return hipErrorInvalidValue;
   LnFwdArgs a{x, res, bias, gamma, beta, y, s_out, mean, rstd, rows, H, eps, p_drop, seed, offset, rms,
-              smdt_rng_step(), x2};
+              smdt_rng_step(), x2, nullptr, nullptr, nullptr};
   if (dtype == 1 && wdtype == 1) return ln_fwd_typed<bf16, bf16>(a, st);
   if (dtype == 1 && wdtype == 0) return ln_fwd_typed<bf16, float>(a, st);
   if (dtype == 2 && wdtype == 2) return ln_fwd_typed<f16, f16>(a, st);
   if (dtype == 2 && wdtype == 0) return ln_fwd_typed<f16, float>(a, st);
   if (dtype == 0 && wdtype == 0) return ln_fwd_typed<float, float>(a, st);
+  return hipErrorInvalidValue;
+}
+
+// Every width the 16-bit forward takes, in a 16-bit dtype.
+extern "C" int smdt_layernorm_fp8_supported(int dtype, int H) {
+  return (dtype == 1 || dtype == 2) && H >= 8 && H % 8 == 0 && H <= 16384;
+}
+
+extern "C" hipError_t smdt_layernorm_fwd_fp8(int dtype, int wdtype, const void* x, const void* res,
+                                             const void* bias, const void* gamma, const void* beta,
+                                             void* y, void* s_out, float* mean, float* rstd,
+                                             int64_t rows, int H, float eps, float p_drop,
+                                             uint64_t seed, uint64_t offset, int rms, const void* x2,
+                                             void* q, const float* scale, float* amax, hipStream_t st) {
+  if (!smdt_layernorm_fp8_supported(dtype, H) || q == nullptr || scale == nullptr || amax == nullptr)
+    return hipErrorInvalidValue;
+  LnFwdArgs a{x, res, bias, gamma, beta, y, s_out, mean, rstd, rows, H, eps, p_drop, seed, offset, rms,
+              smdt_rng_step(), x2, q, scale, amax};
+  if (dtype == 1 && wdtype == 1) return ln_fwd_fp8_typed<bf16, bf16>(a, st);
+  if (dtype == 1 && wdtype == 0) return ln_fwd_fp8_typed<bf16, float>(a, st);
+  if (dtype == 2 && wdtype == 2) return ln_fwd_fp8_typed<f16, f16>(a, st);
+  if (dtype == 2 && wdtype == 0) return ln_fwd_fp8_typed<f16, float>(a, st);
   return hipErrorInvalidValue;
 }
 

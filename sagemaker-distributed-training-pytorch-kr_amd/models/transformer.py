@@ -94,6 +94,9 @@ class TransformerConfig:
     # --fp8-recipe: "delayed" (per-tensor delayed scaling, above) | "mxfp8" (OCP MX block scaling
     # on the scaled MFMA, tp.MXFP8Linear: no state, no table in the state dict)
     fp8_recipe: str = "delayed"
+    # --fp8-fused-quantize (delayed scaling only): the norm and activation kernels write the E4M3
+    # operand of the linear they feed (QKV, fc1, fc2), which then launches no quantise pass
+    fp8_fused_quantize: bool = False
 
     def __post_init__(self):
         if self.fp8_recipe not in ("delayed", "mxfp8"):
@@ -111,6 +114,15 @@ class TransformerConfig:
         if self.fp8 and self.num_experts:
             raise ValueError("fp8 linears with num_experts are not supported (per-expert row counts are not "
                              "multiples of 16)")
+        if self.fp8_fused_quantize:
+            if not self.fp8:
+                raise ValueError("fp8_fused_quantize needs fp8 linears (fp8 = 'e4m3' or 'hybrid')")
+            if self.fp8_recipe == "mxfp8":
+                raise ValueError("fp8_fused_quantize is for the delayed-scaling recipe: fp8_recipe 'mxfp8' takes its "
+                                 "scales from the blocks themselves")
+            if self.apply_residual_connection_post_layernorm:
+                raise ValueError("fp8_fused_quantize with apply_residual_connection_post_layernorm is not supported "
+                                 "(the norm output is then the residual too)")
         if self.moe_grouped_gemm and not self.num_experts:
             raise ValueError("moe_grouped_gemm needs num_experts")
         if self.num_query_groups is None:
@@ -161,13 +173,13 @@ class Norm(nn.Module):
         else:
             self.register_parameter("bias", None)
 
-    def fused(self, x, xbias, residual, p, training, gather=None):
+    def fused(self, x, xbias, residual, p, training, gather=None, fp8_out=None, keep16=True):
         # called instead of forward() by the layers: wait for this module's overlapped ZeRO
         # parameter all-gather (see _gather_wait) before the kernel reads the weights
         _gather_wait(self, x)
         w = self.weight + 1 if self.one_p else self.weight
         return SF.bias_dropout_add_norm(x, xbias, residual, w, self.bias, p, training, self.eps, self.rms,
-                                        rng=get_rng(self.rng_kind), gather=gather)
+                                        rng=get_rng(self.rng_kind), gather=gather, fp8_out=fp8_out, keep16=keep16)
 
     def forward(self, x):
         return self.fused(x, None, None, 0.0, False)[0]
@@ -480,14 +492,17 @@ class ParallelAttention(nn.Module):
         return lin.bias if tp.bias_from_producer(lin.bias, x) else None
 
     def forward(self, x, training=True, doc_start=None):
-        qkv_bias = self._qkv_bias_from_attention(x)
+        """``x``: the normalised input, or (x16, q) from a norm that quantised it for the
+        QKV linear (``_fp8_handoff``)."""
+        x, qx = x if isinstance(x, tuple) else (x, None)
+        qkv_bias = None if qx is not None else self._qkv_bias_from_attention(x)
         if qkv_bias is not None:
             qkv = self.qkv(x, bias_grad=False)
             p = self.cfg.attention_dropout if training else 0.0
             return self.proj(SF.flash_attention_qkv(qkv, self.nh, self.nkv, self.hd, seq_first=True, causal=True,
                                                     dropout_p=p, rng=get_rng("tp"), doc_start=doc_start,
                                                     bias_p=qkv_bias))
-        qkv = self.qkv(x)                                        # [s, b, (nh + 2 nkv) d]
+        qkv = self.qkv(x, qx=qx)                                 # [s, b, (nh + 2 nkv) d]
         if _PACK["idx"] is not None:                              # padding-free micro-batch
             if doc_start is not None:
                 raise NotImplementedError("per-document attention (doc_start / --reset-attention-mask) is not "
@@ -651,6 +666,20 @@ def _apply_rope_parts(flat, cos, sin, rot, nh, nkv, hd, b, s, inverse):
         k.copy_(SF._rope_ref(k, cos.to(flat.device), sin.to(flat.device), rot, pos, inverse))
 
 
+def _fp8_handoff(cfg, lin):
+    """``fp8_out`` / ``keep16`` for the kernel that produces ``lin``'s input under
+    --fp8-fused-quantize, else None. The 16-bit copy is kept only where the linear's backward reads
+    it (the 16-bit weight gradient, i.e. without --fp8-wgrad): nothing else does, since the pre-LN
+    residual is the norm's input and the activation's backward reads its saved pre-activation. Not
+    inside ``generate()``'s weight-format scope, whose linears take 16-bit inputs."""
+    if not cfg.fp8_fused_quantize or lin is None or dw._DECODE["state"] is not None:
+        return None
+    slot = lin.fp8_input_slot()
+    if slot is None:
+        return None
+    return {"fp8_out": slot, "keep16": fp8_linear.keeps_input16(lin._fp8)}
+
+
 class ParallelMLP(nn.Module):
     def __init__(self, cfg: TransformerConfig, layer_number: int, device=None, key: Optional[str] = None):
         super().__init__()
@@ -693,7 +722,15 @@ class ParallelMLP(nn.Module):
                 return y, self.fc2.bias
             # fc1 GEMM + bias + GeLU in one launch (gemm_tn.hip's bias-GeLU epilogue)
             return self.fc2(tp.linear_bias_gelu(x, self.fc1))
-        h, b = self.fc1(x)
+        # (x16, q): the norm quantised fc1's input; the activation kernels do the same for fc2
+        h, b = self.fc1(x[0], qx=x[1]) if isinstance(x, tuple) else self.fc1(x)
+        out = _fp8_handoff(self.cfg, self.fc2)
+        if out is not None and (act == "swiglu" or (act in ("gelu", "gelu_erf") and self.cfg.bias_gelu_fusion)):
+            if act == "swiglu":
+                h16, q = SF.swiglu(h if b is None else h + b, **out)
+            else:
+                h16, q = SF.bias_gelu(h, b, "tanh" if act == "gelu" else "none", **out)
+            return self.fc2(h16, qx=q)
         if act in ("gelu", "gelu_erf"):
             if self.cfg.bias_gelu_fusion:
                 h = SF.bias_gelu(h, b, "tanh" if act == "gelu" else "none")
@@ -856,13 +893,17 @@ class ParallelTransformerLayer(nn.Module):
         # linear and (after a layer) its input gradient by the row-parallel linear that produced
         # x — both are written straight into their slot of the gather buffer (no local copy)
         g = _sp_gather(self.cfg)
+        # --fp8-fused-quantize: each norm writes the E4M3 operand of the linear it feeds; ln1 / ln2
+        # are then (x16, q) and travel to that linear with the call
         ln1, residual = self.input_norm.fused(x, xbias, residual, p, training,
-                                              gather=None if g is None else g + (True, residual is not None))
+                                              gather=None if g is None else g + (True, residual is not None),
+                                              **(_fp8_handoff(self.cfg, self.attention.qkv) or {}))
         if self.post_ln_residual:           # Megatron's --apply-residual-connection-post-layernorm
             residual = ln1
         a, ab = self.attention(ln1, training, doc_start)
         ln2, residual = self.post_attention_norm.fused(a, ab, residual, p, training,
-                                                       gather=None if g is None else g + (True, True))
+                                                       gather=None if g is None else g + (True, True),
+                                                       **(_fp8_handoff(self.cfg, getattr(self.mlp, "fc1", None)) or {}))
         if self.post_ln_residual:
             residual = ln2
         m, mb = self.mlp(ln2)

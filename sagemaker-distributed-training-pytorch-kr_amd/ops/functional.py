@@ -70,6 +70,24 @@ def _ln_ref(s, gamma, beta, eps, rms):
     return y.to(s.dtype)
 
 
+# FP8-output producers (``fp8_out=(scale, amax)``): the producer of an FP8 linear's input writes the
+# E4M3 operand itself and returns ``(y, q)``. q = fp8_quantize(y, scale, amax, "e4m3") of the rounded
+# 16-bit output, bit for bit, and is not differentiable. y carries the gradient: it is the 16-bit
+# output when ``keep16``, else (on the kernel path) a one-element tensor expanded to the output's
+# shape, never written and never to be read. An FP8 linear takes both: ``lin(y, qx=q)``.
+
+
+def _carrier_stub(like, shape=None):
+    return like.new_empty(()).expand(like.shape if shape is None else shape)
+
+
+def _fp8_out_ref(y, fp8_out):
+    """The torch twin of every FP8-output producer: fp8_quantize_ref of the rounded output."""
+    with torch.no_grad():
+        q = fp8_quantize_ref(y.detach(), fp8_out[0], fp8_out[1], "e4m3")
+    return y, q
+
+
 def grad_accumulate_target(t):
     """The fp32 DDP ``main_grad`` of parameter ``t`` if a kernel may accumulate the parameter's
     gradient straight into it (then the kernel owner calls ``t._smdt_grad_ready``), else None."""
@@ -104,8 +122,9 @@ def _mark_gather(t, buf, rank):
 
 class _BDALayerNorm(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, bias, residual, gamma, beta, p, eps, rms, seed, offset, gather=None, x2=None):
-        """``gather`` = (world, rank, y_into_gather, dx_into_gather) under sequence parallelism:
+    def forward(ctx, x, bias, residual, gamma, beta, p, eps, rms, seed, offset, gather=None, x2=None, fp8=None):
+        """``fp8`` = (scale, amax, keep16): the FP8-output form; returns (y, s, q).
+        ``gather`` = (world, rank, y_into_gather, dx_into_gather) under sequence parallelism:
         the normalised output (consumed by a column-parallel ring all-gather) and / or the input
         gradient (consumed by a row-parallel linear's backward all-gather) are written into their
         rank's slot of a gather buffer. ``x2`` (no gradient): a second summand of x, added in the
@@ -113,12 +132,22 @@ class _BDALayerNorm(torch.autograd.Function):
         gradient is also x + x2's."""
         C = _ext.ext()
         x = x.contiguous()
-        buf = out_y = None
+        buf = out_y = q = None
         if gather is not None and gather[2]:
             buf, out_y = gather_slot(x, gather[0], gather[1])
-        y, s, mean, rstd = C.layernorm_fwd(x, None if residual is None else residual.contiguous(),
-                                           bias, gamma, beta, eps, p, seed, offset, rms, True, out_y,
-                                           None if x2 is None else x2.contiguous())
+        if fp8 is not None:
+            if gather is not None:
+                raise RuntimeError("bias_dropout_add_norm: fp8_out is for TP = 1 (no sequence-parallel gather slot)")
+            y, s, mean, rstd, q = C.layernorm_fwd_fp8(x, None if residual is None else residual.contiguous(),
+                                                      bias, gamma, beta, eps, p, seed, offset, rms, fp8[0], fp8[1],
+                                                      bool(fp8[2]), None if x2 is None else x2.contiguous())
+            if y is None:
+                y = _carrier_stub(x)
+            ctx.mark_non_differentiable(q)
+        else:
+            y, s, mean, rstd = C.layernorm_fwd(x, None if residual is None else residual.contiguous(),
+                                               bias, gamma, beta, eps, p, seed, offset, rms, True, out_y,
+                                               None if x2 is None else x2.contiguous())
         if buf is not None:
             _mark_gather(y, buf, gather[1])
         ctx.save_for_backward(s, gamma, mean, rstd)
@@ -126,10 +155,10 @@ class _BDALayerNorm(torch.autograd.Function):
         ctx.cfg = (p, seed, offset, rms, bias is not None, residual is not None, beta is not None,
                    gamma.dtype, None if bias is None else bias.dtype)
         ctx.gather = gather
-        return y, s
+        return (y, s) if q is None else (y, s, q)
 
     @staticmethod
-    def backward(ctx, dy, ds):
+    def backward(ctx, dy, ds, dq=None):
         s, gamma, mean, rstd = ctx.saved_tensors
         p, seed, offset, rms, has_bias, has_res, has_beta, gdt, bdt = ctx.cfg
         C = _ext.ext()
@@ -157,12 +186,16 @@ class _BDALayerNorm(torch.autograd.Function):
         g_gamma = None if ta is not None else dgamma.to(gdt)
         g_beta = None if (not has_beta or tb is not None) else dbeta.to(gdt)
         g_bias = None if (not has_bias or tc is not None) else dbias.to(bdt)
-        return (dx, g_bias, d_s if has_res else None, g_gamma, g_beta, None, None, None, None, None, None, None)
+        return (dx, g_bias, d_s if has_res else None, g_gamma, g_beta, None, None, None, None, None, None, None, None)
 
 
 def bias_dropout_add_norm(x, bias, residual, gamma, beta, p: float, training: bool, eps: float = 1e-5,
-                          rms: bool = False, rng: Optional[PhiloxState] = None, gather=None):
+                          rms: bool = False, rng: Optional[PhiloxState] = None, gather=None, fp8_out=None,
+                          keep16: bool = True):
     """Returns ``(norm(s), s)`` with ``s = residual + dropout(x + bias)``.
+
+    ``fp8_out`` = (scale, amax) of the consuming FP8 linear's input slot: ``norm(s)`` comes back as
+    ``(y, q)`` (see "FP8-output producers" above).
 
     ``bias``, ``residual`` may be None; ``beta`` is ignored for RMSNorm. This is the
     residual-stream step of a pre-LN transformer fused with the following LayerNorm.
@@ -176,8 +209,12 @@ def bias_dropout_add_norm(x, bias, residual, gamma, beta, p: float, training: bo
     x = plain(x)
     if _ext.use_kernels(x):
         seed, offset = _rng(rng).next() if p > 0 else (0, 0)
-        return _BDALayerNorm.apply(x, bias, residual, gamma, None if rms else beta, p, float(eps), bool(rms),
-                                   int(seed), int(offset), gather, x2)
+        if fp8_out is None:
+            return _BDALayerNorm.apply(x, bias, residual, gamma, None if rms else beta, p, float(eps), bool(rms),
+                                       int(seed), int(offset), gather, x2)
+        y, s, q = _BDALayerNorm.apply(x, bias, residual, gamma, None if rms else beta, p, float(eps), bool(rms),
+                                      int(seed), int(offset), gather, x2, (fp8_out[0], fp8_out[1], bool(keep16)))
+        return (y, q), s
     if x2 is not None:
         x = x + x2
     h = x if bias is None else x + bias
@@ -190,15 +227,19 @@ def bias_dropout_add_norm(x, bias, residual, gamma, beta, p: float, training: bo
     else:
         y = F.layer_norm(s.float(), (s.shape[-1],), gamma.float(), None if beta is None else beta.float(),
                          eps).to(s.dtype)
+    if fp8_out is not None:
+        return _fp8_out_ref(y, fp8_out), s
     return y, s
 
 
-def layer_norm(x, gamma, beta, eps: float = 1e-5):
-    return bias_dropout_add_norm(x, None, None, gamma, beta, 0.0, False, eps, False)[0]
+def layer_norm(x, gamma, beta, eps: float = 1e-5, fp8_out=None, keep16: bool = True):
+    return bias_dropout_add_norm(x, None, None, gamma, beta, 0.0, False, eps, False, fp8_out=fp8_out,
+                                 keep16=keep16)[0]
 
 
-def rms_norm(x, gamma, eps: float = 1e-6):
-    return bias_dropout_add_norm(x, None, None, gamma, None, 0.0, False, eps, True)[0]
+def rms_norm(x, gamma, eps: float = 1e-6, fp8_out=None, keep16: bool = True):
+    return bias_dropout_add_norm(x, None, None, gamma, None, 0.0, False, eps, True, fp8_out=fp8_out,
+                                 keep16=keep16)[0]
 
 
 def bias_dropout_add(x, bias, residual, p: float, training: bool):
@@ -217,18 +258,22 @@ _ACT_CODES = {"gelu": 0, "gelu_tanh": 0, "gelu_erf": 1}
 
 class _BiasAct(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, bias, act):
+    def forward(ctx, x, bias, act, fp8=None):
+        """``fp8`` = (scale, amax, keep16): the FP8-output form; returns (y, q)."""
         C = _ext.ext()
         x = x.contiguous()
-        y = C.bias_act_fwd(x, bias, act)
         ctx.save_for_backward(x, bias)
         ctx.bias_p = bias
         ctx.act = act
         ctx.has_bias = bias is not None
-        return y
+        if fp8 is None:
+            return C.bias_act_fwd(x, bias, act)
+        y, q = C.act_fwd_fp8(x, bias, act, fp8[0], fp8[1], bool(fp8[2]))
+        ctx.mark_non_differentiable(q)
+        return (_carrier_stub(x) if y is None else y), q
 
     @staticmethod
-    def backward(ctx, dy):
+    def backward(ctx, dy, dq=None):
         x, bias = ctx.saved_tensors
         C = _ext.ext()
         # a detached bias (ColumnParallelLinear(bias_grad_from_output=True): the linear produces
@@ -238,39 +283,54 @@ class _BiasAct(torch.autograd.Function):
         dx, dbias = C.bias_act_bwd(dy.contiguous(), x, bias, ctx.act, want_db, tgt)
         if tgt is not None:
             _mark_ready(ctx.bias_p)
-            return dx, None, None
-        return dx, (dbias.to(bias.dtype) if want_db else None), None
+            return dx, None, None, None
+        return dx, (dbias.to(bias.dtype) if want_db else None), None, None
 
 
-def bias_gelu(x, bias=None, approximate: str = "tanh"):
-    """GeLU(x + bias); ``approximate='tanh'`` is Megatron's bias_gelu, 'none' the erf form."""
+def bias_gelu(x, bias=None, approximate: str = "tanh", fp8_out=None, keep16: bool = True):
+    """GeLU(x + bias); ``approximate='tanh'`` is Megatron's bias_gelu, 'none' the erf form.
+    ``fp8_out`` = (scale, amax): returns ``(y, q)`` (see "FP8-output producers")."""
     act = 0 if approximate == "tanh" else 1
     if _ext.use_kernels(x):
-        return _BiasAct.apply(x, bias, act)
+        if fp8_out is None:
+            return _BiasAct.apply(x, bias, act)
+        y, q = _BiasAct.apply(x, bias, act, (fp8_out[0], fp8_out[1], bool(keep16)))
+        return y, q
     h = x if bias is None else x + bias
-    return F.gelu(h.float(), approximate="tanh" if act == 0 else "none").to(x.dtype)
+    y = F.gelu(h.float(), approximate="tanh" if act == 0 else "none").to(x.dtype)
+    return y if fp8_out is None else _fp8_out_ref(y, fp8_out)
 
 
 class _SwiGLU(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x):
+    def forward(ctx, x, fp8=None):
+        """``fp8`` = (scale, amax, keep16): the FP8-output form; returns (y, q)."""
         C = _ext.ext()
         x = x.contiguous()
         ctx.save_for_backward(x)
-        return C.swiglu_fwd(x)
+        if fp8 is None:
+            return C.swiglu_fwd(x)
+        y, q = C.act_fwd_fp8(x, None, 2, fp8[0], fp8[1], bool(fp8[2]))
+        ctx.mark_non_differentiable(q)
+        return (_carrier_stub(x, q.shape) if y is None else y), q
 
     @staticmethod
-    def backward(ctx, dy):
+    def backward(ctx, dy, dq=None):
         (x,) = ctx.saved_tensors
-        return _ext.ext().swiglu_bwd(dy.contiguous(), x)
+        return _ext.ext().swiglu_bwd(dy.contiguous(), x), None
 
 
-def swiglu(x):
-    """x = [gate | up] on the last dim -> silu(gate) * up."""
+def swiglu(x, fp8_out=None, keep16: bool = True):
+    """x = [gate | up] on the last dim -> silu(gate) * up.
+    ``fp8_out`` = (scale, amax): returns ``(y, q)`` (see "FP8-output producers")."""
     if _ext.use_kernels(x):
-        return _SwiGLU.apply(x)
+        if fp8_out is None:
+            return _SwiGLU.apply(x)
+        y, q = _SwiGLU.apply(x, (fp8_out[0], fp8_out[1], bool(keep16)))
+        return y, q
     g, u = x.chunk(2, dim=-1)
-    return (F.silu(g.float()) * u.float()).to(x.dtype)
+    y = (F.silu(g.float()) * u.float()).to(x.dtype)
+    return y if fp8_out is None else _fp8_out_ref(y, fp8_out)
 
 
 # --------------------------------------------------------------------------------------------

@@ -32,6 +32,10 @@ from .dense import _bias_grad, _fire, _wgrad_and_bias, _wgrad_target
 # The forward then saves q(x) instead of the 16-bit x (scales move only after the optimizer step,
 # so the saved bytes are what a re-quantise in the backward would give), the backward's one q(dY)
 # feeds both the dgrad and the wgrad, and the bias gradient still comes from the 16-bit dY.
+# The producer of x may have quantised it already (--fp8-fused-quantize: the norm and activation
+# kernels write q(x) beside or instead of the 16-bit x, ``SF.*(fp8_out=input_slot(lin))``): the linear
+# is then handed q(x) with the call (``qx``) and launches no quantise of its own; its x is the
+# tensor the producer returned beside q(x), read only where the backward needs 16 bits.
 # Scales are "delayed": a quantise uses the scale the last update derived
 # from earlier amax values and records its own amax for the next update, so no tensor is read
 # twice and nothing syncs with the host. TP = 1 only.
@@ -204,17 +208,29 @@ def _fp8_rows(t, what):
 class FP8Linear(torch.autograd.Function):
     """y = x W^T (+ b) at TP = 1 with FP8 forward and dgrad GEMMs (see the section comment).
     ``slot0`` is the row of x in ``state``'s table (W: + 1, dY: + 2). ``bias`` always gets its
-    gradient; ``add_bias`` False leaves the addition to the caller (skip_bias_add)."""
+    gradient; ``add_bias`` False leaves the addition to the caller (skip_bias_add). ``qx``: x already
+    quantised for ``slot0`` by its producer (amax merged there); x itself is then read only by the
+    16-bit weight gradient, so with ``fp8_wgrad`` it may be the producer's storage-free stand-in."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, add_bias, state, slot0):
+    def forward(ctx, x, weight, bias, add_bias, state, slot0, qx=None):
         ctx.state, ctx.slot0 = state, slot0
         ctx.has_bias = bias is not None
         ctx.bias_p = bias
         ctx.x_shape = x.shape
-        x2 = _fp8_rows(x, "the input")
-        sx, ax, ix = state.slot(slot0)
-        qx = SF.fp8_quantize(x2, sx, ax, "e4m3")
+        ix = state.slot(slot0)[2]
+        if qx is None:
+            x2 = _fp8_rows(x, "the input")
+            sx, ax, _ = state.slot(slot0)
+            qx = SF.fp8_quantize(x2, sx, ax, "e4m3")
+        else:
+            if qx.dtype != SF.FP8_DTYPE["e4m3"] or qx.shape != x.shape:
+                raise ValueError(f"FP8 linear: the handed-over operand must be E4M3 of the input's shape "
+                                 f"{tuple(x.shape)}, got {qx.dtype} {tuple(qx.shape)}")
+            if not state.fp8_wgrad and x.numel() > 1 and x.stride(-1) == 0:
+                raise ValueError("FP8 linear: without fp8_wgrad the weight gradient reads the 16-bit input; its "
+                                 "producer must keep it (keep16=True)")
+            qx = _fp8_rows(qx, "the input")
         ctx.fp8_wgrad = state.fp8_wgrad
         ctx.save_for_backward(qx if state.fp8_wgrad else x, weight)
         qw, _ = state.weight_q(weight, slot0 + 1)
@@ -234,10 +250,10 @@ class FP8Linear(torch.autograd.Function):
         bias_p = ctx.bias_p if ctx.has_bias else None
         if ctx.fp8_wgrad:        # x is q(x): the wgrad on the FP8 operands, the bias from the 16-bit dY
             dw = _fp8_wgrad(weight, qg, x, ig, state.slot(slot0)[2])
-            return gi, dw, _bias_grad(bias_p, g2), None, None, None
+            return gi, dw, _bias_grad(bias_p, g2), None, None, None, None
         t2 = x.reshape(-1, x.shape[-1])
         dw, db = _wgrad_and_bias(weight, bias_p, g2, t2)
-        return gi, dw, db, None, None, None
+        return gi, dw, db, None, None, None, None
 
 
 def _fp8_wgrad(weight, qg, qx, inv_dy, inv_x):
@@ -259,6 +275,19 @@ def attach_fp8(linears, state: FP8State):
     """Give each linear (Column / RowParallelLinear) its three rows of ``state``'s table."""
     for i, lin in enumerate(linears):
         object.__setattr__(lin, "_fp8", (state, _FP8_SLOTS * i))    # a reference, not a submodule
+
+
+def input_slot(fp8):
+    """(scale, amax) of the input row of a linear's ``_fp8`` = (FP8State, row), for the producer of
+    its input (``SF.*(fp8_out=...)``); None for a 16-bit or an MXFP8 linear."""
+    if fp8 is None or not isinstance(fp8[0], FP8State):
+        return None
+    return fp8[0].slot(fp8[1])[:2]
+
+
+def keeps_input16(fp8) -> bool:
+    """Whether the linear's backward reads its 16-bit input (the 16-bit weight gradient)."""
+    return not fp8[0].fp8_wgrad
 
 
 # --------------------------------------------------------------------------------------------

@@ -44,6 +44,7 @@ from .dense import (DEFERRED_WGRAD, DeferredWgrad, _dgrad_weight_t, _fire, _nbyt
                     _wgrad, _wgrad_and_bias, dgrad, drop_cached_weight_t, flush_deferred_wgrad,
                     gemm_tn_blocks, linear_rows, mm_rows, params_changed)
 # (fp8_linear before decode_weights: the order their caches are registered and so dropped in)
+from .fp8_linear import input_slot as _fp8_input_slot
 from .fp8_linear import (FP8Linear, FP8State, MXFP8Linear, MXFP8Recipe, attach_fp8, attach_mxfp8,  # noqa: F401
                          mx_weight_q)
 from . import decode_weights as _dw
@@ -768,7 +769,11 @@ def vp_lm_head_ce_ok(h, weight, tp: int) -> bool:
 
 def linear_with_grad_accumulation_and_async_allreduce(x, weight, bias, sequence_parallel=False,
                                                       async_grad_allreduce=False, add_bias=True, fp8=None,
-                                                      bias_grad=True):
+                                                      bias_grad=True, qx=None):
+    """``qx``: x already quantised by its producer for this delayed-scaling FP8 linear's input row
+    (``fp8_linear.input_slot``); only ``FP8Linear`` takes it."""
+    if qx is not None and (fp8 is None or isinstance(fp8[0], MXFP8Recipe) or _dw._DECODE["state"] is not None):
+        raise RuntimeError("a quantised input (qx) is for the delayed-scaling FP8 linear (--fp8-e4m3 / --fp8-hybrid)")
     if _dw._DECODE["state"] is not None:    # generate(weight_format=...): unsharded, no gradients
         return _dw._decode_route(_dw._DECODE["state"], x, weight, bias, add_bias, fp8)
     if not bias_grad and (fp8 is not None or sequence_parallel):
@@ -777,7 +782,7 @@ def linear_with_grad_accumulation_and_async_allreduce(x, weight, bias, sequence_
     if fp8 is not None and isinstance(fp8[0], MXFP8Recipe):     # from attach_mxfp8; TP = 1
         return MXFP8Linear.apply(x, weight, bias, add_bias, fp8[0].grad_fmt)
     if fp8 is not None:                 # (FP8State, first table row) from attach_fp8; TP = 1
-        return FP8Linear.apply(x, weight, bias, add_bias, fp8[0], fp8[1])
+        return FP8Linear.apply(x, weight, bias, add_bias, fp8[0], fp8[1], qx)
     if sequence_parallel and _TP_OVERLAP and _tp_size() > 1:
         return _ColumnSPLinear.apply(x, weight, bias, add_bias)
     return LinearWithGradAccumulationAndAsyncCommunication.apply(x, weight, bias, sequence_parallel,
@@ -1598,9 +1603,17 @@ class ColumnParallelLinear(nn.Module):
         else:
             self.register_parameter("bias", None)
 
-    def forward(self, x, bias_grad=True):
+    def fp8_input_slot(self):
+        """(scale, amax) for the producer of this linear's input to quantise it (``forward(qx=)``);
+        None unless this is a delayed-scaling FP8 linear."""
+        return _fp8_input_slot(self._fp8)
+
+    def forward(self, x, bias_grad=True, qx=None):
         """``bias_grad`` False: the caller's next kernel makes this linear's bias gradient
-        (``bias_from_producer``), the backward here makes the weight gradient alone."""
+        (``bias_from_producer``), the backward here makes the weight gradient alone.
+        ``qx``: x already quantised by its producer for ``fp8_input_slot()`` (x is then what the
+        producer returned beside it)."""
+        hand = {} if qx is None else {"qx": qx}     # passed on only when there is one
         if not (self.async_ar or self.sequence_parallel):
             x = copy_to_tensor_model_parallel_region(x)
         if not bias_grad:       # only the plain linear that adds its bias (the fused-QKV projection)
@@ -1609,11 +1622,11 @@ class ColumnParallelLinear(nn.Module):
                                                                   self.async_ar, fp8=self._fp8, bias_grad=False)
         elif self.bias_grad_from_output:
             y = linear_with_grad_accumulation_and_async_allreduce(x, self.weight, self.bias, self.sequence_parallel,
-                                                                  self.async_ar, add_bias=False, fp8=self._fp8)
+                                                                  self.async_ar, add_bias=False, fp8=self._fp8, **hand)
         else:
             b = None if self.skip_bias_add else self.bias
             y = linear_with_grad_accumulation_and_async_allreduce(x, self.weight, b, self.sequence_parallel,
-                                                                  self.async_ar, fp8=self._fp8)
+                                                                  self.async_ar, fp8=self._fp8, **hand)
         if self.gather_output:
             y = gather_from_tensor_model_parallel_region(y)
         if self.skip_bias_add:
@@ -1650,7 +1663,13 @@ class RowParallelLinear(nn.Module):
         else:
             self.register_parameter("bias", None)
 
-    def forward(self, x):
+    def fp8_input_slot(self):
+        """As ``ColumnParallelLinear.fp8_input_slot``."""
+        return _fp8_input_slot(self._fp8)
+
+    def forward(self, x, qx=None):
+        """``qx``: as for ``ColumnParallelLinear.forward``."""
+        hand = {} if qx is None else {"qx": qx}     # passed on only when there is one
         if not self.input_is_parallel:
             x = scatter_to_tensor_model_parallel_region(x)
         if self.sequence_parallel and _TP_OVERLAP:
@@ -1659,7 +1678,8 @@ class RowParallelLinear(nn.Module):
             y = linear_with_grad_accumulation_and_async_allreduce(x, self.weight, None, False, False)
             y = reduce_scatter_to_sequence_parallel_region(y)
         else:
-            y = linear_with_grad_accumulation_and_async_allreduce(x, self.weight, None, False, False, fp8=self._fp8)
+            y = linear_with_grad_accumulation_and_async_allreduce(x, self.weight, None, False, False, fp8=self._fp8,
+                                                                  **hand)
             y = reduce_from_tensor_model_parallel_region(y)
         if self.skip_bias_add:
             return y, self.bias

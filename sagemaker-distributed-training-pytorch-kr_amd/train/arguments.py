@@ -180,6 +180,9 @@ _GROUPS = {
         # ours: the weight-gradient GEMM of the FP8 linears on their FP8 operands (opt-in; the
         # reference's --no-fp8-wgrad below keeps dest fp8_wgrad)
         ("--fp8-wgrad", dict(action="store_true", dest="use_fp8_wgrad")),
+        # ours: the norm and activation kernels write the E4M3 input of the FP8 linear they feed,
+        # which then launches no quantise pass (delayed scaling only, opt-in; same numbers)
+        ("--fp8-fused-quantize", dict(action="store_true")),
         # ours (Megatron-core's name): the Switch MLP of --num-experts with device routing and
         # grouped expert GEMMs, no host sync (models/transformer.SwitchMLP, opt-in)
         ("--moe-grouped-gemm", dict(action="store_true")),
@@ -485,6 +488,17 @@ def validate_args(args, defaults=None):
                       ("it" if len(inert) == 1 else "them")
         if why:
             raise ValueError(f"--fp8-recipe mxfp8 {why}")
+    if getattr(args, "fp8_fused_quantize", False):
+        if not (args.fp8_e4m3 or args.fp8_hybrid):
+            raise ValueError("--fp8-fused-quantize needs FP8 linears: add --fp8-hybrid or --fp8-e4m3")
+        if getattr(args, "fp8_recipe", "delayed") == "mxfp8":
+            raise ValueError("--fp8-fused-quantize with --fp8-recipe mxfp8 is not supported: it hands the producer a "
+                             "delayed per-tensor scale, and MX scales come from the blocks themselves")
+        if args.num_experts:
+            raise ValueError("--fp8-fused-quantize with --num-experts is not supported (the Switch MLP stays 16-bit)")
+        if args.apply_residual_connection_post_layernorm:
+            raise ValueError("--fp8-fused-quantize with --apply-residual-connection-post-layernorm is not supported: "
+                             "the norm output is then the residual too")
     if use_fp8_wgrad and not args.fp8_wgrad:
         raise ValueError("--fp8-wgrad and --no-fp8-wgrad contradict each other: drop one")
     if use_fp8_wgrad and not (args.fp8_e4m3 or args.fp8_hybrid):
@@ -643,7 +657,8 @@ def core_transformer_config_from_args(args) -> TransformerConfig:
         fp8_interval=getattr(args, "fp8_interval", 1),
         fp8_amax_history_len=getattr(args, "fp8_amax_history_len", 1),
         fp8_amax_compute_algo=getattr(args, "fp8_amax_compute_algo", "most_recent"),
-        fp8_recipe=getattr(args, "fp8_recipe", "delayed"))
+        fp8_recipe=getattr(args, "fp8_recipe", "delayed"),
+        fp8_fused_quantize=bool(getattr(args, "fp8_fused_quantize", False)))
 
 
 # ------------------------------------------------------------------------ micro-batch calculator (U2)
