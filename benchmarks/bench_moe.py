@@ -4,7 +4,10 @@ h 1024, f 4096, T = 64 x 1024 tokens, E = 8, bf16. Both arms run in one process,
 (A B A B ...), each timed with device events over ``--iters`` calls after warm-up; one JSON line
 per round and arm, and a summary line with the medians.
 
-    python benchmarks/bench_moe.py [--rounds 5] [--iters 10] [--out bench_out/moe.jsonl]
+    python benchmarks/bench_moe.py [--rounds 5] [--iters 10] [--out bench_out/moe.jsonl] [--topk 2]
+
+``--topk k`` (k >= 2) runs both arms with --moe-router-topk k and adds one JSON line that times the
+moe_combine.hip kernels against the torch compositions they replace, on the layer's own route.
 """
 import argparse
 import json
@@ -17,6 +20,54 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def combine_kernels(a, dev):
+    """name -> [kernel us, torch composition us], medians of ``--rounds`` alternating timings."""
+    from smdt_amd.ops import _ext
+    from smdt_amd.ops import functional as SF
+    T, h, k = a.seq * a.batch, a.hidden, a.topk
+    g = torch.Generator(device=dev).manual_seed(1)
+    top_p, _, row, tok, _, _, _, p_row = SF.moe_route(torch.randn(T, a.experts, device=dev, generator=g), topk=k)
+    y = torch.randn(tok.numel(), h, device=dev, generator=g).to(torch.bfloat16)
+    dout = torch.randn(T, h, device=dev, generator=g).to(torch.bfloat16)
+    rows, wb = row.long(), top_p.to(torch.bfloat16)
+
+    def torch_combine():
+        return sum(y.index_select(0, rows[:, j]) * wb[:, j:j + 1] for j in range(k))
+
+    def torch_scatter():          # the k = 1 backward's two passes, per slot weights looked up per row
+        return _ext.ext().gather_rows(dout, tok) * p_row.unsqueeze(-1).to(dout.dtype)
+
+    def torch_gate():
+        return torch.stack([(dout * y.index_select(0, rows[:, j])).sum(-1) for j in range(k)], 1).float()
+
+    pairs = {"moe_combine": (lambda: SF.moe_combine(y, row, top_p), torch_combine),
+             "moe_combine_unit": (lambda: SF.moe_combine(y, row), lambda: sum(y.index_select(0, rows[:, j])
+                                                                              for j in range(k))),
+             "moe_scatter_scaled": (lambda: SF.moe_scatter_scaled(dout, tok, p_row), torch_scatter),
+             "moe_gate_grad": (lambda: SF.moe_gate_grad(dout, y, row), torch_gate)}
+
+    def timed(fn):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(a.iters):
+            fn()
+        e.record()
+        e.synchronize()
+        return s.elapsed_time(e) / a.iters * 1e3
+
+    res = {}
+    for name, fns in pairs.items():
+        for fn in fns:
+            for _ in range(3):
+                fn()
+        ts = [[], []]
+        for _ in range(a.rounds):
+            for i, fn in enumerate(fns):
+                ts[i].append(timed(fn))
+        res[name] = [round(statistics.median(t), 2) for t in ts]
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--hidden", type=int, default=1024)
@@ -27,6 +78,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--topk", type=int, default=1)
     a = ap.parse_args()
     from smdt_amd.models.transformer import SwitchMLP, TransformerConfig
     from smdt_amd.parallel import state as ps
@@ -35,7 +87,7 @@ def main():
     dev = "cuda"
     kw = dict(num_layers=2, hidden_size=a.hidden, ffn_hidden_size=a.ffn, num_attention_heads=a.hidden // 64,
               max_position_embeddings=a.seq, padded_vocab_size=1024, hidden_dropout=0.0, attention_dropout=0.0,
-              seed=3, num_experts=a.experts, params_dtype=torch.bfloat16)
+              seed=3, num_experts=a.experts, params_dtype=torch.bfloat16, moe_router_topk=a.topk)
     arms = {"per_expert_loop": SwitchMLP(TransformerConfig(**kw), 1, device=dev)}
     arms["moe_grouped_gemm"] = SwitchMLP(TransformerConfig(**kw, moe_grouped_gemm=True), 1, device=dev)
     with torch.no_grad():
@@ -76,11 +128,16 @@ def main():
             print(line, flush=True)
             if out:
                 out.write(line + "\n")
+    if a.topk > 1:
+        line = json.dumps({"combine_kernels_us": combine_kernels(a, dev), "topk": a.topk})
+        print(line, flush=True)
+        if out:
+            out.write(line + "\n")
     counts = arms["moe_grouped_gemm"].last_counts.tolist()
     line = json.dumps({"summary": {k: round(statistics.median(v), 4) for k, v in ms.items()},
                        "spread": {k: [round(min(v), 4), round(max(v), 4)] for k, v in ms.items()},
                        "tokens_per_expert": counts, "hidden": a.hidden, "ffn": a.ffn,
-                       "tokens": a.seq * a.batch, "experts": a.experts, "device": torch.cuda.get_device_name(0)})
+                       "tokens": a.seq * a.batch, "experts": a.experts, "topk": a.topk, "device": torch.cuda.get_device_name(0)})
     print(line, flush=True)
     if out:
         out.write(line + "\n")

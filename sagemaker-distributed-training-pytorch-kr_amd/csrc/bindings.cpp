@@ -728,6 +728,106 @@ void moe_route_into(Tensor logits, Tensor top_p, Tensor top_e, Tensor row_of, Te
         "moe_route");
 }
 
+// Top-k routing (--moe-router-topk, 2 <= k <= min(8, E)) into the layout of smdt_moe_rows(T * k, E).
+// Fills (top_p fp32 [T, k], expert_of_token int32 [T, k], row_of_token int32 [T, k], token_of_row
+// int64 [R], tile_expert int32 [R / 256], seg int32 [E, 2], counts int32 [E], p_of_row fp32 [R]):
+// caller-made buffers with any prior contents, every word is overwritten.
+void moe_route_topk_into(Tensor logits, int64_t k, Tensor top_p, Tensor top_e, Tensor row_of, Tensor tok_of,
+                         Tensor tile_e, Tensor seg, Tensor counts, Tensor p_row) {
+  need_contig(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) > 0 && logits.size(1) > 0 && logits.size(1) <= 64,
+              "moe_route_topk: logits must be [T, E] with E <= 64");
+  const int64_t T = logits.size(0), E = logits.size(1);
+  TORCH_CHECK(k >= 2 && k <= 8 && k <= E, "moe_route_topk: topk must be in 2 .. min(8, E), got ", k, " with E = ", E);
+  const int64_t R = smdt_moe_rows(T * k, E);
+  auto ok = [&](const Tensor& t, at::ScalarType ty, int64_t n) {
+    return t.is_cuda() && t.is_contiguous() && t.scalar_type() == ty && t.numel() == n && t.device() == logits.device();
+  };
+  TORCH_CHECK(ok(top_p, at::kFloat, T * k) && ok(top_e, at::kInt, T * k) && ok(row_of, at::kInt, T * k) &&
+                  ok(tok_of, at::kLong, R) && ok(tile_e, at::kInt, R / 256) && ok(seg, at::kInt, 2 * E) &&
+                  ok(counts, at::kInt, E) && ok(p_row, at::kFloat, R),
+              "moe_route_topk_into: table buffer mismatch");
+  Tensor hist = torch::empty({(T + 255) / 256, E}, logits.options().dtype(at::kInt));
+  check(smdt_moe_route_topk(dcode(logits), logits.data_ptr(), T, E, (int)k, top_p.data_ptr<float>(),
+                            top_e.data_ptr<int>(), row_of.data_ptr<int>(), tok_of.data_ptr<int64_t>(),
+                            tile_e.data_ptr<int>(), seg.data_ptr<int>(), counts.data_ptr<int>(),
+                            p_row.data_ptr<float>(), hist.data_ptr<int>(), cur_stream()),
+        "moe_route_topk");
+}
+
+// The same into tables allocated here (uninitialised; every word is written).
+std::vector<Tensor> moe_route_topk(Tensor logits, int64_t k) {
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) > 0, "moe_route_topk: logits must be [T, E]");
+  const int64_t T = logits.size(0), E = logits.size(1), R = smdt_moe_rows(T * std::max<int64_t>(k, 1), E);
+  auto i32 = logits.options().dtype(at::kInt), f32 = logits.options().dtype(at::kFloat);
+  std::vector<Tensor> t = {torch::empty({T, k}, f32), torch::empty({T, k}, i32), torch::empty({T, k}, i32),
+                           torch::empty({R}, logits.options().dtype(at::kLong)), torch::empty({R / 256}, i32),
+                           torch::empty({E, 2}, i32), torch::empty({E}, i32), torch::empty({R}, f32)};
+  moe_route_topk_into(logits, k, t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7]);
+  return t;
+}
+
+// moe_combine.hip: y / dys [R, h] in the padded layout, out / dout [T, h], row_of_token int32 [T, k].
+static void moe_combine_check(const Tensor& a, int64_t T, int64_t R, int64_t k, const char* what) {
+  TORCH_CHECK(a.is_cuda() && a.dim() == 2 && (a.scalar_type() == at::kBFloat16 || a.scalar_type() == at::kHalf),
+              what, ": rows must be a 2-D bf16 / fp16 GPU tensor");
+  TORCH_CHECK(smdt_moe_combine_supported(dcode(a), T, R, a.size(1), (int)k), what, ": unsupported shape (T ", T, ", R ",
+              R, ", h ", a.size(1), ", k ", k, "): h must be a multiple of 8, 1 <= k <= 8, T * k and R below 2^31");
+}
+static void moe_table_check(const Tensor& t, const Tensor& like, at::ScalarType ty, const char* what) {
+  TORCH_CHECK(t.is_contiguous() && t.scalar_type() == ty && t.device() == like.device(), what,
+              ": table of the wrong type, layout or device");
+}
+
+Tensor moe_combine(Tensor y, Tensor row_of_token, c10::optional<Tensor> w) {
+  need_contig(y, "y");
+  TORCH_CHECK(row_of_token.dim() == 2, "moe_combine: row_of_token must be [T, k]");
+  const int64_t T = row_of_token.size(0), k = row_of_token.size(1);
+  moe_combine_check(y, T, y.size(0), k, "moe_combine");
+  moe_table_check(row_of_token, y, at::kInt, "moe_combine row_of_token");
+  if (w.has_value()) {
+    moe_table_check(*w, y, at::kFloat, "moe_combine w");
+    TORCH_CHECK(w->numel() == T * k, "moe_combine: w must be [T, k]");
+  }
+  Tensor out = torch::empty({T, y.size(1)}, y.options());
+  check(smdt_moe_combine_fwd(dcode(y), y.data_ptr(), row_of_token.data_ptr<int>(),
+                             w.has_value() ? w->data_ptr<float>() : nullptr, out.data_ptr(), T, y.size(0), y.size(1),
+                             (int)k, cur_stream()),
+        "moe_combine");
+  return out;
+}
+
+Tensor moe_scatter_scaled(Tensor dout, Tensor token_of_row, Tensor p_of_row) {
+  need_contig(dout, "dout");
+  const int64_t T = dout.size(0), R = token_of_row.numel();
+  moe_combine_check(dout, T, R, 1, "moe_scatter_scaled");
+  moe_table_check(token_of_row, dout, at::kLong, "moe_scatter_scaled token_of_row");
+  moe_table_check(p_of_row, dout, at::kFloat, "moe_scatter_scaled p_of_row");
+  TORCH_CHECK(p_of_row.numel() == R, "moe_scatter_scaled: p_of_row must have one weight per row");
+  Tensor dys = torch::empty({R, dout.size(1)}, dout.options());
+  check(smdt_moe_scatter_scaled(dcode(dout), dout.data_ptr(), token_of_row.data_ptr<int64_t>(),
+                                p_of_row.data_ptr<float>(), dys.data_ptr(), T, R, dout.size(1), cur_stream()),
+        "moe_scatter_scaled");
+  return dys;
+}
+
+Tensor moe_gate_grad(Tensor dout, Tensor y, Tensor row_of_token) {
+  need_contig(dout, "dout");
+  need_contig(y, "y");
+  TORCH_CHECK(row_of_token.dim() == 2 && row_of_token.size(0) == dout.size(0), "moe_gate_grad: row_of_token must be [T, k]");
+  const int64_t T = dout.size(0), k = row_of_token.size(1);
+  moe_combine_check(y, T, y.size(0), k, "moe_gate_grad");
+  TORCH_CHECK(dout.dim() == 2 && dout.scalar_type() == y.scalar_type() && dout.size(1) == y.size(1) &&
+                  dout.device() == y.device(),
+              "moe_gate_grad: dout must be [T, h] of y's type on y's device");
+  moe_table_check(row_of_token, y, at::kInt, "moe_gate_grad row_of_token");
+  Tensor dp = torch::empty({T, k}, y.options().dtype(at::kFloat));
+  check(smdt_moe_gate_grad(dcode(y), dout.data_ptr(), y.data_ptr(), row_of_token.data_ptr<int>(), dp.data_ptr<float>(),
+                           T, y.size(0), y.size(1), (int)k, cur_stream()),
+        "moe_gate_grad");
+  return dp;
+}
+
 // The device table of the base pointers of same-shaped, same-typed contiguous GPU tensors (one per
 // expert) that gemm_tn_grouped picks its B / bias from. The caller keeps the tensors alive and
 // rebuilds the table when one of them is reallocated.
@@ -2072,6 +2172,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_tn_shape_supported", [](int64_t M, int64_t N, int64_t K) { return smdt_gemm_tn_supported(M, N, K) != 0; });
   m.def("moe_route", &moe_route);
   m.def("moe_route_into", &moe_route_into);
+  m.def("moe_route_topk", &moe_route_topk);
+  m.def("moe_route_topk_into", &moe_route_topk_into);
+  m.def("moe_combine", &moe_combine);
+  m.def("moe_scatter_scaled", &moe_scatter_scaled);
+  m.def("moe_gate_grad", &moe_gate_grad);
+  m.def("moe_combine_supported", [](int64_t dtype, int64_t T, int64_t R, int64_t h, int64_t k) {
+    return smdt_moe_combine_supported((int)dtype, T, R, h, (int)k) != 0;
+  });
   m.def("ptr_table", &ptr_table);
   m.def("gemm_tn_grouped", &gemm_tn_grouped, arg("a"), arg("btab"), arg("n"), arg("tile_expert"), arg("epi") = 0,
         arg("biastab") = pybind11::none(), arg("aux") = pybind11::none(), arg("sums") = false,

@@ -365,6 +365,29 @@ int64_t smdt_moe_rows(int64_t T, int64_t E);
 hipError_t smdt_moe_route(int dtype, const void* logits, int64_t T, int64_t E, float* top_p, int* expert_of_token,
                           int* row_of_token, int64_t* token_of_row, int* tile_expert, int* seg, int* counts,
                           int* hist, hipStream_t st);
+// The top-k form (--moe-router-topk, 2 <= k <= min(8, E)): T * k assignments in the layout of
+// smdt_moe_rows(T * k, E). top_p / expert_of_token / row_of_token are [T, k] (slot 0 the largest
+// logit, a tie to the lower index; top_p the softmax over the k selected logits), token_of_row
+// [R] as above, p_of_row fp32 [R] the gate weight of the row's assignment (0 on pad rows). hist:
+// ceil(T / 256) * E words. The same three launches, no atomics, every word written.
+hipError_t smdt_moe_route_topk(int dtype, const void* logits, int64_t T, int64_t E, int k, float* top_p,
+                               int* expert_of_token, int* row_of_token, int64_t* token_of_row, int* tile_expert,
+                               int* seg, int* counts, float* p_of_row, int* hist, hipStream_t st);
+
+// moe_combine.hip: rows out of the padded layout and back into it when a token owns k rows.
+// dtype 1 / 2, h % 8 == 0, 1 <= k <= 8, T * k and R below 2^31 (smdt_moe_combine_supported).
+//   combine_fwd:    out[t] = sum_j w[t, j] * y[row_of_token[t, j]] in fp32, slot order, one
+//                   rounding; w null = weights of 1 (the dx combine of the backward)
+//   scatter_scaled: dys[r] = p_of_row[r] * dout[token_of_row[r]], zeros on pad rows (every row
+//                   written once)
+//   gate_grad:      dp[t, j] = <dout[t], y[row_of_token[t, j]]> in fp32, one wave per token
+int smdt_moe_combine_supported(int dtype, int64_t T, int64_t R, int64_t h, int k);
+hipError_t smdt_moe_combine_fwd(int dtype, const void* y, const int* row_of_token, const float* w, void* out,
+                                int64_t T, int64_t R, int64_t h, int k, hipStream_t st);
+hipError_t smdt_moe_scatter_scaled(int dtype, const void* dout, const int64_t* token_of_row, const float* p_of_row,
+                                   void* dys, int64_t T, int64_t R, int64_t h, hipStream_t st);
+hipError_t smdt_moe_gate_grad(int dtype, const void* dout, const void* y, const int* row_of_token, float* dp,
+                              int64_t T, int64_t R, int64_t h, int k, hipStream_t st);
 
 // wgrad_gemm.hip: main_grad[N, K] (fp32) += dy[M, N]^T . x[M, K] (bf16, or fp16 with dtype 2)
 int smdt_wgrad_supported(int64_t M, int64_t N, int64_t K);

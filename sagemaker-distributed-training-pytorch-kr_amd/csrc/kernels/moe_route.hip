@@ -25,6 +25,9 @@
 //   3. route_place: every block ranks its own tokens again with the same ballots (an in-block
 //      exclusive scan per expert), writes row_of_token / token_of_row, and the blocks together
 //      fill the pad rows of token_of_row with -1.
+//
+// The top-k form (smdt_moe_route_topk, --moe-router-topk) follows the top-1 kernels below: the
+// per-token tables become [T, k], the layout that of T * k assignments, and p_of_row[R] is new.
 #include "common.h"
 #include "launchers.h"
 
@@ -143,6 +146,136 @@ __global__ __launch_bounds__(kB) void route_place_kernel(const int* __restrict__
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Top-k form (--moe-router-topk, 2 <= k <= 8): T * k assignments in the layout of
+// smdt_moe_rows(T * k, E), the same three launches. A token's k experts are distinct, so it holds
+// at most one row per expert and the rows of a segment are still ordered by token: the in-block
+// rank for expert x is one ballot of "x is among my experts" (a 64-bit mask per thread), E ballots
+// in all, not k * E. route_scan_kernel serves as it is (it only sees counts).
+constexpr int kMaxK = 8;
+
+// Per-wave counts wcnt[4][kMaxE] of the threads whose mask `mine` holds expert x, and in rk[j] the
+// rank of this thread among the block's earlier tokens that hold expert e[j]. Ends with a barrier
+// (the caller reads wcnt after it).
+__device__ __forceinline__ void block_rank_mask(unsigned long long mine, const int (&e)[kMaxK], int k, int E,
+                                                int* wcnt, int (&rk)[kMaxK]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+  for (int j = 0; j < kMaxK; ++j) rk[j] = 0;
+  for (int x = 0; x < E; ++x) {
+    const unsigned long long m = __ballot((int)((mine >> x) & 1ull));
+    if (lane == 0) wcnt[wave * kMaxE + x] = __popcll(m);
+    const int r = __popcll(m & below);
+#pragma unroll
+    for (int j = 0; j < kMaxK; ++j)
+      if (j < k && e[j] == x) rk[j] = r;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < kMaxK; ++j)
+    if (j < k && mine)
+      for (int w = 0; w < wave; ++w) rk[j] += wcnt[w * kMaxE + e[j]];
+}
+
+// 256 tokens per block: k selection passes over the token's E logits in fp32 (strict >, so a tie
+// stays with the lower index; an expert already taken is skipped by its mask bit), the gate
+// weights exp(l_j - l_0) / sum_i exp(l_i - l_0) summed in slot order, then the block's histogram.
+template <class T>
+__global__ __launch_bounds__(kB) void route_topk_kernel(const T* __restrict__ logits, int Tn, int E, int k,
+                                                        float* __restrict__ top_p, int* __restrict__ top_e,
+                                                        int* __restrict__ hist) {
+  __shared__ int wcnt[4 * kMaxE];
+  const int t = blockIdx.x * kB + threadIdx.x;
+  unsigned long long mine = 0ull;
+  if (t < Tn) {
+    const T* row = logits + (int64_t)t * E;
+    float l[kMaxK];
+    int e[kMaxK];
+#pragma unroll
+    for (int j = 0; j < kMaxK; ++j) {
+      l[j] = 0.f;
+      e[j] = -1;
+      if (j < k) {
+        float m = 0.f;
+        int best = -1;
+        for (int i = 0; i < E; ++i) {
+          if ((mine >> i) & 1ull) continue;
+          const float v = to_f32(row[i]);
+          if (best < 0 || v > m) {
+            m = v;
+            best = i;
+          }
+        }
+        l[j] = m;
+        e[j] = best;          // k <= E: an expert is always left
+        mine |= 1ull << best;
+      }
+    }
+    float p[kMaxK];
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < kMaxK; ++j)
+      if (j < k) {
+        p[j] = expf(l[j] - l[0]);
+        s += p[j];
+      }
+#pragma unroll
+    for (int j = 0; j < kMaxK; ++j)
+      if (j < k) {
+        top_p[(int64_t)t * k + j] = p[j] / s;
+        top_e[(int64_t)t * k + j] = e[j];
+      }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int x = 0; x < E; ++x) {
+    const unsigned long long m = __ballot((int)((mine >> x) & 1ull));
+    if (lane == 0) wcnt[wave * kMaxE + x] = __popcll(m);
+  }
+  __syncthreads();
+  if (threadIdx.x < E) {
+    const int x = threadIdx.x;
+    hist[blockIdx.x * E + x] = wcnt[x] + wcnt[kMaxE + x] + wcnt[2 * kMaxE + x] + wcnt[3 * kMaxE + x];
+  }
+}
+
+__global__ __launch_bounds__(kB) void route_place_topk_kernel(
+    const int* __restrict__ top_e, const float* __restrict__ top_p, const int* __restrict__ first,
+    const int* __restrict__ counts, const int* __restrict__ seg, const int* __restrict__ tile_expert, int Tn, int E,
+    int k, int R, int* __restrict__ row_of_token, int64_t* __restrict__ token_of_row, float* __restrict__ p_of_row) {
+  __shared__ int wcnt[4 * kMaxE];
+  const int t = blockIdx.x * kB + threadIdx.x;
+  int e[kMaxK], rk[kMaxK];
+  unsigned long long mine = 0ull;
+#pragma unroll
+  for (int j = 0; j < kMaxK; ++j) {
+    e[j] = -1;
+    if (j < k && t < Tn) {
+      e[j] = top_e[(int64_t)t * k + j];
+      mine |= 1ull << e[j];
+    }
+  }
+  block_rank_mask(mine, e, k, E, wcnt, rk);
+#pragma unroll
+  for (int j = 0; j < kMaxK; ++j)
+    if (j < k && t < Tn) {
+      const int r = first[blockIdx.x * E + e[j]] + rk[j];
+      row_of_token[(int64_t)t * k + j] = r;
+      if (r >= 0 && r < R) {
+        token_of_row[r] = t;
+        p_of_row[r] = top_p[(int64_t)t * k + j];
+      }
+    }
+  // the pad rows (no assignment writes them): past the rows of their segment, or in a tail tile
+  for (int r = blockIdx.x * kB + threadIdx.x; r < R; r += gridDim.x * kB) {
+    const int x = tile_expert[r >> 8];
+    if (x < 0 || r >= seg[2 * x] + counts[x]) {
+      token_of_row[r] = -1;
+      p_of_row[r] = 0.f;
+    }
+  }
+}
+
 }  // namespace moe
 }  // namespace smdt
 
@@ -169,5 +302,30 @@ extern "C" hipError_t smdt_moe_route(int dtype, const void* logits, int64_t T, i
                      seg, tile_expert);
   hipLaunchKernelGGL(moe::route_place_kernel, dim3(nblk), dim3(moe::kB), 0, st, expert_of_token, hist, counts, seg,
                      tile_expert, (int)T, (int)E, (int)R, row_of_token, token_of_row);
+  return hipGetLastError();
+}
+
+// hist: int32 scratch of ceil(T / 256) * E words.
+extern "C" hipError_t smdt_moe_route_topk(int dtype, const void* logits, int64_t T, int64_t E, int k, float* top_p,
+                                          int* expert_of_token, int* row_of_token, int64_t* token_of_row,
+                                          int* tile_expert, int* seg, int* counts, float* p_of_row, int* hist,
+                                          hipStream_t st) {
+  if (T <= 0 || E <= 0 || E > moe::kMaxE || dtype < 0 || dtype > 2) return hipErrorInvalidValue;
+  if (k < 2 || k > moe::kMaxK || k > E) return hipErrorInvalidValue;
+  if (T * k >= (1ll << 31) || T * E >= (1ll << 31)) return hipErrorInvalidValue;
+  const int64_t R = smdt_moe_rows(T * k, E);
+  if (R >= (1ll << 31)) return hipErrorInvalidValue;
+  const int nblk = (int)((T + moe::kB - 1) / moe::kB);
+#define SMDT_RT(TY)                                                                                              \
+  hipLaunchKernelGGL((moe::route_topk_kernel<TY>), dim3(nblk), dim3(moe::kB), 0, st, (const TY*)logits, (int)T, \
+                     (int)E, k, top_p, expert_of_token, hist)
+  if (dtype == 0) SMDT_RT(float);
+  else if (dtype == 1) SMDT_RT(bf16);
+  else SMDT_RT(f16);
+#undef SMDT_RT
+  hipLaunchKernelGGL(moe::route_scan_kernel, dim3(1), dim3(64), 0, st, hist, nblk, (int)E, (int)(R / 256), counts,
+                     seg, tile_expert);
+  hipLaunchKernelGGL(moe::route_place_topk_kernel, dim3(nblk), dim3(moe::kB), 0, st, expert_of_token, top_p, hist,
+                     counts, seg, tile_expert, (int)T, (int)E, k, (int)R, row_of_token, token_of_row, p_of_row);
   return hipGetLastError();
 }

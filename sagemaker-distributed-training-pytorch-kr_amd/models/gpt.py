@@ -301,8 +301,11 @@ def gpt_flops_per_token(cfg: TransformerConfig, seq_len: int, recompute: bool = 
         qkv = h * (cfg.num_attention_heads + 2 * cfg.num_query_groups) * hd
         proj = cfg.num_attention_heads * hd * h
         ff = h * cfg.ffn_hidden_size * (3 if cfg.activation == "swiglu" else 2)
-        per_layer = 6 * (qkv + proj + ff) + 12 * seq_len * cfg.num_attention_heads * hd
+        per_layer = 6 * (qkv + proj + cfg.moe_router_topk * ff) + 12 * seq_len * cfg.num_attention_heads * hd
         f = L * per_layer + 6 * h * V
+    elif cfg.moe_router_topk > 1:
+        # --moe-router-topk: a token runs k expert MLPs; the MLP term is 48 of the 72 L h^2
+        f += (cfg.moe_router_topk - 1) * 48.0 * L * h * h
     return f * (4.0 / 3.0 if recompute else 1.0)
 
 

@@ -55,6 +55,7 @@ class TransformerConfig:
     activation: str = "gelu"                     # gelu | swiglu | squared_relu | gelu_erf
     num_experts: Optional[int] = None            # --num-experts: Switch MLP (top-1 routed experts)
     moe_grouped_gemm: bool = False               # --moe-grouped-gemm: device routing + grouped expert GEMMs
+    moe_router_topk: int = 1                     # --moe-router-topk: experts per token, 1 .. min(8, num_experts)
     add_bias_linear: bool = True
     position_embedding_type: str = "learned_absolute"   # or "rope"
     rotary_percent: float = 1.0
@@ -125,6 +126,10 @@ class TransformerConfig:
                                  "(the norm output is then the residual too)")
         if self.moe_grouped_gemm and not self.num_experts:
             raise ValueError("moe_grouped_gemm needs num_experts")
+        if self.moe_router_topk != 1:
+            if not self.num_experts:
+                raise ValueError("moe_router_topk needs num_experts")
+            SF.moe_topk_check(self.moe_router_topk, self.num_experts)
         if self.num_query_groups is None:
             self.num_query_groups = self.num_attention_heads
         if self.kv_channels is None:
@@ -764,7 +769,15 @@ class SwitchMLP(nn.Module):
     experts' GEMMs are grouped launches that pick their weight per 256-row tile from device tables
     (gemm_tn.hip GROUPED, wgrad_gemm.hip's ranged kernel): no host sync, launch shapes independent
     of the routing, so the step can be captured (train/graphs.CapturedStep). Same parameters and
-    checkpoint layout. Where a condition fails the layer raises; it never falls back."""
+    checkpoint layout. Where a condition fails the layer raises; it never falls back.
+
+    ``--moe-router-topk k`` (2 <= k <= min(8, E)): every token goes to its k largest router logits
+    and its output is the gate-weighted sum of the k expert outputs, the gate weights the softmax
+    over the k selected logits (Megatron-core's default, Mixtral's rule). k = 1 keeps the Switch
+    rule: the probability over all E experts, not renormalised. Without --moe-grouped-gemm this is
+    plain torch (``_forward_topk``); with it the router, the combine and its backward are HIP
+    kernels (moe_route.hip's top-k form, moe_combine.hip). No auxiliary load-balancing loss, no
+    capacity limit or token dropping, no expert-parallel group."""
 
     def __init__(self, cfg: TransformerConfig, layer_number: int, device=None):
         super().__init__()
@@ -783,8 +796,14 @@ class SwitchMLP(nn.Module):
         self._tabs = None      # --moe-grouped-gemm: the experts' pointer tables, built at first use
 
     def route(self, flat):
-        """(top-1 probability [n] fp32, expert index [n]) of each token row."""
-        prob = torch.softmax(F.linear(flat, self.router, self.router_bias).float(), dim=-1)
+        """(top-1 probability [n] fp32, expert index [n]) of each token row. With moe_router_topk
+        k >= 2: (gate weights [n, k] fp32, the softmax over the k selected logits; expert indices
+        [n, k], the largest logit first, a tie to the lower index)."""
+        logits = F.linear(flat, self.router, self.router_bias).float()
+        if self.cfg.moe_router_topk > 1:
+            top_e, sel = SF.moe_topk_select(logits, self.cfg.moe_router_topk)
+            return torch.softmax(sel, dim=-1), top_e
+        prob = torch.softmax(logits, dim=-1)
         return prob.max(dim=-1)
 
     def _grouped_check(self, flat):
@@ -803,7 +822,7 @@ class SwitchMLP(nn.Module):
         kern = _ext.use_kernels(flat)
         if why is None and kern:
             T, h, f, E = flat.shape[0], cfg.hidden_size, cfg.ffn_hidden_size, len(self.experts)
-            R = SF.moe_rows(T, E)
+            R = SF.moe_rows(T * cfg.moe_router_topk, E)
             C = _ext.ext()
             probe = self.experts[0]
             if flat.dtype not in (torch.bfloat16, torch.float16) or probe.fc1.weight.dtype != flat.dtype:
@@ -826,10 +845,14 @@ class SwitchMLP(nn.Module):
         flat = x.reshape(s * b, h)
         kern = self._grouped_check(flat)
         logits = F.linear(flat, self.router, self.router_bias)
-        route = SF.moe_route(logits)
+        k = self.cfg.moe_router_topk
+        route = SF.moe_route(logits) if k == 1 else SF.moe_route(logits, topk=k)
         self.last_counts = route[6]      # tokens per expert of the last call (device, int32)
-        # the router's gradient: autograd through the softmax, at the expert the tables picked
-        top_p = torch.softmax(logits.float(), dim=-1).gather(1, route[1].long().unsqueeze(1)).squeeze(1)
+        # the router's gradient: autograd through the softmax, at the expert(s) the tables picked
+        if k == 1:
+            top_p = torch.softmax(logits.float(), dim=-1).gather(1, route[1].long().unsqueeze(1)).squeeze(1)
+        else:
+            top_p = torch.softmax(logits.float().gather(1, route[1].long()), dim=-1)
         ex = self.experts
         w1, b1 = [e.fc1.weight for e in ex], [e.fc1.bias for e in ex]
         w2, b2 = [e.fc2.weight for e in ex], [e.fc2.bias for e in ex]
@@ -842,12 +865,36 @@ class SwitchMLP(nn.Module):
         out = moe_experts.GroupedSwitchExperts.apply(flat, top_p, route, tabs, len(ex), *w1, *b1, *w2, *b2)
         return out.view(s, b, h), None
 
+    def _forward_topk(self, flat, top_p, top_e):
+        """moe_router_topk >= 2 in plain torch (host syncs, any TP size): the n * k assignments are
+        sorted by expert, each expert runs its slice, and a token's k outputs are summed in fp32
+        with its gate weights. The CPU path, and the reference of the grouped top-k path."""
+        n, k = top_e.shape
+        flat_e = top_e.reshape(-1)
+        order = torch.argsort(flat_e, stable=True)
+        counts = torch.bincount(flat_e, minlength=len(self.experts)).tolist()
+        xs = flat.index_select(0, order // k)
+        outs, o = [], 0
+        for i, c in enumerate(counts):
+            if c == 0:
+                continue          # an expert with no tokens gets no gradient this step
+            y, yb = self.experts[i](xs[o:o + c].unsqueeze(1))
+            y = y.squeeze(1)
+            outs.append(y + yb if yb is not None else y)
+            o += c
+        inv = torch.empty_like(order)
+        inv[order] = torch.arange(order.numel(), device=order.device)
+        u = torch.cat(outs).index_select(0, inv).view(n, k, -1)
+        return (u.float() * top_p.unsqueeze(-1)).sum(1).to(flat.dtype)
+
     def forward(self, x):
         if self.cfg.moe_grouped_gemm:
             return self._forward_grouped(x)
         s, b, h = x.shape
         flat = x.reshape(s * b, h)
         top_p, top_e = self.route(flat)
+        if self.cfg.moe_router_topk > 1:
+            return self._forward_topk(flat, top_p, top_e).view(s, b, h), None
         order = torch.argsort(top_e, stable=True)
         counts = torch.bincount(top_e, minlength=len(self.experts)).tolist()
         xs = flat.index_select(0, order)

@@ -2281,8 +2281,70 @@ def moe_rows(T: int, E: int) -> int:
     return (T // MOE_TILE + E) * MOE_TILE
 
 
-def moe_route_ref(logits):
+MOE_MAX_TOPK = 8
+
+
+def moe_topk_check(topk, E) -> int:
+    """``topk`` as an int, or a ValueError naming the limit: 1 <= k <= min(8, E)."""
+    k = int(topk)
+    if not 1 <= k <= min(MOE_MAX_TOPK, int(E)):
+        raise ValueError(f"moe_router_topk must be in 1 .. min({MOE_MAX_TOPK}, num_experts = {E}), got {topk}")
+    return k
+
+
+def moe_topk_select(lf, k: int):
+    """The k largest of each row of fp32 logits [T, E], largest first, a tie to the lower index:
+    (experts int64 [T, k], their logits [T, k], differentiable through the gather)."""
+    T, E = lf.shape
+    ar = torch.arange(E, device=lf.device).expand(T, E)
+    taken = torch.zeros(T, E, dtype=torch.bool, device=lf.device)
+    val = lf.detach()
+    picks = []
+    for _ in range(k):
+        m = val.masked_fill(taken, float("-inf")).max(dim=-1, keepdim=True).values
+        e = torch.where((val == m) & ~taken, ar, E).min(dim=-1).values
+        picks.append(e)
+        taken = taken | (ar == e.unsqueeze(1))
+    experts = torch.stack(picks, dim=1)
+    return experts, lf.gather(1, experts)
+
+
+def _moe_route_topk_ref(logits, k):
+    T, E = logits.shape
+    dev = logits.device
+    R = moe_rows(T * k, E)
+    top_e, sel = moe_topk_select(logits.float(), k)
+    ex = torch.exp(sel - sel[:, :1])
+    s = ex[:, 0].clone()
+    for j in range(1, k):                       # the kernel's order: slot by slot
+        s = s + ex[:, j]
+    top_p = ex / s.unsqueeze(1)
+    flat_e = top_e.reshape(-1)                  # assignment a = t * k + j
+    counts = torch.bincount(flat_e, minlength=E)
+    rows = (counts + MOE_TILE - 1) // MOE_TILE * MOE_TILE
+    start = torch.cumsum(rows, 0) - rows
+    order = torch.argsort(flat_e, stable=True)  # by expert, then by token: a token has one row per expert
+    first = torch.cumsum(counts, 0) - counts
+    se = flat_e[order]
+    dest = start[se] + (torch.arange(T * k, device=dev) - first[se])
+    row_of_token = torch.empty(T * k, dtype=torch.long, device=dev)
+    row_of_token[order] = dest
+    token_of_row = torch.full((R,), -1, dtype=torch.long, device=dev)
+    token_of_row[dest] = order // k
+    p_of_row = torch.zeros(R, dtype=torch.float32, device=dev)
+    p_of_row[dest] = top_p.reshape(-1)[order]
+    tile_expert = torch.full((R // MOE_TILE,), -1, dtype=torch.int32, device=dev)
+    for e, (s0, r) in enumerate(zip(start.tolist(), rows.tolist())):
+        tile_expert[s0 // MOE_TILE:(s0 + r) // MOE_TILE] = e
+    seg = torch.stack([start, rows], dim=1).to(torch.int32)
+    return (top_p, top_e.to(torch.int32), row_of_token.view(T, k).to(torch.int32), token_of_row, tile_expert, seg,
+            counts.to(torch.int32), p_of_row)
+
+
+def moe_route_ref(logits, topk: int = 1):
     """Torch twin of ``moe_route``: the identical tables (it reads the counts on the host)."""
+    if topk != 1:
+        return _moe_route_topk_ref(logits, moe_topk_check(topk, logits.shape[1]))
     T, E = logits.shape
     dev = logits.device
     R = moe_rows(T, E)
@@ -2309,19 +2371,94 @@ def moe_route_ref(logits):
             counts.to(torch.int32))
 
 
-def moe_route(logits):
+def moe_route(logits, topk: int = 1):
     """Top-1 routing of router logits [T, E] (E <= 64) into the expert-sorted, tile-padded layout of
     ``moe_rows(T, E)`` rows, with no host sync on the kernel path. Returns (top_p fp32 [T],
     expert_of_token int32 [T], row_of_token int32 [T], token_of_row int64 [R] with -1 on pad rows,
     tile_expert int32 [R / 256] with -1 on unused tail tiles, seg int32 [E, 2] = (start, rows),
     counts int32 [E]). Tokens keep their order inside a segment; a tie goes to the lowest index.
-    Not differentiable: the router's gradient flows through the caller's own softmax."""
+    Not differentiable: the router's gradient flows through the caller's own softmax.
+
+    ``topk`` = k in 2 .. min(8, E) (--moe-router-topk): a token's experts are its k largest logits
+    in fp32 (slot 0 the largest, a tie to the lower index), laid out as T * k assignments in
+    ``moe_rows(T * k, E)`` rows, inside a segment ordered by token. The per-token tables are
+    [T, k], ``counts`` counts assignments, and an eighth table follows: p_of_row fp32 [R], the gate
+    weight of each row's assignment (0 on pad rows). The gate weights differ from k = 1: there
+    top_p is the softmax probability over all E experts (the Switch rule, not renormalised); for
+    k >= 2 it is the softmax over the k selected logits (Megatron-core's default, Mixtral's rule)."""
     logits = logits.detach()
     if logits.dim() != 2 or logits.shape[1] > 64:
         raise ValueError("moe_route: logits must be [tokens, experts] with at most 64 experts")
+    if topk != 1:
+        k = moe_topk_check(topk, logits.shape[1])
+        if not _ext.use_kernels(logits):
+            return _moe_route_topk_ref(logits, k)
+        return tuple(_ext.ext().moe_route_topk(logits.contiguous(), k))
     if not _ext.use_kernels(logits):
         return moe_route_ref(logits)
     return tuple(_ext.ext().moe_route(logits.contiguous()))
+
+
+def _moe_combine_kernels(rows, T, R, k, what):
+    """Whether the moe_combine.hip kernels run on ``rows``; a shape they do not take raises."""
+    if not _ext.use_kernels(rows):
+        return False
+    code = {torch.bfloat16: 1, torch.float16: 2}.get(rows.dtype, -1)
+    if rows.dim() != 2 or not _ext.ext().moe_combine_supported(code, T, R, rows.shape[-1], k):
+        raise RuntimeError(f"{what}: the kernel does not take {tuple(rows.shape)} {rows.dtype} with T = {T}, R = {R}, "
+                           f"k = {k} (moe_combine_supported: bf16 / fp16, h a multiple of 8, k <= 8, rows below 2^31)")
+    return True
+
+
+def moe_combine_ref(y, row_of_token, w=None):
+    """Torch twin of ``moe_combine``: an fp32 sum over the k slots, one rounding."""
+    T, k = row_of_token.shape
+    u = y.index_select(0, row_of_token.reshape(-1).long()).view(T, k, -1).float()
+    if w is not None:
+        u = u * w.float().unsqueeze(-1)
+    return u.sum(1).to(y.dtype)
+
+
+def moe_combine(y, row_of_token, w=None):
+    """out[t] = sum_j w[t, j] * y[row_of_token[t, j]] for y [R, h] in the padded layout of
+    ``moe_route(topk=k)``, row_of_token int32 [T, k], w fp32 [T, k] or None for weights of 1:
+    accumulated in fp32 in slot order, rounded once to y's dtype (moe_combine.hip). Not
+    differentiable (``GroupedSwitchExperts`` writes the backward)."""
+    T, k = row_of_token.shape
+    if not _moe_combine_kernels(y, T, y.shape[0], k, "moe_combine"):
+        return moe_combine_ref(y, row_of_token, w)
+    return _ext.ext().moe_combine(y.contiguous(), row_of_token.contiguous(),
+                                  None if w is None else w.float().contiguous())
+
+
+def moe_scatter_scaled_ref(dout, token_of_row, p_of_row):
+    """Torch twin of ``moe_scatter_scaled``."""
+    rows = dout.index_select(0, token_of_row.clamp_min(0)).float() * p_of_row.unsqueeze(-1)
+    return (rows * (token_of_row >= 0).unsqueeze(-1)).to(dout.dtype)
+
+
+def moe_scatter_scaled(dout, token_of_row, p_of_row):
+    """dys[r] = p_of_row[r] * dout[token_of_row[r]] for dout [T, h], zeros on the pad rows
+    (token_of_row -1): the gate-weighted dOut in the padded layout, every row written once."""
+    if not _moe_combine_kernels(dout, dout.shape[0], token_of_row.numel(), 1, "moe_scatter_scaled"):
+        return moe_scatter_scaled_ref(dout, token_of_row, p_of_row)
+    return _ext.ext().moe_scatter_scaled(dout.contiguous(), token_of_row, p_of_row)
+
+
+def moe_gate_grad_ref(dout, y, row_of_token):
+    """Torch twin of ``moe_gate_grad``."""
+    T, k = row_of_token.shape
+    u = y.index_select(0, row_of_token.reshape(-1).long()).view(T, k, -1).float()
+    return (u * dout.float().unsqueeze(1)).sum(-1)
+
+
+def moe_gate_grad(dout, y, row_of_token):
+    """dp[t, j] = <dout[t], y[row_of_token[t, j]]> in fp32 [T, k]: the gradient of the gate weights
+    (one wave per token, no atomics, bitwise repeatable)."""
+    T, k = row_of_token.shape
+    if not _moe_combine_kernels(y, T, y.shape[0], k, "moe_gate_grad"):
+        return moe_gate_grad_ref(dout, y, row_of_token)
+    return _ext.ext().moe_gate_grad(dout.contiguous(), y.contiguous(), row_of_token.contiguous())
 
 
 def gelu_tanh_grad_ref(z):

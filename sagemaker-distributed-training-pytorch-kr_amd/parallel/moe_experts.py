@@ -30,11 +30,21 @@ class GroupedSwitchExperts(torch.autograd.Function):
     an expert without tokens.
 
     ``apply(x [T, h], top_p [T], route, tabs, E, *w1, *b1, *w2, *b2)``: ``route`` the tuple
-    ``SF.moe_route`` returned, ``tabs`` = (fc1 tables, fc2 tables) for the forward or None."""
+    ``SF.moe_route`` returned, ``tabs`` = (fc1 tables, fc2 tables) for the forward or None.
+
+    Top-k (--moe-router-topk, ``route`` the 8-tuple of ``SF.moe_route(topk=k)``, top_p [T, k]): a
+    token owns k rows of the padded buffer. The GEMMs, their tables and the ranged weight
+    gradients are the same; the rows come back through ``SF.moe_combine`` (fp32 weighted sum over
+    the k rows with the route's gate weights), and the backward is ``SF.moe_gate_grad`` for
+    d(top_p), ``SF.moe_scatter_scaled`` for the gate-weighted dOut in the padded layout, and
+    ``SF.moe_combine`` with unit weights for dx (csrc/kernels/moe_combine.hip)."""
 
     @staticmethod
     def forward(ctx, x, top_p, route, tabs, E, *params):
         w1, b1, w2, b2 = (list(params[i * E:(i + 1) * E]) for i in range(4))
+        ctx.topk = len(route) == 8
+        if ctx.topk:
+            return _topk_forward(ctx, x, route, tabs, (w1, b1, w2, b2))
         _, _, row_of_token, token_of_row, tile_expert, seg, _ = route
         kern = _ext.use_kernels(x)
         if kern:
@@ -51,33 +61,69 @@ class GroupedSwitchExperts(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
+        if ctx.topk:
+            return _topk_backward(ctx, dout)
         xs, pre, act, u, top_p, row_of_token, token_of_row, tile_expert, seg = ctx.saved_tensors
-        w1, b1, w2, b2 = ctx.params
-        E = len(w1)
         dprob = (dout * u).sum(-1).to(top_p.dtype)
         du = (dout * top_p.unsqueeze(-1).to(dout.dtype)).contiguous()
         if ctx.kern:
             dys = _ext.ext().gather_rows(du, token_of_row)
-            w2t, w1t = moe_weight_t_tables(w2, b1), moe_weight_t_tables(w1, None)
         else:
             dys = du.index_select(0, token_of_row.clamp_min(0)) * (token_of_row >= 0).unsqueeze(-1).to(du.dtype)
-            w2t = w1t = None
-        b1d = [b.detach() for b in b1]
-        dz = SF.gemm_tn_grouped(dys, w2t[0] if w2t else [w.detach().t().contiguous() for w in w2], tile_expert, 3, b1d,
-                                aux=pre, tables=w2t[1] if w2t else None)[0]
-        dxs = SF.gemm_tn_grouped(dz, w1t[0] if w1t else [w.detach().t().contiguous() for w in w1], tile_expert, 0,
-                                 tables=w1t[1] if w1t else None)[0]
+        dxs, wgrads = _experts_backward(ctx, dys, xs, pre, act, tile_expert, seg)
         dx = dxs.index_select(0, row_of_token)
-        grads = []
-        for ws, bs, g2, t2 in ((w1, b1, dz, xs), (w2, b2, dys, act)):
-            gw, gb = [], []
-            for e in range(E):
-                dw, db = _wgrad_ranged(ws[e], bs[e], g2, t2, seg, e, ctx.kern)
-                gw.append(dw)
-                gb.append(db)
-            grads.append((gw, gb))
-        (gw1, gb1), (gw2, gb2) = grads
-        return (dx, dprob, None, None, None, *gw1, *gb1, *gw2, *gb2)
+        return (dx, dprob, None, None, None, *wgrads)
+
+
+def _experts_backward(ctx, dys, xs, pre, act, tile_expert, seg):
+    """From dys (dOut in the padded layout, gate weight applied): the two grouped dgrads and the
+    2 E ranged weight gradients. Returns (dxs, [*gw1, *gb1, *gw2, *gb2])."""
+    w1, b1, w2, b2 = ctx.params
+    if ctx.kern:
+        w2t, w1t = moe_weight_t_tables(w2, b1), moe_weight_t_tables(w1, None)
+    else:
+        w2t = w1t = None
+    b1d = [b.detach() for b in b1]
+    dz = SF.gemm_tn_grouped(dys, w2t[0] if w2t else [w.detach().t().contiguous() for w in w2], tile_expert, 3, b1d,
+                            aux=pre, tables=w2t[1] if w2t else None)[0]
+    dxs = SF.gemm_tn_grouped(dz, w1t[0] if w1t else [w.detach().t().contiguous() for w in w1], tile_expert, 0,
+                             tables=w1t[1] if w1t else None)[0]
+    grads = []
+    for ws, bs, g2, t2 in ((w1, b1, dz, xs), (w2, b2, dys, act)):
+        gw, gb = [], []
+        for e in range(len(w1)):
+            dw, db = _wgrad_ranged(ws[e], bs[e], g2, t2, seg, e, ctx.kern)
+            gw.append(dw)
+            gb.append(db)
+        grads += gw + gb
+    return dxs, grads
+
+
+def _topk_forward(ctx, x, route, tabs, params):
+    """``GroupedSwitchExperts.forward`` on a top-k route: out[t] = sum_j p[t, j] * y[row[t, j]]."""
+    w1, b1, w2, b2 = params
+    top_p, _, row_of_token, token_of_row, tile_expert, seg, _, p_of_row = route
+    kern = _ext.use_kernels(x)
+    if kern:
+        xs = _ext.ext().gather_rows(x.contiguous(), token_of_row)
+    else:
+        xs = x.index_select(0, token_of_row.clamp_min(0)) * (token_of_row >= 0).unsqueeze(-1).to(x.dtype)
+    pre, act = SF.gemm_tn_grouped(xs, w1, tile_expert, 2, b1, tables=tabs[0] if tabs else None)
+    y = SF.gemm_tn_grouped(act, w2, tile_expert, 1, b2, tables=tabs[1] if tabs else None)[0]
+    ctx.save_for_backward(xs, pre, act, y, row_of_token, token_of_row, tile_expert, seg, p_of_row)
+    ctx.params = params
+    ctx.kern = kern
+    return SF.moe_combine(y, row_of_token, top_p)
+
+
+def _topk_backward(ctx, dout):
+    xs, pre, act, y, row_of_token, token_of_row, tile_expert, seg, p_of_row = ctx.saved_tensors
+    dout = dout.contiguous()
+    dprob = SF.moe_gate_grad(dout, y, row_of_token)
+    dys = SF.moe_scatter_scaled(dout, token_of_row, p_of_row)
+    dxs, wgrads = _experts_backward(ctx, dys, xs, pre, act, tile_expert, seg)
+    dx = SF.moe_combine(dxs, row_of_token)
+    return (dx, dprob, None, None, None, *wgrads)
 
 
 def _wgrad_ranged(weight, bias_p, g2, t2, seg, e, kern):

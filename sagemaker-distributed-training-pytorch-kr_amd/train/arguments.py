@@ -186,6 +186,12 @@ _GROUPS = {
         # ours (Megatron-core's name): the Switch MLP of --num-experts with device routing and
         # grouped expert GEMMs, no host sync (models/transformer.SwitchMLP, opt-in)
         ("--moe-grouped-gemm", dict(action="store_true")),
+        # ours (Megatron-core's name): experts per token of the --num-experts MLP
+        ("--moe-router-topk", dict(type=int, default=1, help=(
+            "experts per token, 1 .. min(8, --num-experts). k >= 2: the k largest router logits (a tie to the "
+            "lower index), gate weights the softmax over those k logits (Megatron-core's default, Mixtral's rule). "
+            "k = 1 (default) keeps the Switch rule: the softmax probability over all experts, not renormalised. "
+            "No auxiliary load-balancing loss, capacity limit, token dropping or expert-parallel group."))),
     ],
     "distributed": [
         ("--tensor-model-parallel-size", dict(type=int, default=1)),
@@ -535,6 +541,12 @@ def validate_args(args, defaults=None):
     assert args.seq_length is not None and args.max_position_embeddings >= args.seq_length
     if args.ffn_hidden_size is None:
         args.ffn_hidden_size = 4 * args.hidden_size if not args.swiglu else int(8 * args.hidden_size / 3)
+    if getattr(args, "moe_router_topk", 1) != 1:
+        if not args.num_experts:
+            raise ValueError("--moe-router-topk needs --num-experts")
+        if not 1 <= args.moe_router_topk <= min(8, args.num_experts):
+            raise ValueError(f"--moe-router-topk must be in 1 .. min(8, --num-experts = {args.num_experts}), got "
+                             f"{args.moe_router_topk}")
     if getattr(args, "moe_grouped_gemm", False):
         # the grouped Switch path (moe_experts.GroupedSwitchExperts): what it cannot run is refused here
         if not args.num_experts:
@@ -641,6 +653,7 @@ def core_transformer_config_from_args(args) -> TransformerConfig:
         init_method="xavier_uniform" if args.init_method_xavier_uniform else "normal",
         layernorm_zero_centered_gamma=args.apply_layernorm_1p, num_experts=args.num_experts,
         moe_grouped_gemm=bool(getattr(args, "moe_grouped_gemm", False)),
+        moe_router_topk=int(getattr(args, "moe_router_topk", 1)),
         apply_residual_connection_post_layernorm=args.apply_residual_connection_post_layernorm,
         perform_initialization=args.perform_initialization,
         use_cpu_initialization=bool(args.use_cpu_initialization),
